@@ -13,24 +13,28 @@ joins the ranks it is given.  The batch shards embarrassingly -- rank r simulate
 each step with no data-path collective (weak scaling); `--gather summary|trials` adds the RCCL all-gather that
 reassembles a training minibatch (north_star) to the timed region.
 
-Rank 0 prints ONE JSON line (contract in the task description) with extra objects:
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (the wall time of one timed step), the
+config, and the objects that cost no run of their own:
   roofline      HBM view of the dominant kernel (algorithmic bytes / measured kernel time vs 8 TB/s) -- tiny by
                 construction: 8 B are written per trial for ~246 Gaussian draws
+  dist          (any line with a process group) who ran it: backend, RCCL version, one entry per rank (device, PCI bus id, kernel ms,
+                elapsed, host prior seconds), imbalance = slowest / fastest
+  toolchain     HIP runtime actually loaded, hipcc, torch, RCCL, rocRAND
+A plain run does nothing else: set up, warm up, time --steps steps, write --dump-outputs if asked, print the line.  `--full` adds,
+each outside the headline's timed region:
   roofline_valu the binding resource, vector-ALU issue, against two ceilings: (i) the same kernel's step loop with
                 every lane useful, MEASURED in this run (a lockstep workload, outside the timed region); (ii) the ISA-level
                 issue model of the shipped library (tools/isa_mix.py x tools/ubench_valu, profiles/*_issue_model.json)
   cpu_baseline  the CPU oracle (C restatement, same Philox stream) timed on this box's host cores on a bounded
                 sample of the same workload; plus the pure-Python/NumPy port the reference runs without numba
-
-  legs          (N = 1, default command) the OTHER BASELINE configs under the same command and clock, each outside the headline's timed
+  occupancy, ks_vs_ref, packed_gauss   (N = 1) resident waves, KS against the reference fixtures, the opt-in packed transform
+  legs          (N = 1) the OTHER BASELINE configs under the same command and clock, each outside the headline's timed
                 region: `single` = configs[3] (trials + fused summaries, and summaries alone), `alpha_ns_bridge` = configs[2], `train` =
                 configs[4] (GraphTrainer at one rank and in the RCCL all-gather form, both step sizes); each with rate, kernel time,
                 KS + bar, roofline_valu
-  dist          (any line with a process group) who ran it: backend, RCCL version, one entry per rank (device, PCI bus id, kernel ms,
-                elapsed, host prior seconds), imbalance = slowest / fastest
-  side_legs     (process group, default command) short timed passes the weak-scaling headline leaves out: the minibatch all-gather of
+  side_legs     (process group) short timed passes the weak-scaling headline leaves out: the minibatch all-gather of
                 the summaries and of the 2-byte codes (north_star's collective), and the strong-scaling point (1M sets in total)
-  toolchain     HIP runtime actually loaded, hipcc, torch, RCCL, rocRAND
+  dist.gathered_over_plain_same_process   (--dist at world 1 with a gather; any world with --compare-plain) gathered / plain rate
 
 `--train` measures BASELINE config 5 instead (online simulation feeding the PyTorch-ROCm amortizer): iterations/s,
 microseconds per simulate launch (eager and hipGraph), simulator share of a step, prefetch on/off.
@@ -72,7 +76,7 @@ def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # (defaults: 6.6 s of GPU time at the headline shape -- 32 ms per step -- so that the timed region is long against launch
-    #  jitter and visible to a coarse utilisation sampler; the CPU-baseline legs beside it take ~55 s)
+    #  jitter and visible to a coarse utilisation sampler; under --full the CPU-baseline legs beside it take ~55 s)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sets", type=int, default=1_000_000, help="parameter sets per GPU per step")
@@ -99,7 +103,7 @@ def parse():
     ap.add_argument("--no-ks", action="store_true")
     ap.add_argument("--no-ceiling", action="store_true", help="skip the lockstep run that measures the VALU ceiling")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the side legs of the default line: at N = 1 the other BASELINE configs (single-trial + fused summaries, "
+                    help="skip the side legs of the --full line: at N = 1 the other BASELINE configs (single-trial + fused summaries, "
                          "alpha_not_scaled with the bridge, the config-5 training loop), at N > 1 the all-gather and strong-scaling legs")
     ap.add_argument("--leg-launches", type=int, default=4, help="timed launches per simulator side leg (a leg whose launch is under 15 ms times four times as many: the first launches of a short "
                          "sample run while the clocks settle; every launch's time is in the leg's launch_ms)")
@@ -131,6 +135,19 @@ def parse():
     ap.add_argument("--train", action="store_true", help="BASELINE config 5: online simulation feeding the amortizer")
     ap.add_argument("--train-iters", type=int, default=150)
     ap.add_argument("--batch", type=int, default=32, help="--train: parameter sets per rank per training step")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline, each outside its timed region: the VALU roofline with its lockstep ceiling, "
+                         "occupancy, KS against the reference fixtures, the packed transform, the side legs (the other BASELINE configs "
+                         "at N = 1; the all-gather and strong-scaling legs with a process group), the gathered-over-plain comparison "
+                         "and the CPU baseline.  Without it a run sets up, warms up, times --steps steps and prints the line "
+                         "(the --no-* options above narrow what --full adds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed on rank 0 as DIR/<name>.npy: summary.npy (the "
+                         "fused summaries, f32[B,10]) and trials.npy (the (rt, choice) pairs, f32[B,N,2]; trial_codes.npy for an "
+                         "ungathered --gather codes run), all finite: where the library writes NaN by contract (the RT mean / variance "
+                         "of a set without such trials) the file holds 0 and <name>_finite.npy (1 = the library's value, 0 = NaN) "
+                         "says so.  56 MB at most: a larger output is cut to a fixed sample of parameter sets (numpy default_rng(0), "
+                         "sorted), whose indices go to summary_sets.npy / trial_sets.npy (float64)")
     return ap.parse_args()
 
 
@@ -279,8 +296,8 @@ def plan(a):
     out["plain_command"] = {
         "gather": "none",
         "why": "the path shards with no data-path collective (basic_ddm_dc.py:121-122: sets are independent): the driver's plain `bench.py "
-               "--gpus N` measures weak scaling of the simulator itself; north_star's minibatch all-gather is measured by the line's "
-               "side_legs (gather_summary, gather_codes: the two forms that stay hidden behind the simulate) and by --gather",
+               "--gpus N` measures weak scaling of the simulator itself; north_star's minibatch all-gather is measured by the --full "
+               "line's side_legs (gather_summary, gather_codes: the two forms that stay hidden behind the simulate) and by --gather",
         "side_legs": {g: {"allocated_bytes_per_rank": out["gather"][g]["allocated_bytes_per_rank"] if g in out["gather"] else None,
                           "runs_if_free_memory_exceeds": None if g not in out["gather"] else
                           1.25 * side_leg_need(W, B, N, g) + (1 << 30)} for g in ("summary", "codes")},
@@ -710,7 +727,52 @@ def simulate_pass(a, ctx, p_dev, B, gather, steps, warmup, first_step=0, summary
     last = (first_step + warmup + steps - 1) % nbuf       # the buffers the last step wrote
     return {"elapsed": elapsed, "elapsed_local": elapsed_local, "kernel_ms": float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev])),
             "trials": buf_trials[last], "summary": buf_summary[last], "geometry": geometry, "overlap": overlap, "codes": codes,
+            "trial_codes": buf_codes[last] if codes else None, "gathered": gathered[last] if gathered else None,
             "step": step, "last_step": first_step + warmup + steps - 1, "allocated_bytes": allocated}
+
+
+DUMP_TRIALS_BYTES, DUMP_SUMMARY_BYTES = 16_000_000, 40_000_000     # --dump-outputs: 56 MB at most, masks and sample indices included
+
+
+def dump_outputs(a, ctx, run):
+    """--dump-outputs DIR: what the last timed step computed on this rank, as float32 .npy files (after the timed region).  The trials
+    of a run whose floats exist only after the gather (--gather codes) are rank 0's rows of the decoded minibatch.  Every file is
+    finite: where the library writes NaN by contract (include/nddm.h: the mean / variance of the RTs of a set with no responded, or
+    no upper-boundary, trial) the value file holds 0 and <name>_finite.npy, 1 where the value is the library's and 0 where it wrote a
+    non-finite value, says so -- element for element, so two builds are compared on where they write NaN as well."""
+    torch, rank = ctx["torch"], ctx["rank"]
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    if run["codes"] and run["gathered"] is not None:
+        trials, tname = run["gathered"][rank], "trials"
+    elif run["codes"]:
+        trials, tname = run["trial_codes"], "trial_codes"
+    else:
+        trials, tname = run["trials"], "trials"
+    arrays = [("summary", run["summary"], DUMP_SUMMARY_BYTES)] + ([(tname, trials, DUMP_TRIALS_BYTES)] if trials is not None else [])
+    written = []
+    for name, t, budget in arrays:
+        if t.dtype == torch.int16:                   # the 2-byte wire format is unsigned
+            t = t.to(torch.int32) & 0xFFFF
+        t = t.float()
+        masked = not bool(torch.isfinite(t).all())   # a mask of the same shape goes beside the values
+        B, row = t.shape[0], t[0].numel() * 4 * (2 if masked else 1)
+        if B * row <= budget:
+            x = t
+        else:                                        # a fixed sample of the parameter sets, index array beside it
+            S = max(1, budget // (row + 8))
+            idx = np.sort(np.random.default_rng(0).choice(B, size=S, replace=False))
+            x = t.index_select(0, torch.as_tensor(idx, device=t.device))
+            sets = ("trial_sets" if name != "summary" else "summary_sets")
+            np.save(os.path.join(a.dump_outputs, sets + ".npy"), idx.astype(np.float64))
+            written.append(sets)
+        if masked:
+            finite = torch.isfinite(x)
+            np.save(os.path.join(a.dump_outputs, name + "_finite.npy"), finite.float().cpu().numpy())
+            x = torch.where(finite, x, torch.zeros_like(x))
+            written.append(name + "_finite")
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), x.cpu().numpy())
+        written.append(f"{name}{list(x.shape)}")
+    print(f"bench.py: --dump-outputs {a.dump_outputs}: {', '.join(written)}", file=sys.stderr, flush=True)
 
 
 def rank_identity(a, ctx, t_prior, run):
@@ -1041,9 +1103,11 @@ def simulate_bench(a, ctx):
     elapsed, kern_ms, geometry, overlap, codes, step = (run[k] for k in ("elapsed", "kernel_ms", "geometry", "overlap", "codes", "step"))
     out_trials, out_summary = run["trials"], run["summary"]
     # ---- everything below is OUTSIDE the headline's timed region
+    if a.dump_outputs and rank == 0:                 # (before anything else writes into the last step's buffers)
+        dump_outputs(a, ctx, run)
     ident = rank_identity(a, ctx, t_prior, run) if dist_on else None            # (a collective: every rank takes part)
     pass_allocated = run["allocated_bytes"]
-    if dist_on and a.gather != "none" and ((a.dist and world == 1 and not a.no_plain_compare) or a.compare_plain):
+    if dist_on and a.gather != "none" and ((a.full and a.dist and world == 1 and not a.no_plain_compare) or a.compare_plain):
         # The gathered pass against the plain one IN THIS PROCESS, interleaved (gathered, plain, gathered, plain, ...): the ratio
         # the correctness suite used to take between two separately launched processes -- where one hiccup of the box read as a
         # 27 % gap in round 5 (gpurun_out/r5/gpu_suite1.log) -- reported here as a number, asserted nowhere.
@@ -1060,7 +1124,7 @@ def simulate_bench(a, ctx):
                                                      "what": "this line's pass (process group, all-gather on the communication stream) and the "
                                                              "plain pass, interleaved in one process; median over median"}
     side = {}
-    if dist_on and not a.no_legs and a.model == "basic" and not a.summary_only and a.gather == "none":
+    if a.full and dist_on and not a.no_legs and a.model == "basic" and not a.summary_only and a.gather == "none":
         # What the default multi-GPU command leaves out, as short timed passes of the same code (every rank takes part): north_star's
         # minibatch all-gather in its two practical forms, and the strong-scaling point (a FIXED 1M-set batch split over the ranks)
         del run
@@ -1148,7 +1212,7 @@ def simulate_bench(a, ctx):
         # the per-kernel analysis belongs to the one-GPU line: these objects are measured at N = 1 only (their absence here is
         # by design, not a failure); `roofline` (the contract's object) and `launch` are on every line
         res["n1_only"] = ["roofline_valu", "occupancy", "ks_vs_ref", "packed_gauss", "cpu_baseline", "gpu_over_cpu_1core", "legs"]
-    if world == 1:
+    if world == 1 and a.full:
         achieved_steps = em_steps / (kern_ms * 1e-3)
         simds = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
         spb = 8 if (packed or bridge) else 4         # Euler-Maruyama steps per pass of the step loop (packed: one Philox block; bridge: two + one of crossing uniforms)
@@ -1485,6 +1549,8 @@ def main():
         sys.exit("--gpus must be >= 1")
     if a.plan:
         return plan(a)
+    if a.dump_outputs and a.train:
+        sys.exit("--dump-outputs writes the simulator line's outputs: not with --train")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         if not a.share_device:
             have = visible_gpus()

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                         "--sets", "30000", "--cpu-seconds", "0.5", "--cpu-sample", "--leg-launches", "2", "--leg-train-iters", "40"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -100,7 +100,7 @@ def _check_legs(d):
 def test_bench_other_models_carry_the_same_objects(model):
     """configs[2] / configs[3] are measured the way configs[1] is: KS against the reference fixtures, CPU oracle
     baseline of the same model, lockstep ceiling."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", model, "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", model, "--steps", "2", "--warmup", "1", "--full",
                         "--sets", "30000", "--cpu-seconds", "0.5", "--cpu-sample"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -134,7 +134,7 @@ def test_bench_many_ranks_rehearsal_names_what_an_n_gpu_line_omits():
     parameter draw on standard error, rank 0 prints ONE line with n_gpus 5 -- and, because the per-kernel analysis
     (roofline_valu, KS, CPU baseline ...) is measured at N = 1 only, the line NAMES the objects it omits (`n1_only`)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = _bench("--gpus", "5", "--share-device", "--backend", "gloo", "--sets", "20000", "--steps", "3", "--warmup", "1", env=env)
+    r = _bench("--gpus", "5", "--share-device", "--backend", "gloo", "--sets", "20000", "--steps", "3", "--warmup", "1", "--full", env=env)
     d = _one_line(r)
     assert d["n_gpus"] == 5 and d["scaling"] == "weak" and "roofline" in d and "launch" in d
     # the line says WHO ran it: the backend the process group reports, one entry per rank with its device and its own times
@@ -173,7 +173,7 @@ def test_bench_rccl_branch_runs_at_world_1(gather):
     the device-side all_reduce(MAX) of the elapsed time -- every distributed call `bench.py --gpus 8` makes.  The line says
     n_gpus 1 and its value is the plain run's (the collective of one rank is a copy, overlapped with the next simulate)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    common = ["--sets", "300000", "--steps", "6", "--warmup", "2", "--no-ceiling", "--no-ks", "--no-cpu-baseline", "--no-legs"]
+    common = ["--sets", "300000", "--steps", "6", "--warmup", "2", "--full", "--no-ceiling", "--no-ks", "--no-cpu-baseline", "--no-legs"]
     d = _one_line(_bench("--dist", "--backend", "nccl", "--gather", gather, *common, env=env))
     assert d["n_gpus"] == 1 and "distributed code path forced at world 1 (nccl)" in d["config"]["parallelism"]
     assert d["dist"]["backend"] == "nccl" and d["dist"]["rccl_version"] and d["dist"]["world"] == 1 and d["dist"]["ranks"][0]["pci_bus_id"]
@@ -194,7 +194,7 @@ def test_bench_rccl_branch_runs_at_world_1(gather):
     if gather == "summary":
         # the driver's PLAIN command over RCCL (gather none): the line carries the all-gather and strong-scaling side legs, and -- at
         # world 1 -- the N = 1 legs too, whose RCCL training form joins the process group that is already up
-        f = _one_line(_bench("--dist", "--backend", "nccl", "--sets", "30000", "--steps", "2", "--warmup", "1", "--no-ceiling", "--no-ks",
+        f = _one_line(_bench("--dist", "--backend", "nccl", "--sets", "30000", "--steps", "2", "--warmup", "1", "--full", "--no-ceiling", "--no-ks",
                              "--no-cpu-baseline", "--leg-launches", "1", "--leg-train-iters", "30", env=env))
         assert f["dist"]["backend"] == "nccl" and set(f["side_legs"]) == {"gather_summary", "gather_codes", "strong"}
         assert all(v["value"] > 0 and v["kernel_ms"] > 0 for v in f["side_legs"].values()) and f["side_legs"]["strong"]["sets_total"] == 30000
@@ -307,3 +307,34 @@ def test_two_fresh_ranks_union_equals_unsharded(tmp_path):
     assert shards[0]["none"]["rows"] == (0, 501) and shards[1]["none"]["rows"] == (501, 1001)
     assert torch.equal(torch.cat([sh["none"]["trials"] for sh in shards]), ft)
     assert torch.equal(torch.nan_to_num(torch.cat([sh["none"]["summary"] for sh in shards])), fs)
+
+
+def test_bench_plain_line_is_the_headline_and_dumps_what_its_last_step_computed(tmp_path):
+    """Without --full the line is the headline alone (no extra runs: no lockstep ceiling, KS, legs or CPU baseline), and --dump-outputs
+    writes what the last timed step computed: the same floats as that step's launch repeated in this process, bit for bit, in files that
+    are all finite -- where the library writes NaN by contract the value is 0 and <name>_finite.npy marks it."""
+    B, N, steps, warmup = 30000, 300, 3, 2
+    out = tmp_path / "out"
+    d = _one_line(_bench("--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--sets", str(B), "--dump-outputs", str(out)))
+    assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "trials/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - B * N / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert not {"roofline_valu", "occupancy", "ks_vs_ref", "packed_gauss", "legs", "cpu_baseline"} & set(d)
+    import numpy as np
+    import torch
+    from bayesflow_nddms_amd import engine
+    from bayesflow_nddms_amd import priors
+    summary, trials = np.load(out / "summary.npy"), np.load(out / "trials.npy")
+    assert summary.dtype == trials.dtype == np.float32 and summary.shape == (B, engine.SUMMARY_K)
+    rows = np.load(out / "trial_sets.npy").astype(np.int64)                 # (B x N x 8 bytes is above the budget: a fixed sample)
+    assert trials.shape == (len(rows), N, 2) and 0 < len(rows) < B and np.all(np.diff(rows) > 0)
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 56_000_000 + 4096
+    assert all(np.isfinite(np.load(f)).all() for f in out.iterdir())
+    p = torch.as_tensor(priors.basic_prior_matrix(B, 2023)).cuda()
+    r = engine.simulate(engine.BASIC_DDM_DC, p, N, dt=0.001, max_steps=4000.0, seed=2023, set_offset=(warmup + steps - 1) * B, fast=True)
+    rs, rt = r["summary"].cpu().numpy(), r["trials"].cpu().numpy()[rows]
+    for want, name, got in ((rs, "summary", summary), (rt, "trials", trials)):
+        fin = np.isfinite(want)
+        mask = np.load(out / f"{name}_finite.npy") if (out / f"{name}_finite.npy").exists() else np.ones_like(got)
+        assert mask.dtype == np.float32 and np.array_equal(mask, fin.astype(np.float32)), name
+        assert np.all(got[~fin] == 0) and np.array_equal(want[fin].view(np.uint32), got[fin].view(np.uint32)), name
+    assert not np.isfinite(rs).all()              # (this batch has sets without an upper-boundary trial: the mask is exercised)

@@ -16,7 +16,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$ROOT"
 PY=$(readlink -f "$(command -v python3)")
-ARGS="--steps 5 --warmup 1 --no-cpu-baseline --no-ks --no-legs $*"       # (the headline kernel alone; the legs have a trace pass of their own below)
+ARGS="--steps 5 --warmup 1 --full --no-cpu-baseline --no-ks --no-legs $*"       # (the headline kernel and its lockstep ceiling; the legs have a trace pass of their own below)
 echo "$PY bench.py $ARGS" > "$OUT/command.txt"
 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o bench --output-format csv -- "$PY" bench.py $ARGS > "$OUT/bench_trace.json" 2> "$OUT/trace.err" || { tail -5 "$OUT/trace.err"; exit 1; }
 i=0
@@ -30,7 +30,7 @@ for PMC in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR S
 done
 # the default command WITH its side legs (every BASELINE config in one trace): tools/legs_trace_summary.py
 if [ -z "$*" ]; then
-  LEGS="--steps 5 --warmup 1 --no-cpu-baseline --no-ks --no-ceiling"
+  LEGS="--steps 5 --warmup 1 --full --no-cpu-baseline --no-ks --no-ceiling"
   echo "$PY bench.py $LEGS" > "$OUT/command_legs.txt"
   rocprofv3 --kernel-trace --stats -d "$OUT/trace_legs" -o bench --output-format csv -- "$PY" bench.py $LEGS > "$OUT/bench_trace_legs.json" 2> "$OUT/trace_legs.err" || { tail -5 "$OUT/trace_legs.err"; }
 fi

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/art
 mkdir -p "$OUT"
 cd "$ROOT"
-run() { name=$1; shift; python3 bench.py "$@" > "$OUT/$name" 2> "$OUT/$name.err" && echo "ok $name" || { echo "FAILED $name"; tail -3 "$OUT/$name.err"; }; }
+run() { name=$1; shift; python3 bench.py --full "$@" > "$OUT/$name" 2> "$OUT/$name.err" && echo "ok $name" || { echo "FAILED $name"; tail -3 "$OUT/$name.err"; }; }
 run r6_bench_basic.json
 run r6_bench_single.json --model single
 run r6_bench_alpha_ns.json --model alpha_ns
@@ -20,8 +20,8 @@ run r6_bench_dist_trials_world1.json --dist --backend nccl --gather trials --no-
 run r6_bench_dist_codes_world1.json --dist --backend nccl --gather codes --no-ceiling --no-ks --no-cpu-baseline
 run r6_train_gather_world1.json --train --dist --backend nccl --train-mode graph
 run r6_train_ddp_world1.json --train --dist --backend nccl --train-mode graph --train-parallel ddp
-python3 bench.py --gpus 5 --share-device --backend gloo --sets 100000 --steps 3 --warmup 1 > "$OUT/r6_five_rank_none.log" 2>&1 && echo "ok five_rank_none"
-python3 bench.py --gpus 2 --share-device --backend gloo --sets 100000 --steps 3 --warmup 1 --no-cpu-baseline --no-ks --no-ceiling > "$OUT/r6_two_rank_none.log" 2>&1 && echo "ok two_rank_none"
+python3 bench.py --gpus 5 --share-device --backend gloo --sets 100000 --steps 3 --warmup 1 --full > "$OUT/r6_five_rank_none.log" 2>&1 && echo "ok five_rank_none"
+python3 bench.py --gpus 2 --share-device --backend gloo --sets 100000 --steps 3 --warmup 1 --full --no-cpu-baseline --no-ks --no-ceiling > "$OUT/r6_two_rank_none.log" 2>&1 && echo "ok two_rank_none"
 python3 bench.py --gpus 2 --share-device --backend gloo --sets 100000 --steps 3 --warmup 1 --no-cpu-baseline --no-ks --no-ceiling --gather summary > "$OUT/r6_two_rank_summary.log" 2>&1 && echo "ok two_rank_summary"
 python3 bench.py --gpus 2 --share-device --backend gloo --sets 100000 --steps 3 --warmup 1 --no-cpu-baseline --no-ks --no-ceiling --gather trials > "$OUT/r6_two_rank_trials.log" 2>&1 && echo "ok two_rank_trials"
 python3 bench.py --gpus 2 --share-device --backend gloo --train --train-iters 60 > "$OUT/r6_two_rank_train.log" 2>&1 && echo "ok two_rank_train"
@@ -36,7 +36,7 @@ python3 tools/probe_stream_validation.py > "$OUT/r6_stream_validation.txt" 2>/de
 python3 tools/probe_graph_memset_node.py 2>&1 | grep -v "amdgpu.ids" > "$OUT/r6_probe_graph_memset_node.txt" && echo "ok probe_graph_memset_node"
 (hipcc -O3 --offload-arch=gfx950 -o /tmp/probe_b128 tools/probe_buffer_load_b128.hip 2>/dev/null && /tmp/probe_b128) > "$OUT/r6_probe_buffer_load_b128.txt" 2>&1 && echo "ok probe_buffer_load_b128"
 python3 tools/fused_accuracy.py 2>&1 | grep -v "amdgpu.ids" > "$OUT/r6_fused_accuracy.txt" && echo "ok fused_accuracy"
-python3 bench.py --dist --backend nccl > "$OUT/r6_bench_dist_none_world1.json" 2> "$OUT/r6_bench_dist_none_world1.err" && echo "ok dist_none_world1"
+python3 bench.py --full --dist --backend nccl > "$OUT/r6_bench_dist_none_world1.json" 2> "$OUT/r6_bench_dist_none_world1.err" && echo "ok dist_none_world1"
 # (the whole training runs + recovery on the reference's statistic + the tail-draw traces: ~6 min)
 # python3 tools/full_training_run.py 500 basic gpurun_out/basic_500.pt > "$OUT/r6_full_training_run.txt"; python3 tools/locate_tail_draws.py gpurun_out/basic_500.pt basic 500 100000 > "$OUT/r6_tail_draw_incidence.txt"
 python3 tools/resource_table.py --train --md > "$OUT/r6_train_resource_table.md" 2>/dev/null && echo "ok train_resource_table"
