@@ -89,3 +89,25 @@ def generate_data(test_num=2, nparts=100, ntrials=100, seed=2021, dt=.001, max_s
                     participant=np.repeat(np.arange(1, nparts + 1), ntrials).astype(np.float64),
                     nparts=nparts, ntrials=ntrials, N=N)
     return genparam
+
+
+def log_likelihood(params, y, per_trial=False):
+    """log p(y | params) of the generator's model (drift ~ N(Nu, Eta) integrated out, Nu clipped to +-5 as the generator does), one
+    launch: params [R, 6] (or [6]) = Nu, Alpha, Beta, Tau, Eta, Varsigma; y [D, n_trials] (or [n_trials]) the signed RTs
+    (y = +-rt, positive = upper boundary; alpha_not_scaled.py:98-100), R = D * S -- row r is scored against data set r // S.  y == 0
+    (the Euler-Maruyama form's timeout) carries no time and gives NaN.  Returns float64 [R] on the device (and float32 [R, n_trials]
+    per-trial values with per_trial=True)."""
+    p = params if hasattr(params, "is_cuda") else np.asarray(params, dtype=np.float64).reshape(-1, 6)
+    if hasattr(y, "is_cuda"):
+        import torch
+        yy = y[None] if y.ndim == 1 else y
+        d = torch.stack([yy, (torch.sign(yy) + 1) / 2], -1)
+    else:
+        yy = np.asarray(y, dtype=np.float64)
+        yy = yy[None] if yy.ndim == 1 else yy
+        d = np.stack([yy, (np.sign(yy) + 1) / 2], -1)
+    R, D = (p.shape[0] if p.ndim == 2 else 1), d.shape[0]
+    if R % D:
+        raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
+    r = engine.wiener_log_likelihood(engine.ALPHA_NOT_SCALED, p, d, draws_per_dataset=R // D, per_trial=per_trial)
+    return (r["loglik"], r["trial_logp"]) if per_trial else r["loglik"]

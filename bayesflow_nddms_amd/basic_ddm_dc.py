@@ -90,3 +90,18 @@ def make_generative_model(batched=True, device_prior=False, dt=.01, max_steps=40
     # how a graph loop re-creates this model on the device (amortizer.Trainer(graph=True) -> graph_trainer.GraphTrainer)
     gm.graph_spec = dict(model="basic", dt=dt, max_steps=max_steps, seed=2023 if seed is None else seed, n_min=60, n_max=300)
     return gm
+
+
+def log_likelihood(params, sim_data, per_trial=False):
+    """log p(sim_data | params) under the Wiener first-passage density, one launch (engine.wiener_log_likelihood): params [R, 5] (or
+    [5]), sim_data [D, n_trials, 2] (or [n_trials, 2]) = (rt, choice) as simulate_trials writes it, R = D * S -- row r is scored
+    against data set r // S.  A timeout (choice 0) counts as right-censored, log P(T > rt - tau).  Returns float64 [R] on the device
+    (and float32 [R, n_trials] per-trial values with per_trial=True)."""
+    p = params if hasattr(params, "is_cuda") else np.asarray(params, dtype=np.float64).reshape(-1, 5)
+    d = sim_data if hasattr(sim_data, "is_cuda") else np.asarray(sim_data, dtype=np.float64)
+    R = p.shape[0] if p.ndim == 2 else 1
+    D = d.shape[0] if d.ndim == 3 else 1
+    if R % D:
+        raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
+    r = engine.wiener_log_likelihood(MODEL, p, d, draws_per_dataset=R // D, per_trial=per_trial)
+    return (r["loglik"], r["trial_logp"]) if per_trial else r["loglik"]

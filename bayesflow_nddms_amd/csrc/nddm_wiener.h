@@ -1,0 +1,274 @@
+// nddm_wiener.h -- batched Wiener first-passage log-likelihood (gfx950): the density the reference's likelihood-based fits
+// evaluate, JAGS dwiener(alpha/varsigma, ndt, beta, delta/varsigma) (basic_ddm_dc_pyjags.py:129-133, alpha_not_scaled.py:170-176,
+// jagscode/*.jags) and Stan wiener_lpdf behind diffusion_lpdf (basic_ddm_dc_pystan2.py:119-131, stancode/basic_ddm_dc_test.stan),
+// one independent value per (parameter row, trial).  Included by nddm_kernels.hip (one translation unit).  DESIGN.md section 11.
+//
+// Conventions (the reference's): the evidence starts at beta*a and drifts toward the upper boundary; choice 1 / y > 0 is the upper
+// boundary.  Diffusion coefficient s: a' = a/s, v' = v/s, eta' = eta/s.  The lower boundary takes (v', w = beta), the upper one the
+// same formula with (-v', 1 - beta).  t = rt - tau, u = t / a'^2.  With the drift v ~ N(nu, eta^2) integrated out in closed form
+// (Ratcliff 1978; Blurton et al. 2017):
+//     log f(t) = log g(u; w) - 2 log a' + (eta'^2 a'^2 w^2 - 2 a' nu' w - nu'^2 t) / (2 (1 + eta'^2 t)) - 1/2 log(1 + eta'^2 t)
+// (eta = 0: the ordinary -a'v'w - v'^2 t / 2), g the standard first-passage density (Navarro & Fuss 2009) in one of two forms:
+//     small time  g = (2 pi u^3)^-1/2 sum_{k=-2..2} (w + 2k) exp(-(w + 2k)^2 / (2u))                         for u <  WIENER_U_STAR
+//     large time  g = pi sum_{k=1..3} k exp(-k^2 pi^2 u / 2) sin(k pi w)                                      for u >= WIENER_U_STAR
+// both FIXED-TRIP (5 and 3 terms: relative truncation error <= 2e-10 for u <= 0.40 and <= 1e-10 for u >= 0.35 over w in
+// [0.001, 0.999]; tests/test_wiener_host.py) and both in the log domain, the leading exponent taken out:
+//     small: log g = -1/2 log(2 pi) - 3/2 log u - w^2 / (2u) + log(w + (w-2) A + (w+2) B + (w-4) A^3 B + (w+4) A B^3),
+//            A = exp(-2 (1-w) / u), B = exp(-2 (1+w) / u)   (the k = -+2 exponents are A^3 B and A B^3: two exponentials)
+//     large: log g = log pi + log sin(pi w) - pi^2 u / 2 + log(1 + 4c q^3 + 3 (4c^2 - 1) q^8),  c = cos(pi w), q = exp(-pi^2 u / 2)
+//            (sin 2x / sin x = 2 cos x, sin 3x / sin x = 4 cos^2 x - 1: one sin / cos per row and boundary, one exponential per trial)
+// A per-lane select between the two, no loop: 3 v_exp_f32, 2 v_log_f32 and 1 v_rcp_f32 per trial (+ 1 of each with eta > 0).
+//
+// Special values (the math, none an error): t <= 0 (an RT at or below tau) gives -inf; a row with a non-finite parameter, a <= 0,
+// s <= 0, beta outside (0, 1), tau < 0 or eta < 0 gives NaN for every trial and its sum, its neighbours unaffected.
+//   basic_ddm_dc (rt, choice): choice 0 is the Euler-Maruyama simulator's timeout at rt = max_steps dt + tau, RIGHT-CENSORED:
+//     log P(T > t) from the large-time survival series of both boundaries,
+//     S(t) = sum_{sides} (pi / a'^2) e^{-a' v w} sum_k k sin(k pi w) e^{-lambda_k t} / lambda_k,  lambda_k = v'^2/2 + k^2 pi^2 / (2 a'^2),
+//     terms added until the next is below 2^-24 of the sum, at most 64 (a loop: timeouts are rare; t <= 0 gives log 1 = 0).
+//   alpha_not_scaled (y, acc): rt = |y|, upper iff y > 0; Nu clipped to +-5 as the generator does (pyhddmjagsutils.py:102-103);
+//     y == 0 (the Euler-Maruyama form's timeout) carries no time: NaN.  simulratcliff never writes one.
+//
+// Execution: a workgroup of 4 waves owns WIENER_ROWS consecutive parameter rows, a wave WIENER_RPW of them (rows w, w+4, ...).  Lane k
+// of a wave works out the constants of its k-th row (all rows of the wave at once) and the wave broadcasts them with v_readlane.
+// Lane j accumulates trials j, j+64, j+128, ... of a row in that order in float64, and a butterfly of the 64 partial sums gives the
+// row's sum: the order is a function of n_trials alone, not of the layout, the grid or the tile, so a row's sum has the same bits
+// whichever launch scores it.  Broadcast layout (draws_per_dataset >= WIENER_ROWS): the workgroup's rows all score one data set,
+// staged in LDS one WIENER_TILE of trials at a time and read by every row from there; paired layout: each row reads its trials
+// from HBM (each is read once anyway).  No scratch memory, no atomics; stores are plain vector stores.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/nddm.h"
+
+namespace nddm {
+
+constexpr float WIENER_U_STAR = 0.375f;         // small-time series below, large-time at and above (both exact to < 1e-9 there)
+constexpr int WIENER_RPW = 4;                   // rows per wave
+constexpr int WIENER_ROWS = 4 * WIENER_RPW;     // rows per workgroup (4 waves)
+constexpr int WIENER_TILE = 1024;               // trials staged in LDS at a time (8 KB); a constant, not a knob
+constexpr int WIENER_SURV_TERMS = 64;
+
+struct WienerArgs {
+    const float *params;        // [R, P]
+    const float *data;          // [D, N, 2]
+    float *out_trial;           // [R, N] or NULL
+    double *out_sum;            // [R] or NULL
+    long long R, S;             // rows, rows per data set
+    long long chunks;           // workgroups per data set (broadcast layout)
+    int N, P;
+};
+
+// The constants of one row, one value per field; side 0 = the lower boundary (w = beta, nu = v'), side 1 = the upper one.
+// In log2 units where they feed v_exp_f32 / v_log_f32 (base 2), in natural units where they add to the result.
+struct WienerRow {
+    float tau, tstar;           // tstar = WIENER_U_STAR a'^2 (small-time series for t < tstar)
+    float mq;                   // -pi^2 / (2 a'^2) log2(e): q = 2^(mq t)
+    float lq;                   // -pi^2 / (2 a'^2): the large-time exponent, natural units
+    float hn2, e2;              // v'^2 / 2, eta'^2
+    float w[2], m1[2], m2[2];   // w; -2 (1 -+ w) a'^2 log2(e): A = 2^(m1 / t), B = 2^(m2 / t)
+    float w2[2];                // w^2 a'^2 / 2: w^2 / (2u) = w2 / t
+    float cs[2], cl[2];         // -1/2 log(2 pi) + log a';  log pi + log sin(pi w) - 2 log a'
+    float c4[2], c3[2];         // 4 cos(pi w); 3 (4 cos^2(pi w) - 1)
+    float d0[2];                // eta'^2 a'^2 w^2 / 2 - a' nu w
+    float s1, cpb;              // sin(pi beta), cos(pi beta) (the survival series' recurrence)
+    float la;                   // log a'
+    float valid;                // 1 or NaN
+};
+constexpr int WIENER_ROW_WORDS = sizeof(WienerRow) / sizeof(float);
+
+template <int MODEL>
+__device__ __forceinline__ WienerRow wiener_row(const float *p)
+{
+    float v, a, beta, tau, eta, s;
+    if (MODEL == NDDM_BASIC_DDM_DC) { v = p[0]; a = p[1]; beta = p[2]; tau = p[3]; s = p[4]; eta = 0.0f; }
+    else { v = p[0]; a = p[1]; beta = p[2]; tau = p[3]; eta = p[4]; s = p[5]; }
+    const bool ok = isfinite(v) && isfinite(a) && isfinite(beta) && isfinite(tau) && isfinite(eta) && isfinite(s) && a > 0.0f && s > 0.0f &&
+                    beta > 0.0f && beta < 1.0f && tau >= 0.0f && eta >= 0.0f;
+    if (MODEL == NDDM_ALPHA_NOT_SCALED && (v < -5.0f || v > 5.0f)) v = v > 0.0f ? 5.0f : -5.0f;      // pyhddmjagsutils.py:102-103
+    const float ap = a / s, vp = v / s, ep = eta / s;
+    const float a2 = ap * ap, e2 = ep * ep, la = logf(ap);
+    const float log2e = 1.44269504088896341f, pi2h = 4.93480220054467931f;     // pi^2 / 2
+    WienerRow c;
+    c.tau = tau;
+    c.tstar = WIENER_U_STAR * a2;
+    c.lq = -pi2h / a2;
+    c.mq = c.lq * log2e;
+    c.hn2 = 0.5f * (vp * vp);
+    c.e2 = e2;
+    c.la = la;
+    const float sb = sinpif(beta), cb = cospif(beta);
+    c.s1 = sb; c.cpb = cb;
+    const float lsin = logf(sb);
+    for (int side = 0; side < 2; ++side) {
+        const float w = side ? 1.0f - beta : beta, nu = side ? -vp : vp, cw = side ? -cb : cb;
+        c.w[side] = w;
+        c.m1[side] = (-2.0f * (1.0f - w)) * a2 * log2e;
+        c.m2[side] = (-2.0f * (1.0f + w)) * a2 * log2e;
+        c.w2[side] = 0.5f * (w * w) * a2;
+        c.cs[side] = -0.918938533204672742f + la;                      // -1/2 log(2 pi) + log a'
+        c.cl[side] = 1.14472988584940017f + lsin - 2.0f * la;           // log pi + log sin(pi w) - 2 log a'
+        c.c4[side] = 4.0f * cw;
+        c.c3[side] = 3.0f * (4.0f * (cw * cw) - 1.0f);
+        c.d0[side] = 0.5f * (e2 * a2 * (w * w)) - ap * nu * w;
+    }
+    c.valid = ok ? 1.0f : __builtin_nanf("");
+    return c;
+}
+
+// log P(T > t) of the η = 0 process (basic_ddm_dc's censored timeouts): the large-time survival series of both boundaries, with
+// e^{-lambda_1 t} and the larger side weight taken out; sin(k pi w) by the Chebyshev recurrence (sin(k pi (1 - beta)) = (-1)^(k+1) sin(k pi beta))
+__device__ __forceinline__ float wiener_log_survival(const WienerRow &c, float t)
+{
+    if (!(t > 0.0f)) return t == t ? 0.0f : t;
+    const float m = fmaxf(c.d0[0], c.d0[1]);
+    const float wl = __expf(c.d0[0] - m), wu = __expf(c.d0[1] - m);
+    const float kk = -c.lq;                                             // pi^2 / (2 a'^2)
+    const float lam1 = c.hn2 + kk;
+    float sk_1 = 0.0f, sk = c.s1, sum = 0.0f;
+    for (int k = 1; k <= WIENER_SURV_TERMS; ++k) {
+        const float fk = (float)k;
+        const float lam = c.hn2 + kk * (fk * fk);
+        const float sgn = (k & 1) ? 1.0f : -1.0f;
+        const float env = fk * __expf(-kk * (fk * fk - 1.0f) * t) * __builtin_amdgcn_rcpf(lam);
+        // stop when the next term's bound (|sin| <= 1) is below 2^-24 of the sum: the term itself can vanish (sin(2 pi / 2) = 0 at
+        // beta = 1/2) while later ones do not
+        if (k > 1 && env * (wl + wu) < 5.9604644775390625e-08f * fabsf(sum)) break;
+        sum += env * (wl * sk + wu * sgn * sk);
+        const float sn = 2.0f * c.cpb * sk - sk_1;
+        sk_1 = sk; sk = sn;
+    }
+    return -lam1 * t + m + (1.14472988584940017f - 2.0f * c.la) + 0.693147180559945309f * __builtin_amdgcn_logf(sum);
+}
+
+// log f of one trial on one boundary: a pure function of (row constants, rt, side)
+template <int MODEL>
+__device__ __forceinline__ float wiener_logpdf(const WienerRow &c, float rt, int sd)
+{
+    const float t = rt - c.tau;
+    const float w = sd ? c.w[1] : c.w[0];
+    // small time (2 exponentials: A, B), for u < WIENER_U_STAR
+    const float tc = fmaxf(t, 1.17549435e-38f);                        // (a t below the smallest normal float is evaluated there)
+    const float it = __builtin_amdgcn_rcpf(tc);
+    const float A = __builtin_amdgcn_exp2f((sd ? c.m1[1] : c.m1[0]) * it);
+    const float B = __builtin_amdgcn_exp2f((sd ? c.m2[1] : c.m2[0]) * it);
+    const float A3B = (A * A) * (A * B), AB3 = (B * B) * (A * B);
+    const float ssum = w + (w - 2.0f) * A + (w + 2.0f) * B + (w - 4.0f) * A3B + (w + 4.0f) * AB3;
+    // large time (1 exponential: q), for u >= WIENER_U_STAR
+    const float q = __builtin_amdgcn_exp2f(c.mq * t);
+    const float q2 = q * q, q4 = q2 * q2, q3 = q2 * q, q8 = q4 * q4;
+    const float lsum = 1.0f + (sd ? c.c4[1] : c.c4[0]) * q3 + (sd ? c.c3[1] : c.c3[0]) * q8;
+    const bool small = t < c.tstar;
+    const float ln2 = 0.693147180559945309f;
+    const float lx = ln2 * __builtin_amdgcn_logf(small ? ssum : lsum);
+    const float lt = ln2 * __builtin_amdgcn_logf(tc);
+    const float rest = small ? (sd ? c.cs[1] : c.cs[0]) - 1.5f * lt - (sd ? c.w2[1] : c.w2[0]) * it
+                             : (sd ? c.cl[1] : c.cl[0]) + c.lq * t;
+    float lf = lx + rest;
+    // drift term, eta' integrated out; with eta = 0 the general form reduces to d0 - hn2 t exactly (a division by 1, log of 1), so the
+    // row-uniform branch only skips work
+    const float d0 = sd ? c.d0[1] : c.d0[0];
+    if (MODEL == NDDM_ALPHA_NOT_SCALED && c.e2 > 0.0f) {                // (basic_ddm_dc has no drift variability)
+        const float den = 1.0f + c.e2 * t;
+        lf += (d0 - c.hn2 * t) * __builtin_amdgcn_rcpf(den) - (0.5f * ln2) * __builtin_amdgcn_logf(den);
+    } else {
+        lf += d0 - c.hn2 * t;
+    }
+    lf = t > 0.0f ? lf : -__builtin_inff();
+    return lf * c.valid;
+}
+
+template <int MODEL>
+__device__ __forceinline__ float wiener_trial(const WienerRow &c, float x0, float x1)
+{
+    if (MODEL == NDDM_BASIC_DDM_DC) {                                   // (rt, choice): 1 upper, -1 lower, 0 censored timeout
+        if (x1 == 0.0f) return wiener_log_survival(c, x0 - c.tau) * c.valid;
+        return wiener_logpdf<MODEL>(c, x0, x1 > 0.0f ? 1 : 0) + (x1 == x1 ? 0.0f : x1);
+    } else {                                                            // (y, acc): rt = |y|, upper iff y > 0; y == 0 has no time
+        const float r = wiener_logpdf<MODEL>(c, fabsf(x0), x0 > 0.0f ? 1 : 0);
+        return x0 == 0.0f ? __builtin_nanf("") : r;
+    }
+}
+
+__device__ __forceinline__ float wiener_bcast(float x, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), k)); }
+
+// STAGED: the workgroup's rows all score one data set, read from LDS (broadcast layout); else every row reads its own (paired layout)
+template <int MODEL, bool STAGED>
+__global__ __launch_bounds__(256) void wiener_kernel(WienerArgs A)
+{
+    __shared__ float2 tile[STAGED ? WIENER_TILE : 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long rbase, rend;
+    if (STAGED) {
+        const long long d = blockIdx.x / A.chunks, ch = blockIdx.x - d * A.chunks;
+        rbase = d * A.S + ch * WIENER_ROWS;
+        rend = rbase + WIENER_ROWS < (d + 1) * A.S ? rbase + WIENER_ROWS : (d + 1) * A.S;
+    } else {
+        rbase = (long long)blockIdx.x * WIENER_ROWS;
+        rend = rbase + WIENER_ROWS < A.R ? rbase + WIENER_ROWS : A.R;
+    }
+    const long long wrow0 = rbase + wave;                               // the wave's rows: wrow0 + 4k, k < WIENER_RPW
+    const bool has_rows = wrow0 < rend;
+    if (!STAGED && !has_rows) return;
+    // lane k < WIENER_RPW works out the constants of the wave's k-th row (clamped into range; unused lanes repeat the last)
+    WienerRow mine;
+    {
+        long long r = wrow0 + 4ll * (lane < WIENER_RPW ? lane : WIENER_RPW - 1);
+        if (r >= rend) r = rend - 1;
+        if (r < rbase) r = rbase;
+        mine = wiener_row<MODEL>(A.params + r * A.P);
+    }
+    // per-lane partial sums of the wave's rows (named, not an array: the row loop is not unrolled, and a dynamically indexed array
+    // would live in scratch)
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
+    static_assert(WIENER_RPW == 4, "one partial sum per row of the wave");
+    for (int t0 = 0; t0 < A.N; t0 += WIENER_TILE) {
+        const int nt = A.N - t0 < WIENER_TILE ? A.N - t0 : WIENER_TILE;
+        if (STAGED) {
+            const float *src = A.data + ((rbase / A.S) * (long long)A.N + t0) * 2;
+            __syncthreads();                                           // the previous tile is no longer read
+            for (int j = threadIdx.x; j < nt; j += 256) tile[j] = make_float2(src[2 * j], src[2 * j + 1]);
+            __syncthreads();
+        }
+#pragma nounroll
+        for (int k = 0; k < WIENER_RPW; ++k) {
+            const long long row = wrow0 + 4ll * k;
+            if (row >= rend) break;                                     // wave-uniform
+            WienerRow c;
+            const float *m = reinterpret_cast<const float *>(&mine);
+            float *cw = reinterpret_cast<float *>(&c);
+#pragma unroll
+            for (int f = 0; f < WIENER_ROW_WORDS; ++f) cw[f] = wiener_bcast(m[f], k);
+            const float *src = STAGED ? nullptr : A.data + ((row / A.S) * (long long)A.N + t0) * 2;
+            float *dst = A.out_trial ? A.out_trial + row * (long long)A.N + t0 : nullptr;
+            double s = k == 0 ? acc0 : k == 1 ? acc1 : k == 2 ? acc2 : acc3;
+            // (paired layout: the next trial's pair is loaded before this one is evaluated, so that HBM latency overlaps the arithmetic)
+            float n0 = 0.0f, n1 = 0.0f;
+            if (!STAGED && lane < nt) { n0 = src[2 * lane]; n1 = src[2 * lane + 1]; }
+            for (int i = lane; i < nt; i += 64) {
+                float x0, x1;
+                if (STAGED) { const float2 x = tile[i]; x0 = x.x; x1 = x.y; }
+                else {
+                    x0 = n0; x1 = n1;
+                    if (i + 64 < nt) { n0 = src[2 * (i + 64)]; n1 = src[2 * (i + 64) + 1]; }
+                }
+                const float lf = wiener_trial<MODEL>(c, x0, x1);
+                if (dst) dst[i] = lf;
+                s += (double)lf;
+            }
+            acc0 = k == 0 ? s : acc0; acc1 = k == 1 ? s : acc1; acc2 = k == 2 ? s : acc2; acc3 = k == 3 ? s : acc3;
+        }
+    }
+    if (!A.out_sum || !has_rows) return;
+    for (int k = 0; k < WIENER_RPW; ++k) {
+        const long long row = wrow0 + 4ll * k;
+        if (row >= rend) break;
+        double s = k == 0 ? acc0 : k == 1 ? acc1 : k == 2 ? acc2 : acc3;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m, 64);       // a + b == b + a: every lane ends with the same bits
+        if (lane == 0) A.out_sum[row] = s;
+    }
+}
+
+}  // namespace nddm

@@ -97,3 +97,20 @@ def converged_fits(param_means, index=3, low=0.0, high=1.0):
     posterior MEAN of the non-decision time (parameter 3 in both models) lies inside (0, 1) -> boolean [n_datasets]."""
     m = np.asarray(param_means, dtype=np.float64)
     return (m[:, index] > low) & (m[:, index] < high)
+
+
+def posterior_log_likelihood(samples, data, model):
+    """Score posterior draws by the exact likelihood: samples [D, S, P] (what amortizer.sample returns for a batch of D data sets;
+    [S, P] for one), data [D, n_trials, 2] in the simulator's format (model = engine.BASIC_DDM_DC or engine.ALPHA_NOT_SCALED) ->
+    float64 [D, S] = log p(data[d] | samples[d, s]), in one launch of the broadcast layout (each data set staged once per 16 draws).
+    The numbers importance weights, posterior predictive log scores and LOO / WAIC start from."""
+    from . import engine
+    single = samples.ndim == 2
+    s = samples[None] if single else samples
+    d = data[None] if data.ndim == 2 else data
+    D, S, P = (int(x) for x in s.shape)
+    if int(d.shape[0]) != D:
+        raise ValueError(f"samples hold {D} data sets but data holds {int(d.shape[0])}")
+    flat = s.reshape(D * S, P) if hasattr(s, "is_cuda") else np.asarray(s, dtype=np.float64).reshape(D * S, P)
+    ll = engine.wiener_log_likelihood(model, flat, d, draws_per_dataset=S)["loglik"].reshape(D, S)
+    return ll[0] if single else ll

@@ -293,6 +293,95 @@ def simulratcliff(params, n_trials, seed=None, set_offset=None, fast=None, ext_s
     return res
 
 
+def _wiener_host_checks(model, p_np, d_np):
+    """Shape and range checks of host-side likelihood inputs (ValueError, before any device work)."""
+    if p_np is not None:
+        P = NPARAMS[model]
+        if p_np.ndim != 2 or p_np.shape[1] != P:
+            raise ValueError(f"params must have shape [R, {P}], got {p_np.shape}")
+        if not np.all(np.isfinite(p_np)):
+            raise ValueError("parameters must be finite")
+        a, beta, tau = p_np[:, 1], p_np[:, 2], p_np[:, 3]
+        s = p_np[:, 4] if model == BASIC_DDM_DC else p_np[:, 5]
+        if np.any(a <= 0) or np.any(s <= 0):
+            raise ValueError("boundary and diffusion coefficient must be > 0")
+        if np.any(beta <= 0) or np.any(beta >= 1):
+            raise ValueError("beta must lie in (0, 1)")
+        if np.any(tau < 0) or (model == ALPHA_NOT_SCALED and np.any(p_np[:, 4] < 0)):
+            raise ValueError("tau and Eta must be >= 0")
+    if d_np is not None:
+        if d_np.ndim != 3 or d_np.shape[2] != 2 or d_np.shape[1] <= 0:
+            raise ValueError(f"data must have shape [D, n_trials, 2], got {d_np.shape}")
+        if model == BASIC_DDM_DC and not np.all(np.isin(d_np[..., 1], (-1.0, 0.0, 1.0))):
+            raise ValueError("basic_ddm_dc data are (rt, choice) with choice in {1, -1, 0}")
+
+
+def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=False, want_sum=True, device=None):
+    """Log-likelihood of observed trials under the Wiener first-passage density (include/nddm.h: nddm_wiener_log_likelihood), one
+    kernel launch: the density JAGS dwiener / Stan wiener_lpdf evaluate in the reference's likelihood-based fits.
+
+    model: BASIC_DDM_DC (params [R, 5], data (rt, choice); choice 0 = a timeout, scored as log P(T > rt - tau)) or ALPHA_NOT_SCALED
+    (params [R, 6], drift ~ N(Nu, Eta) integrated out, Nu clipped to +-5; data (y, acc), y == 0 gives NaN).  data: [D, n_trials, 2]
+    in the simulator's output format, R = D * draws_per_dataset, row r scored against data set r // draws_per_dataset.
+    Returns a dict of device tensors: 'loglik' float64 [R] (want_sum) and 'trial_logp' float32 [R, n_trials] (per_trial).
+    Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN."""
+    if model not in (BASIC_DDM_DC, ALPHA_NOT_SCALED):
+        raise ValueError(f"model {model} has no closed-form likelihood here (BASIC_DDM_DC and ALPHA_NOT_SCALED only)")
+    if not (per_trial or want_sum):
+        raise ValueError("ask for per_trial and/or want_sum")
+    S = int(draws_per_dataset)
+    if S <= 0:
+        raise ValueError("draws_per_dataset must be > 0")
+    P = NPARAMS[model]
+    p_host = not (hasattr(params, "is_cuda") and params.is_cuda)
+    d_host = not (hasattr(data, "is_cuda") and data.is_cuda)
+    p_np = d_np = None
+    if p_host:
+        p_np = np.asarray(params.detach().cpu().numpy() if hasattr(params, "detach") else params, dtype=np.float64)
+        if p_np.ndim == 1:
+            p_np = p_np[None]
+    if d_host:
+        d_np = np.asarray(data.detach().cpu().numpy() if hasattr(data, "detach") else data, dtype=np.float64)
+        if d_np.ndim == 2:
+            d_np = d_np[None]
+    _wiener_host_checks(model, p_np, d_np)
+    R = p_np.shape[0] if p_host else (1 if params.ndim == 1 else int(params.shape[0]))
+    D = d_np.shape[0] if d_host else (1 if data.ndim == 2 else int(data.shape[0]))
+    if R != D * S:
+        raise ValueError(f"params has {R} rows but data holds {D} data sets x draws_per_dataset {S}")
+    torch = require_device()
+    L = _lib.lib()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        if p_host:
+            p_dev = torch.as_tensor(p_np, dtype=torch.float32).to(dev)
+        else:
+            p_dev = (params[None] if params.ndim == 1 else params).to(dtype=torch.float32).contiguous()
+            if p_dev.ndim != 2 or p_dev.shape[1] != P:
+                raise ValueError(f"params must have shape [R, {P}], got {tuple(p_dev.shape)}")
+        if d_host:
+            d_dev = torch.as_tensor(d_np, dtype=torch.float32).to(dev)
+        else:
+            d_dev = (data[None] if data.ndim == 2 else data).to(dtype=torch.float32).contiguous()
+            if d_dev.ndim != 3 or d_dev.shape[2] != 2 or d_dev.shape[1] <= 0:
+                raise ValueError(f"data must have shape [D, n_trials, 2], got {tuple(d_dev.shape)}")
+        N = int(d_dev.shape[1])
+        out_t = torch.empty((R, N), dtype=torch.float32, device=dev) if per_trial else None
+        out_s = torch.empty((R,), dtype=torch.float64, device=dev) if want_sum else None
+        pt = lambda t: None if t is None else t.data_ptr()
+        if R > 0:
+            st = torch.cuda.current_stream(dev)
+            _lib.check(L.nddm_wiener_log_likelihood(int(model), pt(p_dev), R, S, pt(d_dev), N, 0, pt(out_t), pt(out_s), st.cuda_stream))
+            p_dev.record_stream(st)
+            d_dev.record_stream(st)
+    res = {}
+    if out_s is not None:
+        res["loglik"] = out_s
+    if out_t is not None:
+        res["trial_logp"] = out_t
+    return res
+
+
 def decode_codes(model, codes, params, dt, out_trials=None):
     """The 2-byte wire format back to the float pairs the simulator writes: codes int16 [B, n_trials] (uint16 content), params
     f32 [B, P] (tau is read from them), -> f32 [B, n_trials, 2], bit-identical to simulate()'s 'trials' (nddm_decode_codes)."""

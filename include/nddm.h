@@ -67,6 +67,7 @@ extern "C" {
  *    frees only what was captured with no arena bound (up to ABI 2: every captured launch's memory on the device, whoever's graph
  *    replayed into it); a `stream` the HIP runtime does not know is refused with NDDM_ERR_HIP (validated with hipStreamGetDevice at entry).  The random stream is ABI 2's. */
 /* 4: NDDM_STATE_F64 (flag 8), nddm_build_info, nddm_simulratcliff.  The random stream and every ABI-3 entry point are unchanged. */
+/* 4 (additive): nddm_wiener_log_likelihood.  No existing entry point changes. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -236,6 +237,30 @@ int nddm_alpha_not_scaled_simulate(const float *params, int64_t B, int32_t n_tri
  * (same bits); with summaries such a launch cannot be captured into a hipGraph. */
 int nddm_simulratcliff(const float *params, int64_t B, int32_t n_trials, uint64_t seed, uint64_t set_offset, uint32_t flags,
                        float ext_sigma, int32_t ext_mode, float *out_trials, float *out_summary, float *out_extdata, void *stream);
+
+/* ---- likelihood ---------------------------------------------------------------------------------------------------------
+ * replaces the Wiener first-passage density the reference's likelihood-based fits evaluate per trial: JAGS
+ * dwiener(alpha/varsigma, ndt, beta, delta/varsigma) (basic_ddm_dc_pyjags.py:129-133, alpha_not_scaled.py:170-176, jagscode/*.jags) and
+ * Stan wiener_lpdf inside diffusion_lpdf(Y | boundary, ter, bias, drift, dc) (basic_ddm_dc_pystan2.py:119-131, :170-175,
+ * stancode/basic_ddm_dc_test.stan) -- the per-trial log density, not the samplers around it.  (ABI 4, additive)
+ *   model              NDDM_BASIC_DDM_DC (P=5) or NDDM_ALPHA_NOT_SCALED (P=6, drift ~ N(Nu, Eta) integrated out, Nu clipped to +-5);
+ *                      any other model: NDDM_ERR_PARAM
+ *   params             device f32 [R, P] in the simulator's parameter order; R = D * draws_per_dataset
+ *   draws_per_dataset  S: row r is scored against data set r / S (S = 1: a simulator batch under its own parameters; D = 1 and S large:
+ *                      posterior draws against one observed data set -- the data set is staged in LDS once per 16 rows)
+ *   data               device f32 [D, n_trials, 2] in the simulator's own output format: (rt, choice) for basic (choice 0 = a timeout,
+ *                      scored RIGHT-CENSORED as log P(T > rt - tau)), (y, acc) for alpha_not_scaled (y == 0 carries no time: NaN)
+ *   flags              0 (reserved)
+ *   out_trial_logp     device f32 [R, n_trials] or NULL: log f of every trial (natural log; rt <= tau gives -inf)
+ *   out_loglik         device f64 [R] or NULL (not both NULL): the row's sum, accumulated in float64 in an order that depends on n_trials
+ *                      alone -- the same bits for a row whatever the layout, launch, stream or capture
+ * A row with a non-finite parameter, boundary or diffusion coefficient <= 0, beta outside (0, 1), tau < 0 or eta < 0 gives NaN for its
+ * trials and its sum; the other rows are unaffected.  No scratch memory: a call made while `stream` is capturing is one kernel node.
+ * Errors (checked before any HIP call): NDDM_ERR_SHAPE for R < 0, n_trials <= 0, draws_per_dataset <= 0 or not dividing R;
+ * NDDM_ERR_NULL for a NULL params / data or both outputs NULL; R = 0 is NDDM_OK.  The math: csrc/nddm_wiener.h, DESIGN.md section 11. */
+int nddm_wiener_log_likelihood(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
+                               int32_t n_trials, uint32_t flags, float *out_trial_logp /* [R, n_trials] or NULL */,
+                               double *out_loglik /* [R] or NULL */, void *stream);
 
 /* replaces the per-trial loop over diffusion_trial(drift, bound_trial, beta, ter, dc),
  * imputation_from_stahl_not_scaled.py:120-148, :207-213.  bounds: device f32 [B, n_trials].

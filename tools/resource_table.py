@@ -25,6 +25,9 @@ def pretty(name):
         mod, fast, cap4, bridge, small, packed, vkeys, codes, f64 = (int(x) for x in m.groups())
         return (f"sim_kernel<{MODELS[mod]}, {'fast' if fast else 'exact'}, cap4={cap4}, bridge={bridge}, small={small}, "
                 f"packed={packed}, vkeys={vkeys}{', codes' if codes else ''}{', state_f64' if f64 else ''}>")
+    m = re.match(r"_ZN4nddm13wiener_kernelILi(\d)ELb(\d)E", name)
+    if m:                                                     # <MODEL, STAGED>: the LDS-staged broadcast layout or the paired one
+        return f"wiener_kernel<{MODELS[int(m.group(1))]}, {'broadcast' if m.group(2) == '1' else 'paired'}>"
     m = re.match(r"_ZN(?:4nddm|10nddm_train|12nddm_deepset|11nddm_update)(\d+)", name)
     if m:
         n = int(m.group(1))

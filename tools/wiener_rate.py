@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""Rate of nddm_wiener_log_likelihood (csrc/nddm_wiener.h) at the shapes of its users, timed with HIP events, beside the same formula
+composed from PyTorch elementwise ops in the same process (the yardstick).  Prints one JSON line.
+
+  paired_sums       basic_ddm_dc, 1M rows x 300 trials, each row against its own data set, sums only   (8 B of data per evaluation)
+  paired_trials     the same with the per-trial output as well                                         (12 B per evaluation)
+  broadcast_sums    500 data sets x 10 000 draws x 300 trials, sums only: the recovery loop's shape (basic_ddm_dc.py:211-223)
+  broadcast_ans     the same for alpha_not_scaled (drift variability integrated out: one more v_rcp / v_log per evaluation)
+  torch_composed    the fixed-trip formula of the kernel as PyTorch elementwise ops on 100 000 rows x 300 trials (basic, eta = 0)
+
+Each shape runs in a child process of its own under `timeout` (a step that faults or hangs ends the tool; nothing further starts).
+Usage: python tools/wiener_rate.py [--json OUT] [--reps 10]        (one shape: --only NAME)
+"""
+import argparse
+import json
+import math
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = ("paired_sums", "paired_trials", "broadcast_sums", "broadcast_ans", "torch_composed")
+HBM_BPS = 8e12
+
+
+def _time(torch, fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    ms.sort()
+    return ms[len(ms) // 2], ms[0]
+
+
+def _basic_params(torch, n, gen):
+    u = lambda lo, hi: torch.rand(n, generator=gen, device="cuda") * (hi - lo) + lo
+    return torch.stack([u(-3, 3), u(0.6, 2.0), u(0.3, 0.7), u(0.1, 0.5), u(0.8, 1.3)], 1).contiguous()
+
+
+def _data(torch, D, N, gen, signed=False):
+    rt = 0.5 + torch.rand((D, N), generator=gen, device="cuda") * 1.5
+    ch = torch.where(torch.rand((D, N), generator=gen, device="cuda") < 0.6, 1.0, -1.0)
+    if signed:
+        return torch.stack([rt * ch, (ch + 1) / 2], -1).contiguous()
+    return torch.stack([rt, ch], -1).contiguous()
+
+
+def torch_logpdf(torch, p, d):
+    """The kernel's formula (basic, eta = 0) from PyTorch elementwise ops: p [R, 5] against d [R, N, 2]."""
+    v, a, beta, tau, s = (p[:, i:i + 1] for i in range(5))
+    rt, ch = d[..., 0], d[..., 1]
+    up = ch > 0
+    ap, vp = a / s, v / s
+    w = torch.where(up, 1 - beta, beta)
+    nu = torch.where(up, -vp, vp)
+    t = rt - tau
+    u = t / (ap * ap)
+    A, B = torch.exp(-2 * (1 - w) / u), torch.exp(-2 * (1 + w) / u)
+    ss = w + (w - 2) * A + (w + 2) * B + (w - 4) * A ** 3 * B + (w + 4) * A * B ** 3
+    small = -0.5 * math.log(2 * math.pi) - 1.5 * torch.log(u) - w * w / (2 * u) + torch.log(ss)
+    q = torch.exp(-math.pi ** 2 * u / 2)
+    c = torch.cos(math.pi * w)
+    large = math.log(math.pi) + torch.log(torch.sin(math.pi * w)) - math.pi ** 2 * u / 2 + torch.log(1 + 4 * c * q ** 3 + 3 * (4 * c * c - 1) * q ** 8)
+    lg = torch.where(u < 0.375, small, large)
+    lf = lg - 2 * torch.log(ap) - ap * nu * w - nu * nu * t / 2
+    return torch.where(t > 0, lf, torch.full_like(lf, -math.inf))
+
+
+def run_one(name, reps):
+    sys.path.insert(0, ROOT)
+    import torch
+    from bayesflow_nddms_amd import _lib, engine
+    L = _lib.lib()
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(7)
+    st = lambda: torch.cuda.current_stream().cuda_stream
+    N = 300
+    if name in ("paired_sums", "paired_trials"):
+        R = 1_000_000
+        p, d = _basic_params(torch, R, gen), _data(torch, R, N, gen)
+        out_s = torch.empty(R, dtype=torch.float64, device="cuda")
+        out_t = torch.empty((R, N), dtype=torch.float32, device="cuda") if name == "paired_trials" else None
+        fn = lambda: _lib.check(L.nddm_wiener_log_likelihood(0, p.data_ptr(), R, 1, d.data_ptr(), N, 0,
+                                                             None if out_t is None else out_t.data_ptr(), out_s.data_ptr(), st()))
+        nbytes = d.numel() * 4 + p.numel() * 4 + R * 8 + (R * N * 4 if out_t is not None else 0)
+        evals = R * N
+    elif name in ("broadcast_sums", "broadcast_ans"):
+        D, S = 500, 10_000
+        R = D * S
+        if name == "broadcast_sums":
+            p, model = _basic_params(torch, R, gen), 0
+        else:
+            b = _basic_params(torch, R, gen)
+            eta = torch.rand(R, generator=gen, device="cuda") * 1.5
+            p, model = torch.stack([b[:, 0], b[:, 1], b[:, 2], b[:, 3], eta, b[:, 4]], 1).contiguous(), engine.ALPHA_NOT_SCALED
+        d = _data(torch, D, N, gen, signed=name == "broadcast_ans")
+        out_s = torch.empty(R, dtype=torch.float64, device="cuda")
+        fn = lambda: _lib.check(L.nddm_wiener_log_likelihood(model, p.data_ptr(), R, S, d.data_ptr(), N, 0, None, out_s.data_ptr(), st()))
+        nbytes = d.numel() * 4 + p.numel() * 4 + R * 8
+        evals = R * N
+    else:
+        R = 100_000
+        p = _basic_params(torch, R, gen)
+        d = _data(torch, R, N, gen)
+        # the same values as the kernel, to the tolerance of f32 (a check that the yardstick computes the same thing)
+        k = engine.wiener_log_likelihood(0, p[:1000], d[:1000], per_trial=True)["trial_logp"]
+        dev = (torch_logpdf(torch, p[:1000], d[:1000]) - k).abs().max().item()
+        fn = lambda: torch_logpdf(torch, p, d).sum(1, dtype=torch.float64)
+        nbytes = d.numel() * 4 + p.numel() * 4 + R * 8
+        evals = R * N
+    med, best = _time(torch, fn, reps)
+    res = {"shape": name, "evals": evals, "ms_median": round(med, 4), "ms_best": round(best, 4),
+           "evals_per_s": evals / (med * 1e-3), "GB_per_s": nbytes / (med * 1e-3) / 1e9, "frac_of_8TBps": nbytes / (med * 1e-3) / HBM_BPS}
+    if name == "torch_composed":
+        res["max_abs_diff_vs_kernel_first_1000_rows"] = dev
+    print(json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only")
+    ap.add_argument("--json")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--timeout", type=int, default=300)
+    a = ap.parse_args()
+    if a.only:
+        run_one(a.only, a.reps)
+        return
+    sys.path.insert(0, ROOT)
+    from bayesflow_nddms_amd import build
+    out = {"tool": "tools/wiener_rate.py", "library_source_hash": build.source_hash(), "shapes": {}}
+    for name in SHAPES:
+        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--only", name, "--reps", str(a.reps)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout + r.stderr)
+            sys.exit(f"{name}: exit status {r.returncode}; nothing further is started")
+        out["shapes"][name] = json.loads(r.stdout.strip().splitlines()[-1])
+    tc = out["shapes"]["torch_composed"]["evals_per_s"]
+    for name in ("broadcast_sums", "broadcast_ans", "paired_sums"):
+        out["shapes"][name]["x_torch_composed"] = out["shapes"][name]["evals_per_s"] / tc
+    line = json.dumps(out)
+    print(line)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
