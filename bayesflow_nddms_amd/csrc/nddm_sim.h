@@ -561,6 +561,10 @@ __global__ __launch_bounds__(WAVE) void sim_kernel(const SimArgs A)
     // which lanes hold a trial / are still stepping: wave-uniform lane masks kept in SGPRs (a per-lane bool that is
     // balloted costs v_cndmask + v_cmp each time; __builtin_amdgcn_inverse_ballot_w64 turns a mask into exec for free)
     unsigned long long has_m = 0ull, act_m = 0ull;
+    // a refill phase is at most this many blocks of the step loop (unless the threshold is >= 64: see the step phase)
+    constexpr int MAX_BLOCKS = 16;
+    // CAP4 && !PACKED step block: the step cap if a lane can reach it in the current refill phase, else -1 (set at the hand-out)
+    [[maybe_unused]] int cap_k = -1;
     PathCtr pc = {0u, 0u, 0u, 0u, 0u};
     [[maybe_unused]] PathKeys pkeys;              // VKEYS: the step loop's Philox round keys
     if constexpr (VKEYS) pkeys.init(A.k0, A.k1);
@@ -847,13 +851,24 @@ __global__ __launch_bounds__(WAVE) void sim_kernel(const SimArgs A)
             // are masked by has_m)
             if constexpr (BRIDGE) act_m = __builtin_amdgcn_ballot_w64(ta > 0.0f) & __builtin_amdgcn_ballot_w64(k < A.max_k) & has_m;
             else if constexpr (F64) act_m = __builtin_amdgcn_ballot_w64(xe > 0.0) & __builtin_amdgcn_ballot_w64(xe < ab) & __builtin_amdgcn_ballot_w64(k < A.max_k) & has_m;
+            else if constexpr (CAP4 && !PACKED) {
+                // the step cap, once per refill phase instead of once per block: a lane that steps on from the phase before is
+                // below the cap (the loop took the others out), a fresh one has k = 0, so "k < max_k" is the scalar max_k > 0.
+                // What is asked per lane is whether the cap is within reach of THIS phase -- at most MAX_BLOCKS blocks; no
+                // bound with a threshold >= 64 (lockstep), where every phase counts as near.  Only then does the step loop
+                // test the cap after a block (cap_k = the cap), otherwise it skips the compare (cap_k < 0)
+                // (the cap is read afresh: held in an SGPR through the kernel, it and what derives from it cost residency)
+                const int max_k = fresh_args(Ak)->max_k;
+                act_m = max_k > 0 ? __builtin_amdgcn_ballot_w64(in_range(w, h)) & has_m : 0ull;
+                const int near_from = A.refill_thresh < WAVE ? max_k - 4 * MAX_BLOCKS : (int)0x80000000;
+                cap_k = (__builtin_amdgcn_ballot_w64(k >= near_from) & has_m) ? max_k : -1;
+            }
             else act_m = __builtin_amdgcn_ballot_w64(in_range(w, h)) & __builtin_amdgcn_ballot_w64(k < A.max_k) & has_m;
         }
         // ------------------------------------------------------------ step phase
         // leave the loop for a refill once refill_thresh lanes hold a finished trial, or none is stepping, or after
         // MAX_BLOCKS blocks (so that a few finished lanes never wait long for company; a threshold >= 64 -- the lockstep
         // measurement -- switches that exit off)
-        constexpr int MAX_BLOCKS = 16;
         const int it_limit = A.refill_thresh < WAVE ? MAX_BLOCKS - 1 : 0x7fffffff;      // (one integer, not a lane-mask pair)
         // leave when this many lanes hold a finished trial: the threshold, or all the lanes that hold one at all ("none is
         // stepping" is the same test: the occupied lanes do not change inside the step loop)
@@ -999,25 +1014,47 @@ __global__ __launch_bounds__(WAVE) void sim_kernel(const SimArgs A)
             }
             if constexpr (CAP4 && !PACKED) {
                 // The four steps with the execution mask narrowed by the range compare itself (v_cmpx writes EXEC): fmac, add,
-                // k + 1, compare per step and not one scalar instruction in between.  As the compiler writes `if (active)` a
-                // step carries four (s_and_saveexec, s_cbranch_execz, s_and, s_or), and a SIMD issues one scalar instruction
+                // compare per step and no branch in between.  As the compiler writes `if (active)` a
+                // step carries four scalar instructions (s_and_saveexec, s_cbranch_execz, s_and, s_or), and a SIMD issues one
                 // per ~4.2 cycles, only partly in the shadow of the vector ones (tools/ubench_salu).  Measured A/B on one box:
                 // +0.5 % at the headline, +1.4 % single_trial, +1.9 % alpha_not_scaled, +3 % at 60 trials per set, 0 at
                 // dt=.01 -- and -1.8 % in lockstep, where no lane ever leaves (the compare-to-EXEC dependency costs there
                 // what the scalar instructions cost elsewhere), -2 % with the 8-step packed layout, which keeps the C form.
-                // The lanes still in range afterwards are EXEC itself.  (EXEC is all ones here -- the step loop is
-                // wave-uniform code -- and is left so.)
-                unsigned long long still;
-#define NDDM_STEP(R, T) "v_fmac_f32 %[w], %[" R "], %[" T "]\n\tv_add_f32 %[w], %[mu], %[w]\n\tv_add_u32 %[k], 1, %[k]\n\tv_cmpx_lt_f32_e64 vcc, |%[w]|, %[h]\n\t"
+                // (EXEC is all ones here -- the step loop is wave-uniform code -- and is left so.)
+                //
+                // k is counted two steps at a time: + 2 under the lanes that start the block, + 2 under the survivors of step 2.
+                // A lane that leaves at step 2 or 4, or survives, then holds its count; one that leaves at step 1 or 3 holds one
+                // too many.  Those lanes are collected in the mask pair itself: each compare also leaves its result in VCC
+                // (zero for lanes outside EXEC), the masks m1 >= m2 >= m3 are nested, so am ^ m1 ^ m2 ^ m3 = (am \ m1) | (m2 \ m3).
+                // Only when that set is not empty -- a scalar branch -- one v_subrev runs under it.  (The s_andn2 with m4 changes
+                // nothing -- m4 lies within m3 -- it sets SCC and orders the EXEC write behind the last compare.)  VCC is read by
+                // scalar instructions only, which the hardware interlocks: no wait states.
+                // The lanes still in range afterwards are the last compare's VCC.  The step cap is tested only in a phase in
+                // which a lane can reach it (cap_k >= 0: the hand-out): one loop, the compare behind a scalar branch.
+#define NDDM_STEP(R, T, K2) "v_fmac_f32 %[w], %[" R "], %[" T "]\n\tv_add_f32 %[w], %[mu], %[w]\n\t" K2 "v_cmpx_lt_f32_e64 vcc, |%[w]|, %[h]\n\t"
+#define NDDM_K2 "v_add_u32 %[k], 2, %[k]\n\t"
                 asm volatile("s_mov_b64 exec, %[am]\n\t"
-                             NDDM_STEP("r0", "t0") NDDM_STEP("r0", "t1") NDDM_STEP("r1", "t2") NDDM_STEP("r1", "t3")
-                             "s_nop 1\n\ts_mov_b64 %[st], exec\n\ts_mov_b64 exec, -1"
-                             : [w] "+v"(w), [k] "+v"(k), [st] "=s"(still)
-                             : [am] "s"(act_m), [mu] "v"(mu_dt), [h] "v"(h), [r0] "v"(rr[0]), [r1] "v"(rr[2]),
+                             NDDM_STEP("r0", "t0", NDDM_K2) "s_xor_b64 %[am], %[am], vcc\n\t"
+                             NDDM_STEP("r0", "t1", "")      "s_xor_b64 %[am], %[am], vcc\n\t"
+                             NDDM_STEP("r1", "t2", NDDM_K2) "s_xor_b64 %[am], %[am], vcc\n\t"
+                             NDDM_STEP("r1", "t3", "")      "s_andn2_b64 %[am], %[am], vcc\n\t"
+                             "s_cbranch_scc0 1f\n\t"
+                             "s_mov_b64 exec, %[am]\n\t"
+                             "v_subrev_u32 %[k], 1, %[k]\n"
+                             "1:\n\t"
+                             "s_mov_b64 %[am], vcc\n\t"
+                             "s_mov_b64 exec, -1\n\t"
+                             "s_cmp_lt_i32 %[ck], 0\n\t"
+                             "s_cbranch_scc1 2f\n\t"
+                             "v_cmp_gt_i32 vcc, %[ck], %[k]\n\t"
+                             "s_and_b64 %[am], %[am], vcc\n"
+                             "2:"
+                             : [w] "+v"(w), [k] "+v"(k), [am] "+s"(act_m)
+                             : [ck] "s"(cap_k), [mu] "v"(mu_dt), [h] "v"(h), [r0] "v"(rr[0]), [r1] "v"(rr[2]),
                                [t0] "v"(tt[0]), [t1] "v"(tt[1]), [t2] "v"(tt[2]), [t3] "v"(tt[3])
-                             : "vcc");
+                             : "vcc", "scc");
 #undef NDDM_STEP
-                act_m = still & __builtin_amdgcn_ballot_w64(k < A.max_k);      // (still is a subset of the lanes that stepped)
+#undef NDDM_K2
                 if ((int)__popcll(has_m & ~act_m) >= leave_at) break;
                 if (it >= it_limit) break;
                 continue;
