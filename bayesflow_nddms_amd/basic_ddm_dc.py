@@ -12,7 +12,7 @@ import numpy as np
 
 from . import engine
 from .priors import RNG, DevicePrior, draw_prior_basic as draw_prior, prior_N, truncnorm_better  # noqa: F401
-from .simulation import ContextGenerator, GenerativeModel, Prior, Simulator
+from .simulation import ContextGenerator, GenerativeModel, Prior, Simulator, build_generative_model  # noqa: F401
 
 MODEL = engine.BASIC_DDM_DC
 PARAM_NAMES = ("drift", "boundary", "beta", "tau", "dc")   # basic_ddm_dc.py:118 -- the order is the ABI
@@ -77,19 +77,8 @@ def make_generative_model(batched=True, device_prior=False, dt=.01, max_steps=40
     """The reference's wrapper block (basic_ddm_dc.py:130-134).  batched=False keeps the per-set simulator_fun loop
     exactly as BayesFlow runs it; batched=True hands the whole batch to one kernel launch (and, with
     device_prior=True, also draws the parameters on the device)."""
-    experimental_context = ContextGenerator(non_batchable_context_fun=prior_N)
-    prior = Prior(batch_prior_fun=DevicePrior("basic", seed=2023 if seed is None else seed), param_names=PARAM_NAMES) \
-        if device_prior else Prior(prior_fun=draw_prior, param_names=PARAM_NAMES)
-    if batched:
-        fun = lambda p, n: batch_simulate_trials(p, n, dt=dt, max_steps=max_steps, fast=fast, as_numpy=as_numpy)
-        simulator = Simulator(batch_simulator_fun=fun, context_generator=experimental_context)
-    else:
-        fun = lambda p, n: simulate_trials(p, n, dt=dt, max_steps=max_steps, fast=fast)
-        simulator = Simulator(simulator_fun=fun, context_generator=experimental_context)
-    gm = GenerativeModel(prior, simulator, skip_test=skip_test, name="basic_ddm_dc")
-    # how a graph loop re-creates this model on the device (amortizer.Trainer(graph=True) -> graph_trainer.GraphTrainer)
-    gm.graph_spec = dict(model="basic", dt=dt, max_steps=max_steps, seed=2023 if seed is None else seed, n_min=60, n_max=300)
-    return gm
+    return build_generative_model("basic", "basic_ddm_dc", PARAM_NAMES, draw_prior, simulate_trials, batch_simulate_trials, batched,
+                                  device_prior, dt, max_steps, fast, as_numpy, seed, skip_test)
 
 
 def log_likelihood(params, sim_data, per_trial=False):

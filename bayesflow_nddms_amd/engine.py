@@ -39,6 +39,77 @@ def require_device():
     return torch
 
 
+def _device(device):
+    """The torch.device a call runs on: the one named, or the current ROCm device."""
+    torch = _torch()
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _u64(v):
+    """Seeds and set offsets are uint64 in the ABI: a negative or oversized Python int wraps as it would there."""
+    return int(v) & 0xFFFFFFFFFFFFFFFF
+
+
+# what simulate() and simulate_to_host() take as params: (dimensions, size of the last one, the refusal's text)
+_SIM_ROWS = {m: (2, P, f"params must have shape [B, {P}] for this model") for m, P in NPARAMS.items()}
+
+
+def _check_shape(shape, ndim, last, label):
+    # the leading dimension may be empty (no rows is a batch), the inner ones may not
+    if len(shape) != ndim or shape[-1] != last or 0 in shape[1:-1]:
+        raise ValueError(f"{label}, got {tuple(shape)}")
+
+
+def _host_rows(x, ndim, last, label):
+    """Host input (array-like or CPU tensor) as a float64 array, a single item promoted to a batch of one, shape-checked: what the
+    callers' value checks read.  None for a device tensor: those are never read on the host.  `label`: the caller's refusal."""
+    if getattr(x, "is_cuda", False):
+        return None
+    a = np.ascontiguousarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float64)
+    if a.ndim == ndim - 1:
+        a = a[None]
+    _check_shape(a.shape, ndim, last, label)
+    return a
+
+
+def _device_rows(x, host, dev, ndim, last, label):
+    """The float32 contiguous device tensor the kernels read: the upload of `host` (what _host_rows made of x, after the caller's
+    value checks), or the device tensor x itself -- promoted, shape-checked and cast, its values never looked at."""
+    torch = _torch()
+    if host is not None:
+        return torch.as_tensor(host, dtype=torch.float32).contiguous().to(dev)
+    if x.ndim == ndim - 1:
+        x = x[None]
+    _check_shape(x.shape, ndim, last, label)
+    return x.to(dtype=torch.float32).contiguous()
+
+
+def _out_buffer(want, buf, shape, dev):
+    """A float32 output of `shape`: allocated when it is wanted and the caller brought none; a buffer the caller brought is used
+    as it is or refused."""
+    torch = _torch()
+    if buf is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev) if want else None
+    if tuple(buf.shape) != shape or buf.dtype != torch.float32 or not buf.is_contiguous() or not buf.is_cuda:
+        raise ValueError(f"output buffer must be a contiguous float32 device tensor of shape {shape}")
+    return buf
+
+
+def _bounds_device(bounds, B, n_trials, dev):
+    """The explicit-boundary model's per-trial boundaries as f32 [B, n_trials] on the device; host values are checked first."""
+    torch = _torch()
+    if getattr(bounds, "is_cuda", False):
+        return bounds.to(dtype=torch.float32).reshape(B, n_trials).contiguous()
+    b_np = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(B, n_trials))
+    if np.any(b_np < 0) or not np.all(np.isfinite(b_np)):
+        raise ValueError("Trial-level boundary cannot be less than zero")
+    return torch.as_tensor(b_np, dtype=torch.float32).contiguous().to(dev)
+
+
 class StreamState:
     """Functional RNG position: (seed, next set index).  The simulators are stateless apart from this pair, so a
     resumed run continues the stream by restoring it (checkpoint/resume)."""
@@ -70,6 +141,16 @@ def seed(s):
     GLOBAL_STREAM.set_state({"seed": int(s), "offset": 0})
 
 
+def _stream_position(seed, set_offset, stream_state, n_sets):
+    """(seed, set_offset) of a call over n_sets parameter sets, as uint64.  Unless the caller gave both, the position is taken from
+    the stream state -- once, and the stream moves on by n_sets even when one of the two was given."""
+    if seed is None or set_offset is None:
+        s_seed, s_off = (stream_state or GLOBAL_STREAM).take(n_sets)
+        seed = s_seed if seed is None else seed
+        set_offset = s_off if set_offset is None else set_offset
+    return _u64(seed), _u64(set_offset)
+
+
 def max_k_of(max_steps):
     """The reference loops `while ... n_steps < max_steps` with a float cap (basic_ddm_dc.py:87, 95): the largest
     step count reached is ceil(max_steps)."""
@@ -89,6 +170,11 @@ def validate_params_host(model, params):
         lat = p[..., 1] if model == SINGLE_TRIAL else p[..., 5]
         if np.any(lat + 8.0 * np.abs(p[..., 4]) <= 0):
             raise ValueError("per-trial latent N(mean, std) > 0 is (numerically) never satisfied")
+
+
+# the per-model entries that take (params, common arguments, trials, summary, stream) and nothing else
+_PLAIN_ENTRY = {BASIC_DDM_DC: "nddm_basic_ddm_dc_simulate", SINGLE_TRIAL: "nddm_single_trial_simulate",
+                SINGLE_TRIAL_ALT: "nddm_single_trial_alt_simulate"}
 
 
 def simulate(model, params, n_trials, dt=0.01, max_steps=400.0, seed=None, set_offset=None, fast=None,
@@ -118,25 +204,12 @@ def simulate(model, params, n_trials, dt=0.01, max_steps=400.0, seed=None, set_o
     """
     torch = require_device()
     L = _lib.lib()
-    P = NPARAMS[model]
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    on_host = not (isinstance(params, torch.Tensor) and params.is_cuda)
-    if on_host:
-        p_np = np.ascontiguousarray(params.detach().cpu().numpy() if isinstance(params, torch.Tensor) else params,
-                                    dtype=np.float64)
-        if p_np.ndim == 1:
-            p_np = p_np[None]
-        if p_np.ndim != 2 or p_np.shape[1] != P:
-            raise ValueError(f"params must have shape [B, {P}] for this model, got {p_np.shape}")
+    dev = _device(device)
+    rows = _SIM_ROWS[model]
+    p_np = _host_rows(params, *rows)
+    if p_np is not None:
         validate_params_host(model, p_np)
-        p_dev = torch.as_tensor(p_np, dtype=torch.float32).contiguous().to(dev)
-    else:
-        p_dev = params
-        if p_dev.ndim == 1:
-            p_dev = p_dev[None]
-        if p_dev.ndim != 2 or p_dev.shape[1] != P:
-            raise ValueError(f"params must have shape [B, {P}] for this model, got {tuple(p_dev.shape)}")
-        p_dev = p_dev.to(dtype=torch.float32).contiguous()
+    p_dev = _device_rows(params, p_np, dev, *rows)
     B = int(p_dev.shape[0])
     n_trials = int(n_trials)
     if n_trials <= 0:
@@ -151,20 +224,9 @@ def simulate(model, params, n_trials, dt=0.01, max_steps=400.0, seed=None, set_o
     if model == EXPLICIT_BOUNDARY:
         if bounds is None:
             raise ValueError("explicit-boundary model needs `bounds`")
-        if not (isinstance(bounds, torch.Tensor) and bounds.is_cuda):
-            b_np = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(B, n_trials))
-            if np.any(b_np < 0) or not np.all(np.isfinite(b_np)):
-                raise ValueError("Trial-level boundary cannot be less than zero")
-            b_dev = torch.as_tensor(b_np, dtype=torch.float32).contiguous().to(dev)
-        else:
-            b_dev = bounds.to(dtype=torch.float32).reshape(B, n_trials).contiguous()
+        b_dev = _bounds_device(bounds, B, n_trials, dev)
 
-    if seed is None or set_offset is None:
-        s_seed, s_off = (stream_state or GLOBAL_STREAM).take(B)
-        seed = s_seed if seed is None else seed
-        set_offset = s_off if set_offset is None else set_offset
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    set_offset = int(set_offset) & 0xFFFFFFFFFFFFFFFF
+    seed, set_offset = _stream_position(seed, set_offset, stream_state, B)
     fast = DEFAULT_FAST if fast is None else bool(fast)
     flags = (_lib.GAUSS_FAST if fast else _lib.GAUSS_EXACT) | (_lib.BRIDGE if bridge else 0) | (_lib.GAUSS_PACKED if packed else 0) \
         | (_lib.STATE_F64 if state_f64 else 0)
@@ -172,48 +234,34 @@ def simulate(model, params, n_trials, dt=0.01, max_steps=400.0, seed=None, set_o
         raise ValueError("the Brownian-bridge correction is only available for the alpha_not_scaled model")
 
     with torch.cuda.device(dev):
-        if want_trials and out_trials is None:
-            out_trials = torch.empty((B, n_trials, 2), dtype=torch.float32, device=dev)
-        if want_summary and out_summary is None:
-            out_summary = torch.empty((B, SUMMARY_K), dtype=torch.float32, device=dev)
         out_ext = torch.empty((B,), dtype=torch.float32, device=dev) if (want_ext and model == ALPHA_NOT_SCALED) else None
         if want_codes and out_codes is None:
             out_codes = torch.empty((B, n_trials), dtype=torch.int16, device=dev)
         if out_codes is not None and (tuple(out_codes.shape) != (B, n_trials) or out_codes.dtype != torch.int16
                                       or not out_codes.is_contiguous() or not out_codes.is_cuda):
             raise ValueError(f"out_codes must be a contiguous int16 device tensor of shape {(B, n_trials)}")
-        for t, shape in ((out_trials, (B, n_trials, 2)), (out_summary, (B, SUMMARY_K))):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()
-                                  or not t.is_cuda):
-                raise ValueError(f"output buffer must be a contiguous float32 device tensor of shape {shape}")
+        out_trials = _out_buffer(want_trials, out_trials, (B, n_trials, 2), dev)
+        out_summary = _out_buffer(want_summary, out_summary, (B, SUMMARY_K), dev)
         st = torch.cuda.current_stream(dev).cuda_stream
-        pt = lambda t: None if t is None else t.data_ptr()
         if B > 0:
             common = (B, n_trials, float(dt), max_k, seed, set_offset, flags)
             if set_offset_dev is not None and not (isinstance(set_offset_dev, torch.Tensor) and set_offset_dev.is_cuda
                                                    and set_offset_dev.dtype == torch.int64 and set_offset_dev.numel() >= 1):
                 raise ValueError("set_offset_dev must be a device int64 tensor")
             if out_codes is not None:
-                rc = L.nddm_simulate_codes(model, pt(p_dev), *common[:-1], pt(set_offset_dev), flags, pt(out_codes), pt(out_trials),
-                                           pt(out_summary), st)
+                rc = L.nddm_simulate_codes(model, _ptr(p_dev), *common[:-1], _ptr(set_offset_dev), flags, _ptr(out_codes), _ptr(out_trials),
+                                           _ptr(out_summary), st)
             elif set_offset_dev is not None:
-                if not (isinstance(set_offset_dev, torch.Tensor) and set_offset_dev.is_cuda and set_offset_dev.dtype == torch.int64
-                        and set_offset_dev.numel() >= 1):
-                    raise ValueError("set_offset_dev must be a device int64 tensor")
-                rc = L.nddm_simulate_indirect(model, pt(p_dev), pt(b_dev), *common[:-1], set_offset_dev.data_ptr(), flags,
-                                              float(ext_sigma), int(ext_mode), pt(out_trials), pt(out_summary), pt(out_ext), st)
-            elif model == BASIC_DDM_DC:
-                rc = L.nddm_basic_ddm_dc_simulate(pt(p_dev), *common, pt(out_trials), pt(out_summary), st)
-            elif model == SINGLE_TRIAL:
-                rc = L.nddm_single_trial_simulate(pt(p_dev), *common, pt(out_trials), pt(out_summary), st)
-            elif model == SINGLE_TRIAL_ALT:
-                rc = L.nddm_single_trial_alt_simulate(pt(p_dev), *common, pt(out_trials), pt(out_summary), st)
+                rc = L.nddm_simulate_indirect(model, _ptr(p_dev), _ptr(b_dev), *common[:-1], set_offset_dev.data_ptr(), flags,
+                                              float(ext_sigma), int(ext_mode), _ptr(out_trials), _ptr(out_summary), _ptr(out_ext), st)
+            elif model in _PLAIN_ENTRY:
+                rc = getattr(L, _PLAIN_ENTRY[model])(_ptr(p_dev), *common, _ptr(out_trials), _ptr(out_summary), st)
             elif model == ALPHA_NOT_SCALED:
-                rc = L.nddm_alpha_not_scaled_simulate(pt(p_dev), *common, float(ext_sigma), int(ext_mode),
-                                                      pt(out_trials), pt(out_summary), pt(out_ext), st)
+                rc = L.nddm_alpha_not_scaled_simulate(_ptr(p_dev), *common, float(ext_sigma), int(ext_mode),
+                                                      _ptr(out_trials), _ptr(out_summary), _ptr(out_ext), st)
             elif model == EXPLICIT_BOUNDARY:
-                rc = L.nddm_explicit_boundary_simulate(pt(p_dev), pt(b_dev), *common, pt(out_trials),
-                                                       pt(out_summary), st)
+                rc = L.nddm_explicit_boundary_simulate(_ptr(p_dev), _ptr(b_dev), *common, _ptr(out_trials),
+                                                       _ptr(out_summary), st)
             else:
                 raise ValueError("unknown model")
             _lib.check(rc)
@@ -222,14 +270,9 @@ def simulate(model, params, n_trials, dt=0.01, max_steps=400.0, seed=None, set_o
             if b_dev is not None:
                 b_dev.record_stream(torch.cuda.current_stream(dev))
     res = {"seed": seed, "set_offset": set_offset, "params": p_dev}
-    if out_trials is not None:
-        res["trials"] = out_trials
-    if out_summary is not None:
-        res["summary"] = out_summary
-    if out_ext is not None:
-        res["ext"] = out_ext
-    if out_codes is not None:
-        res["codes"] = out_codes
+    for k, v in (("trials", out_trials), ("summary", out_summary), ("ext", out_ext), ("codes", out_codes)):
+        if v is not None:
+            res[k] = v
     return res
 
 
@@ -246,44 +289,26 @@ def simulratcliff(params, n_trials, seed=None, set_offset=None, fast=None, ext_s
     (profiles/r6_ratcliff_agreement.txt), at twice the rate."""
     torch = require_device()
     L = _lib.lib()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if not (isinstance(params, torch.Tensor) and params.is_cuda):
-        p_np = np.ascontiguousarray(params.detach().cpu().numpy() if isinstance(params, torch.Tensor) else params, dtype=np.float64)
-        if p_np.ndim == 1:
-            p_np = p_np[None]
-        if p_np.ndim != 2 or p_np.shape[1] != 6:
-            raise ValueError(f"params must have shape [B, 6] (Nu, Alpha, Beta, Tau, Eta, Varsigma), got {p_np.shape}")
+    dev = _device(device)
+    rows = (2, 6, "params must have shape [B, 6] (Nu, Alpha, Beta, Tau, Eta, Varsigma)")
+    p_np = _host_rows(params, *rows)
+    if p_np is not None:
         validate_params_host(ALPHA_NOT_SCALED, p_np)
         if np.any(p_np[:, 2] < 0) or np.any(p_np[:, 2] > 1) or np.any(p_np[:, 4] < 0):
             raise ValueError("Beta must lie in [0, 1] and Eta must be >= 0")
-        p_dev = torch.as_tensor(p_np, dtype=torch.float32).contiguous().to(dev)
-    else:
-        p_dev = params[None] if params.ndim == 1 else params
-        if p_dev.ndim != 2 or p_dev.shape[1] != 6:
-            raise ValueError(f"params must have shape [B, 6], got {tuple(p_dev.shape)}")
-        p_dev = p_dev.to(dtype=torch.float32).contiguous()
+    p_dev = _device_rows(params, p_np, dev, *rows)
     B, n_trials = int(p_dev.shape[0]), int(n_trials)
     if n_trials <= 0:
         raise ValueError("n_trials must be positive")
-    if seed is None or set_offset is None:
-        s_seed, s_off = (stream_state or GLOBAL_STREAM).take(B)
-        seed = s_seed if seed is None else seed
-        set_offset = s_off if set_offset is None else set_offset
-    seed, set_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(set_offset) & 0xFFFFFFFFFFFFFFFF
+    seed, set_offset = _stream_position(seed, set_offset, stream_state, B)
     fast = DEFAULT_FAST if fast is None else bool(fast)
     with torch.cuda.device(dev):
-        if want_trials and out_trials is None:
-            out_trials = torch.empty((B, n_trials, 2), dtype=torch.float32, device=dev)
-        if want_summary and out_summary is None:
-            out_summary = torch.empty((B, SUMMARY_K), dtype=torch.float32, device=dev)
         out_ext = torch.empty((B,), dtype=torch.float32, device=dev) if want_ext else None
-        for t, shape in ((out_trials, (B, n_trials, 2)), (out_summary, (B, SUMMARY_K))):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
-                raise ValueError(f"output buffer must be a contiguous float32 device tensor of shape {shape}")
-        pt = lambda t: None if t is None else t.data_ptr()
+        out_trials = _out_buffer(want_trials, out_trials, (B, n_trials, 2), dev)
+        out_summary = _out_buffer(want_summary, out_summary, (B, SUMMARY_K), dev)
         if B > 0:
-            _lib.check(L.nddm_simulratcliff(pt(p_dev), B, n_trials, seed, set_offset, _lib.GAUSS_FAST if fast else _lib.GAUSS_EXACT,
-                                            float(ext_sigma), int(ext_mode), pt(out_trials), pt(out_summary), pt(out_ext),
+            _lib.check(L.nddm_simulratcliff(_ptr(p_dev), B, n_trials, seed, set_offset, _lib.GAUSS_FAST if fast else _lib.GAUSS_EXACT,
+                                            float(ext_sigma), int(ext_mode), _ptr(out_trials), _ptr(out_summary), _ptr(out_ext),
                                             torch.cuda.current_stream(dev).cuda_stream))
             p_dev.record_stream(torch.cuda.current_stream(dev))
     res = {"seed": seed, "set_offset": set_offset, "params": p_dev}
@@ -293,27 +318,18 @@ def simulratcliff(params, n_trials, seed=None, set_offset=None, fast=None, ext_s
     return res
 
 
-def _wiener_host_checks(model, p_np, d_np):
-    """Shape and range checks of host-side likelihood inputs (ValueError, before any device work)."""
-    if p_np is not None:
-        P = NPARAMS[model]
-        if p_np.ndim != 2 or p_np.shape[1] != P:
-            raise ValueError(f"params must have shape [R, {P}], got {p_np.shape}")
-        if not np.all(np.isfinite(p_np)):
-            raise ValueError("parameters must be finite")
-        a, beta, tau = p_np[:, 1], p_np[:, 2], p_np[:, 3]
-        s = p_np[:, 4] if model == BASIC_DDM_DC else p_np[:, 5]
-        if np.any(a <= 0) or np.any(s <= 0):
-            raise ValueError("boundary and diffusion coefficient must be > 0")
-        if np.any(beta <= 0) or np.any(beta >= 1):
-            raise ValueError("beta must lie in (0, 1)")
-        if np.any(tau < 0) or (model == ALPHA_NOT_SCALED and np.any(p_np[:, 4] < 0)):
-            raise ValueError("tau and Eta must be >= 0")
-    if d_np is not None:
-        if d_np.ndim != 3 or d_np.shape[2] != 2 or d_np.shape[1] <= 0:
-            raise ValueError(f"data must have shape [D, n_trials, 2], got {d_np.shape}")
-        if model == BASIC_DDM_DC and not np.all(np.isin(d_np[..., 1], (-1.0, 0.0, 1.0))):
-            raise ValueError("basic_ddm_dc data are (rt, choice) with choice in {1, -1, 0}")
+def _wiener_check_params(model, p_np):
+    """Range checks of host-side likelihood parameters (ValueError, before any device work)."""
+    if not np.all(np.isfinite(p_np)):
+        raise ValueError("parameters must be finite")
+    a, beta, tau = p_np[:, 1], p_np[:, 2], p_np[:, 3]
+    s = p_np[:, 4] if model == BASIC_DDM_DC else p_np[:, 5]
+    if np.any(a <= 0) or np.any(s <= 0):
+        raise ValueError("boundary and diffusion coefficient must be > 0")
+    if np.any(beta <= 0) or np.any(beta >= 1):
+        raise ValueError("beta must lie in (0, 1)")
+    if np.any(tau < 0) or (model == ALPHA_NOT_SCALED and np.any(p_np[:, 4] < 0)):
+        raise ValueError("tau and Eta must be >= 0")
 
 
 def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=False, want_sum=True, device=None):
@@ -332,46 +348,31 @@ def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=Fa
     S = int(draws_per_dataset)
     if S <= 0:
         raise ValueError("draws_per_dataset must be > 0")
-    P = NPARAMS[model]
-    p_host = not (hasattr(params, "is_cuda") and params.is_cuda)
-    d_host = not (hasattr(data, "is_cuda") and data.is_cuda)
-    p_np = d_np = None
-    if p_host:
-        p_np = np.asarray(params.detach().cpu().numpy() if hasattr(params, "detach") else params, dtype=np.float64)
-        if p_np.ndim == 1:
-            p_np = p_np[None]
-    if d_host:
-        d_np = np.asarray(data.detach().cpu().numpy() if hasattr(data, "detach") else data, dtype=np.float64)
-        if d_np.ndim == 2:
-            d_np = d_np[None]
-    _wiener_host_checks(model, p_np, d_np)
-    R = p_np.shape[0] if p_host else (1 if params.ndim == 1 else int(params.shape[0]))
-    D = d_np.shape[0] if d_host else (1 if data.ndim == 2 else int(data.shape[0]))
+    p_rows = (2, NPARAMS[model], f"params must have shape [R, {NPARAMS[model]}]")
+    d_rows = (3, 2, "data must have shape [D, n_trials, 2]")
+    # host inputs are refused here, before any device work; a device tensor's shape is checked where it is cast, after the split
+    p_np = _host_rows(params, *p_rows)
+    if p_np is not None:
+        _wiener_check_params(model, p_np)
+    d_np = _host_rows(data, *d_rows)
+    if d_np is not None and model == BASIC_DDM_DC and not np.all(np.isin(d_np[..., 1], (-1.0, 0.0, 1.0))):
+        raise ValueError("basic_ddm_dc data are (rt, choice) with choice in {1, -1, 0}")
+    R = p_np.shape[0] if p_np is not None else (1 if params.ndim == 1 else int(params.shape[0]))
+    D = d_np.shape[0] if d_np is not None else (1 if data.ndim == 2 else int(data.shape[0]))
     if R != D * S:
         raise ValueError(f"params has {R} rows but data holds {D} data sets x draws_per_dataset {S}")
     torch = require_device()
     L = _lib.lib()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = _device(device)
     with torch.cuda.device(dev):
-        if p_host:
-            p_dev = torch.as_tensor(p_np, dtype=torch.float32).to(dev)
-        else:
-            p_dev = (params[None] if params.ndim == 1 else params).to(dtype=torch.float32).contiguous()
-            if p_dev.ndim != 2 or p_dev.shape[1] != P:
-                raise ValueError(f"params must have shape [R, {P}], got {tuple(p_dev.shape)}")
-        if d_host:
-            d_dev = torch.as_tensor(d_np, dtype=torch.float32).to(dev)
-        else:
-            d_dev = (data[None] if data.ndim == 2 else data).to(dtype=torch.float32).contiguous()
-            if d_dev.ndim != 3 or d_dev.shape[2] != 2 or d_dev.shape[1] <= 0:
-                raise ValueError(f"data must have shape [D, n_trials, 2], got {tuple(d_dev.shape)}")
+        p_dev = _device_rows(params, p_np, dev, *p_rows)
+        d_dev = _device_rows(data, d_np, dev, *d_rows)
         N = int(d_dev.shape[1])
         out_t = torch.empty((R, N), dtype=torch.float32, device=dev) if per_trial else None
         out_s = torch.empty((R,), dtype=torch.float64, device=dev) if want_sum else None
-        pt = lambda t: None if t is None else t.data_ptr()
         if R > 0:
             st = torch.cuda.current_stream(dev)
-            _lib.check(L.nddm_wiener_log_likelihood(int(model), pt(p_dev), R, S, pt(d_dev), N, 0, pt(out_t), pt(out_s), st.cuda_stream))
+            _lib.check(L.nddm_wiener_log_likelihood(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, 0, _ptr(out_t), _ptr(out_s), st.cuda_stream))
             p_dev.record_stream(st)
             d_dev.record_stream(st)
     res = {}
@@ -400,20 +401,18 @@ def draw_prior_device(model, batch_size, seed=0, set_offset=0, gamma=1.0, device
     """On-device batched draw_prior (basic_ddm_dc.py:62-80 / single_trial_alpha_not_scaled.py:78-102): f32 [B, P].
     set_offset_dev: as in simulate() (nddm_draw_prior_indirect)."""
     torch = require_device()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    L = _lib.lib()
+    dev = _device(device)
     P = NPARAMS[model]
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty((int(batch_size), P), dtype=torch.float32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
+        position = (model, int(batch_size), _u64(seed), _u64(set_offset))
+        rest = (float(gamma), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         if set_offset_dev is not None:
-            rc = _lib.lib().nddm_draw_prior_indirect(model, int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                     int(set_offset) & 0xFFFFFFFFFFFFFFFF, set_offset_dev.data_ptr(),
-                                                     float(gamma), out.data_ptr(), st)
+            _lib.check(L.nddm_draw_prior_indirect(*position, set_offset_dev.data_ptr(), *rest))
         else:
-            rc = _lib.lib().nddm_draw_prior(model, int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                            int(set_offset) & 0xFFFFFFFFFFFFFFFF, float(gamma), out.data_ptr(), st)
-        _lib.check(rc)
+            _lib.check(L.nddm_draw_prior(*position, *rest))
     return out
 
 
@@ -474,31 +473,17 @@ def simulate_to_host(model, params, n_trials, seed=None, set_offset=None, stream
     bit, the device holds two chunks instead of the whole result, and the 2.4 GB of the 1M x 300 workload are on the host
     47 ms after the call instead of 77 (one launch, then the copy) or 400 (`.cpu()`): profiles/r4_pcie_rate.txt."""
     torch = require_device()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    on_host = not (isinstance(params, torch.Tensor) and params.is_cuda)
-    if on_host:
-        p_np = np.ascontiguousarray(params.detach().cpu().numpy() if isinstance(params, torch.Tensor) else params, dtype=np.float64)
-        if p_np.ndim == 1:
-            p_np = p_np[None]
-        if p_np.ndim != 2 or p_np.shape[1] != NPARAMS[model]:
-            raise ValueError(f"params must have shape [B, {NPARAMS[model]}] for this model, got {p_np.shape}")
+    dev = _device(device)
+    rows = _SIM_ROWS[model]
+    p_np = _host_rows(params, *rows)
+    if p_np is not None:
         validate_params_host(model, p_np)
-        params = torch.as_tensor(p_np, dtype=torch.float32).contiguous().to(dev)
-    elif params.ndim == 1:
-        params = params[None]
+    params = _device_rows(params, p_np, dev, *rows)
     B, n_trials = int(params.shape[0]), int(n_trials)
-    if seed is None or set_offset is None:
-        s_seed, s_off = (stream_state or GLOBAL_STREAM).take(B)
-        seed = s_seed if seed is None else seed
-        set_offset = s_off if set_offset is None else set_offset
-    seed, set_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(set_offset) & 0xFFFFFFFFFFFFFFFF
-    if model == EXPLICIT_BOUNDARY and bounds is not None and not (isinstance(bounds, torch.Tensor) and bounds.is_cuda):
-        b_np = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(B, n_trials))
-        if np.any(b_np < 0) or not np.all(np.isfinite(b_np)):
-            raise ValueError("Trial-level boundary cannot be less than zero")
-        bounds = torch.as_tensor(b_np, dtype=torch.float32).contiguous().to(dev)
-    elif bounds is not None and isinstance(bounds, torch.Tensor):
-        bounds = bounds.reshape(B, n_trials)
+    seed, set_offset = _stream_position(seed, set_offset, stream_state, B)
+    # a missing `bounds` is left to simulate(), which refuses it in its own order of checks
+    if model == EXPLICIT_BOUNDARY and bounds is not None:
+        bounds = _bounds_device(bounds, B, n_trials, dev)
     want_ext = bool(want_ext and model == ALPHA_NOT_SCALED)
     row_bytes = n_trials * 8 if want_trials else 4 * SUMMARY_K
     chunk_bytes = HOST_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
@@ -527,7 +512,7 @@ def simulate_to_host(model, params, n_trials, seed=None, set_offset=None, stream
             n = hi - lo
             tr = bufs[b]["trials"][:n] if want_trials else None
             sm = bufs[b]["summary"][:n] if want_summary else None
-            r = simulate(model, params[lo:hi], n_trials, set_offset=(set_offset + lo) & 0xFFFFFFFFFFFFFFFF,
+            r = simulate(model, params[lo:hi], n_trials, set_offset=_u64(set_offset + lo),
                          bounds=None if bounds is None else bounds[lo:hi], out_trials=tr, out_summary=sm, **common)
             ev = torch.cuda.Event()
             ev.record(cur)
@@ -567,7 +552,7 @@ class debug_trace:
     def __init__(self, waves=16384, chunks=0, device=None):
         torch = require_device()
         self.waves, self.chunks = int(waves), int(chunks)
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = _device(device)
         self.buf = torch.zeros(8 * self.waves + self.chunks, dtype=torch.int64, device=dev)
 
     def __enter__(self):

@@ -23,7 +23,7 @@ def _dev(x, dev):
 def _basic_logpdf(y, drift, boundary, beta, tau, dc, device=None):
     """log f of signed RTs under the basic model's parameters (no clipping, no censoring), every argument broadcast."""
     torch = engine.require_device()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = engine._device(device)
     y = _dev(y, dev)
     cols = [_dev(c, dev) for c in (drift, boundary, beta, tau, dc)]
     shape = tuple(torch.broadcast_shapes(y.shape, *(c.shape for c in cols)))
@@ -58,7 +58,7 @@ def diffusion_lpdf(Y, boundary, ter, bias, drift, dc, stan_floor=False, device=N
     stan_floor=False (the default): the math -- |Y| <= ter gives -inf.  stan_floor=True: the reference's substitution for |Y| < ter,
     wiener_lpdf(ter + 0.0001 | ...) at the UPPER boundary whatever the sign of Y (:122-123), for like-for-like comparison with its fits."""
     torch = engine.require_device()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = engine._device(device)
     Y = _dev(Y, dev)
     if stan_floor:
         t = _dev(ter, dev)

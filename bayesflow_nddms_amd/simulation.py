@@ -135,6 +135,27 @@ class Simulator:
         return out
 
 
+def build_generative_model(kind, name, param_names, draw_prior, simulate_trials, batch_simulate_trials, batched, device_prior,
+                           dt, max_steps, fast, as_numpy, seed, skip_test):
+    """The reference's wrapper block (basic_ddm_dc.py:130-134 / single_trial_alpha_not_scaled.py:160-164) around one model module's
+    functions: what both modules' make_generative_model return.  `kind` names the model to priors.DevicePrior and the graph loop."""
+    from .priors import DevicePrior, prior_N
+    seed = 2023 if seed is None else seed
+    experimental_context = ContextGenerator(non_batchable_context_fun=prior_N)
+    prior = Prior(batch_prior_fun=DevicePrior(kind, seed=seed), param_names=param_names) \
+        if device_prior else Prior(prior_fun=draw_prior, param_names=param_names)
+    if batched:
+        fun = lambda p, n: batch_simulate_trials(p, n, dt=dt, max_steps=max_steps, fast=fast, as_numpy=as_numpy)
+        simulator = Simulator(batch_simulator_fun=fun, context_generator=experimental_context)
+    else:
+        fun = lambda p, n: simulate_trials(p, n, dt=dt, max_steps=max_steps, fast=fast)
+        simulator = Simulator(simulator_fun=fun, context_generator=experimental_context)
+    gm = GenerativeModel(prior, simulator, skip_test=skip_test, name=name)
+    # how a graph loop re-creates this model on the device (amortizer.Trainer(graph=True) -> graph_trainer.GraphTrainer)
+    gm.graph_spec = dict(model=kind, dt=dt, max_steps=max_steps, seed=seed, n_min=60, n_max=300)
+    return gm
+
+
 class GenerativeModel:
     """bf.simulation.GenerativeModel(prior, simulator): `generative_model(batch_size)` returns the dictionary the
     reference's configurators consume.  Like BayesFlow, construction runs a small self-test (batch of 2) unless

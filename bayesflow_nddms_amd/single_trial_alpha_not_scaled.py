@@ -10,7 +10,7 @@ from . import engine
 from .basic_ddm_dc import configurator as _basic_configurator
 from .priors import (DevicePrior, draw_prior_scale, draw_prior_single as draw_prior, prior_N,  # noqa: F401
                      truncnorm_better)
-from .simulation import ContextGenerator, GenerativeModel, Prior, Simulator
+from .simulation import ContextGenerator, GenerativeModel, Prior, Simulator, build_generative_model  # noqa: F401
 
 PARAM_NAMES = ("drift", "mu_alpha", "beta", "ter", "std_alpha", "dc", "sigma1")   # :148 -- the order is the ABI
 num_params = 7
@@ -108,16 +108,5 @@ def make_generative_model(batched=True, device_prior=False, fine=False, fast=Non
                           skip_test=False):
     """The reference's wrapper block (:160-164); fine=True builds generative_model_fine (:1726-1728)."""
     dt, max_steps = (.001, 4000) if fine else (.01, 400.)
-    experimental_context = ContextGenerator(non_batchable_context_fun=prior_N)
-    prior = Prior(batch_prior_fun=DevicePrior("single", seed=2023 if seed is None else seed), param_names=PARAM_NAMES) \
-        if device_prior else Prior(prior_fun=draw_prior, param_names=PARAM_NAMES)
-    if batched:
-        fun = lambda p, n: batch_simulate_trials(p, n, dt=dt, max_steps=max_steps, fast=fast, as_numpy=as_numpy)
-        simulator = Simulator(batch_simulator_fun=fun, context_generator=experimental_context)
-    else:
-        fun = lambda p, n: simulate_trials(p, n, dt=dt, max_steps=max_steps, fast=fast)
-        simulator = Simulator(simulator_fun=fun, context_generator=experimental_context)
-    gm = GenerativeModel(prior, simulator, skip_test=skip_test, name="single_trial_alpha_not_scaled")
-    # how a graph loop re-creates this model on the device (amortizer.Trainer(graph=True) -> graph_trainer.GraphTrainer)
-    gm.graph_spec = dict(model="single", dt=dt, max_steps=max_steps, seed=2023 if seed is None else seed, n_min=60, n_max=300)
-    return gm
+    return build_generative_model("single", "single_trial_alpha_not_scaled", PARAM_NAMES, draw_prior, simulate_trials,
+                                  batch_simulate_trials, batched, device_prior, dt, max_steps, fast, as_numpy, seed, skip_test)
