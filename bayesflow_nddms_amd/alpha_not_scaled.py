@@ -111,3 +111,22 @@ def log_likelihood(params, y, per_trial=False):
         raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
     r = engine.wiener_log_likelihood(engine.ALPHA_NOT_SCALED, p, d, draws_per_dataset=R // D, per_trial=per_trial)
     return (r["loglik"], r["trial_logp"]) if per_trial else r["loglik"]
+
+
+def cdf(params, y):
+    """P(T <= |y| - Tau, the boundary the sign of y names | params) of the generator's model (drift ~ N(Nu, Eta) integrated out, Nu clipped
+    to +-5), one launch (engine.wiener_cdf): the arguments of log_likelihood.  y == 0 gives NaN.  Returns float32 [R, n_trials] on the
+    device."""
+    p = params if hasattr(params, "is_cuda") else np.asarray(params, dtype=np.float64).reshape(-1, 6)
+    if hasattr(y, "is_cuda"):
+        import torch
+        yy = y[None] if y.ndim == 1 else y
+        d = torch.stack([yy, (torch.sign(yy) + 1) / 2], -1)
+    else:
+        yy = np.asarray(y, dtype=np.float64)
+        yy = yy[None] if yy.ndim == 1 else yy
+        d = np.stack([yy, (np.sign(yy) + 1) / 2], -1)
+    R, D = (p.shape[0] if p.ndim == 2 else 1), d.shape[0]
+    if R % D:
+        raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
+    return engine.wiener_cdf(engine.ALPHA_NOT_SCALED, p, d, draws_per_dataset=R // D, want_p_upper=False)["cdf"]

@@ -94,3 +94,15 @@ def log_likelihood(params, sim_data, per_trial=False):
         raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
     r = engine.wiener_log_likelihood(MODEL, p, d, draws_per_dataset=R // D, per_trial=per_trial)
     return (r["loglik"], r["trial_logp"]) if per_trial else r["loglik"]
+
+
+def cdf(params, sim_data):
+    """P(T <= rt - tau, the boundary each trial ended on | params), one launch (engine.wiener_cdf): the arguments of log_likelihood.  A
+    timeout (choice 0) gives P(T <= rt - tau) over both boundaries.  Returns float32 [R, n_trials] on the device."""
+    p = params if hasattr(params, "is_cuda") else np.asarray(params, dtype=np.float64).reshape(-1, 5)
+    d = sim_data if hasattr(sim_data, "is_cuda") else np.asarray(sim_data, dtype=np.float64)
+    R = p.shape[0] if p.ndim == 2 else 1
+    D = d.shape[0] if d.ndim == 3 else 1
+    if R % D:
+        raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
+    return engine.wiener_cdf(MODEL, p, d, draws_per_dataset=R // D, want_p_upper=False)["cdf"]

@@ -114,3 +114,39 @@ def posterior_log_likelihood(samples, data, model):
     flat = s.reshape(D * S, P) if hasattr(s, "is_cuda") else np.asarray(s, dtype=np.float64).reshape(D * S, P)
     ll = engine.wiener_log_likelihood(model, flat, d, draws_per_dataset=S)["loglik"].reshape(D, S)
     return ll[0] if single else ll
+
+
+def signed_cdf_analytic(trials, params, model):
+    """The exact law's distribution function of the SIGNED response time, G(y) = P(signed RT <= y), at every trial of every set:
+    trials [B, N, 2] in the simulator's format (model = engine.BASIC_DDM_DC: (rt, choice); engine.ALPHA_NOT_SCALED: (y, acc)), params
+    [B, P] -> float32 [B, N] on the device, one launch (engine.wiener_cdf):
+        G = P_lo - F_lo(rt - tau) on the lower boundary,   G = P_lo + F_up(rt - tau) on the upper one.
+    A timeout (choice 0 / y == 0) has no signed time: NaN."""
+    from . import engine
+    torch = engine.require_device()
+    r = engine.wiener_cdf(model, params, trials, draws_per_dataset=1)
+    t = trials if hasattr(trials, "is_cuda") else torch.as_tensor(np.asarray(trials, dtype=np.float32), device=r["cdf"].device)
+    t = t[None] if t.ndim == 2 else t
+    side = t[..., 1] if model == engine.BASIC_DDM_DC else t[..., 0]
+    p_lo = (1.0 - r["p_upper"])[:, None]
+    g = torch.where(side > 0, p_lo + r["cdf"], p_lo - r["cdf"])
+    return torch.where(side == 0, torch.full_like(g, float("nan")), g)
+
+
+def ks_analytic(trials, params, model):
+    """One-sample Kolmogorov-Smirnov distance of each set's signed response times from the exact law's G (signed_cdf_analytic):
+    sup_y |ECDF(y) - G(y)| = max_i max(|i/n - G(y_(i))|, |(i-1)/n - G(y_(i))|) over the sorted sample -> float64 [B] on the device,
+    no host synchronisation (a sort along the trial axis, one kernel launch, a max).  A set that holds a timeout (choice 0 / y == 0)
+    gives NaN for that set: a timeout has no place on the signed axis."""
+    from . import engine
+    torch = engine.require_device()
+    g = signed_cdf_analytic(trials, params, model).double()
+    n = g.shape[1]
+    t = trials if hasattr(trials, "is_cuda") else torch.as_tensor(np.asarray(trials, dtype=np.float32), device=g.device)
+    t = t[None] if t.ndim == 2 else t
+    y = t[..., 0] * t[..., 1] if model == engine.BASIC_DDM_DC else t[..., 0]
+    gs = torch.gather(g, 1, torch.sort(y, dim=1).indices)
+    i = torch.arange(1, n + 1, dtype=torch.float64, device=g.device)[None, :]
+    dist = torch.maximum((i / n - gs).abs(), ((i - 1.0) / n - gs).abs())
+    ks = dist.max(dim=1).values
+    return torch.where(torch.isnan(g).any(dim=1), torch.full_like(ks, float("nan")), ks)

@@ -332,25 +332,19 @@ def _wiener_check_params(model, p_np):
         raise ValueError("tau and Eta must be >= 0")
 
 
-def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=False, want_sum=True, device=None):
-    """Log-likelihood of observed trials under the Wiener first-passage density (include/nddm.h: nddm_wiener_log_likelihood), one
-    kernel launch: the density JAGS dwiener / Stan wiener_lpdf evaluate in the reference's likelihood-based fits.
-
-    model: BASIC_DDM_DC (params [R, 5], data (rt, choice); choice 0 = a timeout, scored as log P(T > rt - tau)) or ALPHA_NOT_SCALED
-    (params [R, 6], drift ~ N(Nu, Eta) integrated out, Nu clipped to +-5; data (y, acc), y == 0 gives NaN).  data: [D, n_trials, 2]
-    in the simulator's output format, R = D * draws_per_dataset, row r scored against data set r // draws_per_dataset.
-    Returns a dict of device tensors: 'loglik' float64 [R] (want_sum) and 'trial_logp' float32 [R, n_trials] (per_trial).
-    Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN."""
+def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs):
+    """The front end wiener_log_likelihood and wiener_cdf share: host inputs are refused here (ValueError), before any device work; a
+    device tensor's shape is checked where it is cast, after the split.  -> (S, params' and data's row descriptions, the host arrays or
+    None, R).  `what`: the quantity the model would have to have a closed form of; `outputs`: the caller's two output switches by name."""
     if model not in (BASIC_DDM_DC, ALPHA_NOT_SCALED):
-        raise ValueError(f"model {model} has no closed-form likelihood here (BASIC_DDM_DC and ALPHA_NOT_SCALED only)")
-    if not (per_trial or want_sum):
-        raise ValueError("ask for per_trial and/or want_sum")
+        raise ValueError(f"model {model} has no closed-form {what} here (BASIC_DDM_DC and ALPHA_NOT_SCALED only)")
+    if not any(outputs.values()):
+        raise ValueError("ask for " + " and/or ".join(outputs))
     S = int(draws_per_dataset)
     if S <= 0:
         raise ValueError("draws_per_dataset must be > 0")
     p_rows = (2, NPARAMS[model], f"params must have shape [R, {NPARAMS[model]}]")
     d_rows = (3, 2, "data must have shape [D, n_trials, 2]")
-    # host inputs are refused here, before any device work; a device tensor's shape is checked where it is cast, after the split
     p_np = _host_rows(params, *p_rows)
     if p_np is not None:
         _wiener_check_params(model, p_np)
@@ -361,6 +355,20 @@ def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=Fa
     D = d_np.shape[0] if d_np is not None else (1 if data.ndim == 2 else int(data.shape[0]))
     if R != D * S:
         raise ValueError(f"params has {R} rows but data holds {D} data sets x draws_per_dataset {S}")
+    return S, p_rows, d_rows, p_np, d_np, R
+
+
+def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=False, want_sum=True, device=None):
+    """Log-likelihood of observed trials under the Wiener first-passage density (include/nddm.h: nddm_wiener_log_likelihood), one
+    kernel launch: the density JAGS dwiener / Stan wiener_lpdf evaluate in the reference's likelihood-based fits.
+
+    model: BASIC_DDM_DC (params [R, 5], data (rt, choice); choice 0 = a timeout, scored as log P(T > rt - tau)) or ALPHA_NOT_SCALED
+    (params [R, 6], drift ~ N(Nu, Eta) integrated out, Nu clipped to +-5; data (y, acc), y == 0 gives NaN).  data: [D, n_trials, 2]
+    in the simulator's output format, R = D * draws_per_dataset, row r scored against data set r // draws_per_dataset.
+    Returns a dict of device tensors: 'loglik' float64 [R] (want_sum) and 'trial_logp' float32 [R, n_trials] (per_trial).
+    Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN."""
+    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, data, draws_per_dataset, "likelihood",
+                                                           {"per_trial": per_trial, "want_sum": want_sum})
     torch = require_device()
     L = _lib.lib()
     dev = _device(device)
@@ -380,6 +388,38 @@ def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=Fa
         res["loglik"] = out_s
     if out_t is not None:
         res["trial_logp"] = out_t
+    return res
+
+
+def wiener_cdf(model, params, data, draws_per_dataset=1, want_cdf=True, want_p_upper=True, device=None):
+    """Distribution function of observed trials under the Wiener first-passage law and the choice probability (include/nddm.h:
+    nddm_wiener_cdf), one kernel launch: RWiener / HDDM pwiener, the companion of wiener_log_likelihood, whose arguments these are.
+
+    Returns a dict of float32 device tensors: 'cdf' [R, n_trials] (want_cdf) = P(T <= rt - tau, the boundary the trial ended on), the
+    defective distribution function -- 0 for rt <= tau; a basic_ddm_dc timeout (choice 0) gives P(T <= rt - tau) over both boundaries,
+    an alpha_not_scaled y == 0 NaN -- and 'p_upper' [R] (want_p_upper) = P(upper boundary), drift variability integrated out.
+    Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN."""
+    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, data, draws_per_dataset, "distribution function",
+                                                           {"want_cdf": want_cdf, "want_p_upper": want_p_upper})
+    torch = require_device()
+    L = _lib.lib()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        p_dev = _device_rows(params, p_np, dev, *p_rows)
+        d_dev = _device_rows(data, d_np, dev, *d_rows)
+        N = int(d_dev.shape[1])
+        out_c = torch.empty((R, N), dtype=torch.float32, device=dev) if want_cdf else None
+        out_p = torch.empty((R,), dtype=torch.float32, device=dev) if want_p_upper else None
+        if R > 0:
+            st = torch.cuda.current_stream(dev)
+            _lib.check(L.nddm_wiener_cdf(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, 0, _ptr(out_c), _ptr(out_p), st.cuda_stream))
+            p_dev.record_stream(st)
+            d_dev.record_stream(st)
+    res = {}
+    if out_c is not None:
+        res["cdf"] = out_c
+    if out_p is not None:
+        res["p_upper"] = out_p
     return res
 
 

@@ -3,6 +3,8 @@
 
     dwiener_logpdf(y, alpha, tau, beta, delta)                  JAGS dwiener (basic_ddm_dc_pyjags.py:129-133, alpha_not_scaled.py:170-176)
     diffusion_lpdf(Y, boundary, ter, bias, drift, dc)           the Stan function of basic_ddm_dc_pystan2.py:119-131
+    pwiener(q, alpha, tau, beta, delta)                         RWiener / HDDM pwiener, dwiener's distribution function (nddm_wiener_cdf)
+    wiener_choice_prob(alpha, beta, delta, eta, varsigma)       P(upper boundary), drift variability integrated out
 
 Both take numpy arrays, scalars or device tensors, broadcast them against each other (numpy rules), score every element in ONE kernel
 launch and return a float32 device tensor of the broadcast shape.  The sign of y / Y is the response: positive = upper boundary.
@@ -20,10 +22,11 @@ def _dev(x, dev):
     return torch.as_tensor(np.asarray(x, dtype=np.float32), device=dev)
 
 
-def _basic_logpdf(y, drift, boundary, beta, tau, dc, device=None):
-    """log f of signed RTs under the basic model's parameters (no clipping, no censoring), every argument broadcast."""
+def _basic_rows(y, drift, boundary, beta, tau, dc, dev):
+    """Signed RTs and the basic model's parameters, every argument broadcast (numpy rules) -> (params [R, 5], data [R, n, 2] in the
+    simulator's format, the broadcast shape): one row per leading index where the parameters are constant along the last axis, else one
+    row per element."""
     torch = engine.require_device()
-    dev = engine._device(device)
     y = _dev(y, dev)
     cols = [_dev(c, dev) for c in (drift, boundary, beta, tau, dc)]
     shape = tuple(torch.broadcast_shapes(y.shape, *(c.shape for c in cols)))
@@ -38,9 +41,17 @@ def _basic_logpdf(y, drift, boundary, beta, tau, dc, device=None):
         p = torch.stack([c.expand(full) for c in cols], -1).reshape(-1, 5)
         yy = y.expand(full).reshape(-1, 1)
     data = torch.stack([yy.abs(), torch.where(yy >= 0, 1.0, -1.0).to(torch.float32)], -1).contiguous()
+    return p.contiguous(), data, shape
+
+
+def _basic_logpdf(y, drift, boundary, beta, tau, dc, device=None):
+    """log f of signed RTs under the basic model's parameters (no clipping, no censoring), every argument broadcast."""
+    torch = engine.require_device()
+    dev = engine._device(device)
+    p, data, shape = _basic_rows(y, drift, boundary, beta, tau, dc, dev)
     if p.shape[0] == 0 or data.shape[1] == 0:
         return torch.empty(shape, dtype=torch.float32, device=dev)
-    out = engine.wiener_log_likelihood(engine.BASIC_DDM_DC, p.contiguous(), data, per_trial=True, want_sum=False, device=dev)
+    out = engine.wiener_log_likelihood(engine.BASIC_DDM_DC, p, data, per_trial=True, want_sum=False, device=dev)
     return out["trial_logp"].reshape(shape)
 
 
@@ -64,3 +75,34 @@ def diffusion_lpdf(Y, boundary, ter, bias, drift, dc, stan_floor=False, device=N
         t = _dev(ter, dev)
         Y = torch.where(Y.abs() < t, t + torch.tensor(0.0001, dtype=torch.float32, device=dev), Y)
     return _basic_logpdf(Y, drift, boundary, bias, ter, dc, device=dev)
+
+
+def pwiener(q, alpha, tau, beta, delta, device=None):
+    """RWiener / HDDM `pwiener(q, alpha, tau, beta, delta)`: the distribution function of dwiener, P(RT <= |q|, the boundary the sign of q
+    names) -- positive q: upper boundary -- in units of a diffusion coefficient of 1.  DEFECTIVE: its limit in |q| is the boundary's
+    probability, so pwiener(q) + pwiener(-q) -> 1.  Broadcasts as dwiener_logpdf does, one kernel launch; returns a float32 device
+    tensor of the broadcast shape (0 for |q| <= tau, NaN for invalid parameters)."""
+    torch = engine.require_device()
+    dev = engine._device(device)
+    p, data, shape = _basic_rows(q, delta, alpha, beta, tau, 1.0, dev)
+    if p.shape[0] == 0 or data.shape[1] == 0:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    return engine.wiener_cdf(engine.BASIC_DDM_DC, p, data, want_p_upper=False, device=dev)["cdf"].reshape(shape)
+
+
+def wiener_choice_prob(alpha, beta, delta, eta=0.0, varsigma=1.0, device=None):
+    """P(upper boundary) of a diffusion with boundary separation alpha, relative start beta, drift ~ N(delta, eta^2) and diffusion
+    coefficient varsigma, every argument broadcast: float32 device tensor of the broadcast shape (one launch, no trials read).  No
+    clipping of the drift: a |delta| beyond the alpha_not_scaled kernel's +-5 is brought inside by rescaling alpha, delta, eta and
+    varsigma together, which leaves the process unchanged."""
+    torch = engine.require_device()
+    dev = engine._device(device)
+    cols = [_dev(c, dev) for c in (delta, alpha, beta, 0.0, eta, varsigma)]
+    k = 5.0 / cols[0].abs().clamp(min=5.0)
+    cols = [cols[0] * k, cols[1] * k, cols[2], cols[3], cols[4] * k, cols[5] * k]
+    shape = tuple(torch.broadcast_shapes(*(c.shape for c in cols)))
+    p = torch.stack([c.expand(shape) for c in cols], -1).reshape(-1, 6).contiguous()
+    if p.shape[0] == 0:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    data = torch.zeros((p.shape[0], 1, 2), dtype=torch.float32, device=dev)
+    return engine.wiener_cdf(engine.ALPHA_NOT_SCALED, p, data, want_cdf=False, device=dev)["p_upper"].reshape(shape)

@@ -68,6 +68,7 @@ extern "C" {
  *    replayed into it); a `stream` the HIP runtime does not know is refused with NDDM_ERR_HIP (validated with hipStreamGetDevice at entry).  The random stream is ABI 2's. */
 /* 4: NDDM_STATE_F64 (flag 8), nddm_build_info, nddm_simulratcliff.  The random stream and every ABI-3 entry point are unchanged. */
 /* 4 (additive): nddm_wiener_log_likelihood.  No existing entry point changes. */
+/* 4 (additive): nddm_wiener_cdf.  No existing entry point changes. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -261,6 +262,22 @@ int nddm_simulratcliff(const float *params, int64_t B, int32_t n_trials, uint64_
 int nddm_wiener_log_likelihood(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
                                int32_t n_trials, uint32_t flags, float *out_trial_logp /* [R, n_trials] or NULL */,
                                double *out_loglik /* [R] or NULL */, void *stream);
+
+/* The distribution function of the same first-passage law (RWiener / HDDM pwiener, the companion of dwiener) and the choice
+ * probability: where in its distribution an observed response time falls -- posterior predictive p-values, probability-integral
+ * transforms, one-sample KS distances against the exact law, censoring and truncation.  (ABI 4, additive)
+ *   model, params, draws_per_dataset, data, flags: exactly as nddm_wiener_log_likelihood takes them; data may be NULL when out_cdf is
+ *   out_cdf            device f32 [R, n_trials] or NULL: P(T <= rt - tau, the boundary trial i ended on | row r), the DEFECTIVE distribution
+ *                      function (its limit is the boundary's probability); rt <= tau gives 0.  basic_ddm_dc choice 0 (a timeout) gives
+ *                      P(T <= rt - tau) over both boundaries, 1 - S of the censored likelihood; alpha_not_scaled y == 0 gives NaN
+ *   out_p_upper        device f32 [R] or NULL (not both NULL): P(upper boundary | row r), drift variability integrated out
+ * Absolute accuracy 2e-5 (measured: DESIGN.md section 12); relative accuracy in the far lower tail is not promised.  A value depends on
+ * (row, trial) alone: the same bits whatever the layout, launch, stream or capture.  Invalid rows give NaN (their trials and their
+ * P(upper)) as in nddm_wiener_log_likelihood, whose error checks, their order and their status codes this entry shares.  No scratch
+ * memory: a call made while `stream` is capturing is one kernel node.  The math: csrc/nddm_wiener_cdf.h, DESIGN.md section 12. */
+int nddm_wiener_cdf(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data, int32_t n_trials,
+                    uint32_t flags /* 0, reserved */, float *out_cdf /* [R, n_trials] or NULL */,
+                    float *out_p_upper /* [R] or NULL; not both NULL */, void *stream);
 
 /* replaces the per-trial loop over diffusion_trial(drift, bound_trial, beta, ter, dc),
  * imputation_from_stahl_not_scaled.py:120-148, :207-213.  bounds: device f32 [B, n_trials].

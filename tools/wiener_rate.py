@@ -8,8 +8,15 @@ composed from PyTorch elementwise ops in the same process (the yardstick).  Prin
   broadcast_ans     the same for alpha_not_scaled (drift variability integrated out: one more v_rcp / v_log per evaluation)
   torch_composed    the fixed-trip formula of the kernel as PyTorch elementwise ops on 100 000 rows x 300 trials (basic, eta = 0)
 
+With --cdf: nddm_wiener_cdf (csrc/nddm_wiener_cdf.h) instead, every shape writing its [R, 300] float32 output (8 + 4 B per evaluation):
+  cdf_paired_eta0      basic_ddm_dc, 200 000 rows x 300 trials, each row against its own data set
+  cdf_paired_eta       alpha_not_scaled with Eta in (0, 1.5): the large-time form's 16-node rule, the small-time form's closed one
+  cdf_broadcast_eta0   100 data sets x 2 000 draws x 300 trials, basic_ddm_dc
+  cdf_broadcast_eta    the same for alpha_not_scaled with Eta in (0, 1.5)
+  cdf_torch_composed   the eta = 0 formula of the kernel as PyTorch elementwise ops (torch.special.erfcx) on 100 000 rows x 300 trials
+
 Each shape runs in a child process of its own under `timeout` (a step that faults or hangs ends the tool; nothing further starts).
-Usage: python tools/wiener_rate.py [--json OUT] [--reps 10]        (one shape: --only NAME)
+Usage: python tools/wiener_rate.py [--cdf] [--json OUT] [--reps 10]        (one shape: --only NAME)
 """
 import argparse
 import json
@@ -20,6 +27,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = ("paired_sums", "paired_trials", "broadcast_sums", "broadcast_ans", "torch_composed")
+CDF_SHAPES = ("cdf_paired_eta0", "cdf_paired_eta", "cdf_broadcast_eta0", "cdf_broadcast_eta", "cdf_torch_composed")
 HBM_BPS = 8e12
 
 
@@ -72,7 +80,82 @@ def torch_logpdf(torch, p, d):
     return torch.where(t > 0, lf, torch.full_like(lf, -math.inf))
 
 
+def torch_cdf(torch, p, d):
+    """The kernel's distribution function (basic, eta = 0) from PyTorch elementwise ops: p [R, 5] against d [R, N, 2]."""
+    v, a, beta, tau, s = (p[:, i:i + 1] for i in range(5))
+    rt, ch = d[..., 0], d[..., 1]
+    up = ch > 0
+    ap, vp = a / s, v / s
+    w = torch.where(up, 1 - beta, beta)
+    nu = torch.where(up, -vp, vp)
+    t = (rt - tau).clamp(min=1e-30)
+    aw = ap * w
+    d0 = -nu * aw - nu * nu * t / 2
+    rs = torch.rsqrt(2 * t)
+    small = torch.zeros_like(t)
+    for j in range(4):
+        r = ap * (j + 1 - w) if j & 1 else ap * (j + w)
+        eg = torch.exp(d0 - r * r / (2 * t))
+        xa, xb = (r - nu * t) * rs, (r + nu * t) * rs
+        ta, tb = eg * torch.special.erfcx(xa.abs()), eg * torch.special.erfcx(xb.abs())
+        term = torch.where(xa < 0, 2 * torch.exp(-(aw + r) * nu) - ta, ta) + torch.where(xb < 0, 2 * torch.exp(-(aw - r) * nu) - tb, tb)
+        small = small - term / 2 if j & 1 else small + term / 2
+    m = 2 * nu.abs() * ap
+    ms = m.clamp(min=1e-6)
+    ratio = torch.expm1(-ms * (1 - w)) / torch.expm1(-ms)
+    P = torch.where(m < 1e-6, 1 - w, torch.where(nu > 0, torch.exp(-ms * w) * ratio, ratio))
+    q = torch.exp(-math.pi ** 2 * t / (2 * ap * ap))
+    lam = math.pi ** 2 / (ap * ap)
+    tail = sum(k * torch.sin(k * math.pi * w) * q ** (k * k) / (nu * nu + k * k * lam) for k in range(1, 5))
+    large = P - 2 * math.pi / (ap * ap) * torch.exp(d0) * tail
+    F = torch.where(t < 0.375 * ap * ap, small, large)
+    return torch.where(rt - tau > 0, torch.minimum(F.clamp(min=0), P), torch.zeros_like(F))
+
+
+def run_cdf(name, reps):
+    sys.path.insert(0, ROOT)
+    import torch
+    from bayesflow_nddms_amd import _lib, engine
+    L = _lib.lib()
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(7)
+    st = lambda: torch.cuda.current_stream().cuda_stream
+    N = 300
+    ans = name.endswith("_eta")
+
+    def params(R):
+        b = _basic_params(torch, R, gen)
+        if not ans:
+            return b, 0
+        eta = torch.rand(R, generator=gen, device="cuda") * 1.5
+        return torch.stack([b[:, 0], b[:, 1], b[:, 2], b[:, 3], eta, b[:, 4]], 1).contiguous(), engine.ALPHA_NOT_SCALED
+
+    res = {}
+    if name == "cdf_torch_composed":
+        R = 100_000
+        p, d = _basic_params(torch, R, gen), _data(torch, R, N, gen)
+        k = engine.wiener_cdf(0, p[:1000], d[:1000], want_p_upper=False)["cdf"]
+        res["max_abs_diff_vs_kernel_first_1000_rows"] = (torch_cdf(torch, p[:1000], d[:1000]) - k).abs().max().item()
+        fn = lambda: torch_cdf(torch, p, d)
+    else:
+        D, S = (200_000, 1) if "paired" in name else (100, 2_000)
+        R = D * S
+        (p, model), d = params(R), _data(torch, D, N, gen, signed=ans)
+        out = torch.empty((R, N), dtype=torch.float32, device="cuda")
+        fn = lambda: _lib.check(L.nddm_wiener_cdf(model, p.data_ptr(), R, S, d.data_ptr(), N, 0, out.data_ptr(), None, st()))
+        res["small_time_fraction"] = ((d[..., 0].abs()[:, None, :] - p.reshape(D, S, -1)[..., 3:4])
+                                      < 0.375 * (p.reshape(D, S, -1)[..., 1:2] / p.reshape(D, S, -1)[..., -1:]) ** 2)[:, :8].float().mean().item()
+    evals = R * N
+    nbytes = d.numel() * 4 + p.numel() * 4 + evals * 4
+    med, best = _time(torch, fn, reps)
+    res = {"shape": name, "evals": evals, "ms_median": round(med, 4), "ms_best": round(best, 4), "evals_per_s": evals / (med * 1e-3),
+           "GB_per_s": nbytes / (med * 1e-3) / 1e9, "frac_of_8TBps": nbytes / (med * 1e-3) / HBM_BPS, **res}
+    print(json.dumps(res), flush=True)
+
+
 def run_one(name, reps):
+    if name in CDF_SHAPES:
+        return run_cdf(name, reps)
     sys.path.insert(0, ROOT)
     import torch
     from bayesflow_nddms_amd import _lib, engine
@@ -125,6 +208,7 @@ def run_one(name, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only")
+    ap.add_argument("--cdf", action="store_true", help="the shapes of nddm_wiener_cdf instead of the log-likelihood's")
     ap.add_argument("--json")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--timeout", type=int, default=300)
@@ -135,15 +219,16 @@ def main():
     sys.path.insert(0, ROOT)
     from bayesflow_nddms_amd import build
     out = {"tool": "tools/wiener_rate.py", "library_source_hash": build.source_hash(), "shapes": {}}
-    for name in SHAPES:
+    for name in (CDF_SHAPES if a.cdf else SHAPES):
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--only", name, "--reps", str(a.reps)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             sys.exit(f"{name}: exit status {r.returncode}; nothing further is started")
         out["shapes"][name] = json.loads(r.stdout.strip().splitlines()[-1])
-    tc = out["shapes"]["torch_composed"]["evals_per_s"]
-    for name in ("broadcast_sums", "broadcast_ans", "paired_sums"):
+    yard = "cdf_torch_composed" if a.cdf else "torch_composed"
+    tc = out["shapes"][yard]["evals_per_s"]
+    for name in (CDF_SHAPES[:-1] if a.cdf else ("broadcast_sums", "broadcast_ans", "paired_sums")):
         out["shapes"][name]["x_torch_composed"] = out["shapes"][name]["evals_per_s"] / tc
     line = json.dumps(out)
     print(line)
