@@ -7,6 +7,7 @@ from .build import SO_PATH
 
 NDDM_OK, NDDM_ERR_NULL, NDDM_ERR_SHAPE, NDDM_ERR_PARAM, NDDM_ERR_HIP, NDDM_ERR_NO_DEVICE = range(6)
 GAUSS_EXACT, GAUSS_FAST, BRIDGE, GAUSS_PACKED, STATE_F64 = 0, 1, 2, 4, 8
+QUANTILE_CONDITIONAL = 1             # nddm_wiener_quantile's flag (a namespace of its own)
 ABI_VERSION = 4
 
 _lib = None
@@ -38,6 +39,7 @@ def _declare(L):
     L.nddm_simulratcliff.argtypes = [fp, c.c_int64, c.c_int32, c.c_uint64, c.c_uint64, c.c_uint32, c.c_float, c.c_int32, fp, fp, fp, vp]
     L.nddm_wiener_log_likelihood.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_uint32, fp, fp, vp]
     L.nddm_wiener_cdf.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_uint32, fp, fp, vp]
+    L.nddm_wiener_quantile.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_uint32, fp, vp]
     L.nddm_simulate.argtypes = [c.c_int32, fp, fp] + common + [c.c_float, c.c_int32, fp, fp, fp, vp]
     L.nddm_simulate_indirect.argtypes = [c.c_int32, fp, fp] + common[:-1] + [fp, c.c_uint32, c.c_float, c.c_int32, fp, fp, fp, vp]
     L.nddm_simulate_codes.argtypes = [c.c_int32, fp] + common[:-1] + [fp, c.c_uint32, fp, fp, fp, vp]
@@ -65,7 +67,7 @@ EXPORTS = [
     "nddm_release_graph_memory", "nddm_debug_set_slot_limit", "nddm_debug_last_launch",
     "nddm_simulate_indirect", "nddm_draw_prior_indirect", "nddm_source_hash", "nddm_simulate_codes", "nddm_decode_codes",
     "nddm_graph_arena_create", "nddm_graph_arena_bind", "nddm_graph_arena_info", "nddm_graph_arena_release", "nddm_build_info",
-    "nddm_simulratcliff", "nddm_wiener_log_likelihood", "nddm_wiener_cdf",
+    "nddm_simulratcliff", "nddm_wiener_log_likelihood", "nddm_wiener_cdf", "nddm_wiener_quantile",
 ]
 
 

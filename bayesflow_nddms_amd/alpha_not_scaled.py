@@ -130,3 +130,14 @@ def cdf(params, y):
     if R % D:
         raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
     return engine.wiener_cdf(engine.ALPHA_NOT_SCALED, p, d, draws_per_dataset=R // D, want_p_upper=False)["cdf"]
+
+
+def quantile(params, probs=(.1, .3, .5, .7, .9)):
+    """Response-time quantiles of each boundary's own responses under params, one launch (engine.wiener_quantile, conditional): params
+    [R, 6] (or [6]), probs 1-D -> float32 [R, 2, Q] on the device, [:, 0] the lower boundary and [:, 1] the upper one: the predicted
+    side of a quantile-probability plot, beside cdf."""
+    p = params if hasattr(params, "is_cuda") else np.asarray(params, dtype=np.float64).reshape(-1, 6)
+    pr = np.asarray(probs, dtype=np.float64).reshape(-1)
+    R, Q = (p.shape[0] if p.ndim == 2 else 1), pr.shape[0]
+    req = np.stack([np.concatenate([pr, pr]), np.concatenate([-np.ones(Q), np.ones(Q)])], -1)[None]
+    return engine.wiener_quantile(engine.ALPHA_NOT_SCALED, p, req, draws_per_dataset=max(R, 1), conditional=True)["quantile"].reshape(R, 2, Q)

@@ -33,7 +33,7 @@
 // The path is VALU/transcendental-bound: 8 B are written per trial for ~246 Gaussian draws.
 //
 // This translation unit: nddm_rng.h (random stream) -> nddm_sim.h (sim_kernel) -> nddm_prepass.h (pre-pass, combine, prior)
-// -> nddm_ratcliff.h (the exact first-passage sampler) -> nddm_wiener.h (the Wiener first-passage log-likelihood) -> nddm_wiener_cdf.h (its distribution function)
+// -> nddm_ratcliff.h (the exact first-passage sampler) -> nddm_wiener.h (the Wiener first-passage log-likelihood) -> nddm_wiener_cdf.h (its distribution function) -> nddm_wiener_quantile.h (its quantile function)
 // -> below: the host side (launch slots, sizing, dispatch) and the extern "C" entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -52,6 +52,7 @@
 #include "nddm_sim.h"
 #include "nddm_wiener.h"
 #include "nddm_wiener_cdf.h"
+#include "nddm_wiener_quantile.h"
 
 namespace nddm {
 
@@ -1107,6 +1108,51 @@ int nddm_wiener_cdf(int32_t model, const float *params, int64_t R, int64_t draws
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener cdf kernel launch failed: %s", hipGetErrorString(e));
+    return NDDM_OK;
+}
+
+/* the Wiener first-passage quantile function (RWiener / HDDM qwiener), the inverse of nddm_wiener_cdf: csrc/nddm_wiener_quantile.h.  The
+ * argument checks, their order and their status codes are nddm_wiener_cdf's.  One kernel launch, no scratch memory: capturable like a
+ * plain kernel. */
+int nddm_wiener_quantile(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *probs, int32_t n,
+                         uint32_t flags, float *out_q, void *stream)
+{
+    using namespace nddm;
+    g_err[0] = 0;
+    if (model != NDDM_BASIC_DDM_DC && model != NDDM_ALPHA_NOT_SCALED) {
+        char m[16];
+        snprintf(m, sizeof m, "%d", (int)model);
+        return fail(NDDM_ERR_PARAM, "nddm_wiener_quantile: model %s has no closed-form distribution function here (NDDM_BASIC_DDM_DC and "
+                                    "NDDM_ALPHA_NOT_SCALED only)", m);
+    }
+    if ((flags & ~NDDM_QUANTILE_CONDITIONAL) != 0u)
+        return fail(NDDM_ERR_PARAM, "nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL%s");
+    if (R < 0 || n <= 0 || draws_per_dataset <= 0 || R % draws_per_dataset != 0)
+        return fail(NDDM_ERR_SHAPE, "R >= 0, n > 0 and draws_per_dataset > 0 dividing R are required%s");
+    if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
+    if (R == 0) return NDDM_OK;
+    if (!params || !probs) return fail(NDDM_ERR_NULL, "params or probs is NULL%s");
+    if (!out_q) return fail(NDDM_ERR_NULL, "no output buffer given%s");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = check_stream(st)) return rc;
+    WienerQuantileArgs A;
+    A.params = params; A.probs = probs; A.out_q = out_q;
+    A.R = R; A.S = draws_per_dataset; A.N = n; A.P = nddm_model_nparams(model); A.flags = flags;
+    // the layouts of nddm_wiener_cdf; the values do not depend on the choice (nddm_wiener_quantile.h)
+    const bool staged = draws_per_dataset >= WIENER_ROWS;
+    A.chunks = (draws_per_dataset + WIENER_ROWS - 1) / WIENER_ROWS;
+    const long long blocks = staged ? (R / draws_per_dataset) * A.chunks : (R + WIENER_ROWS - 1) / WIENER_ROWS;
+    if (blocks >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / 16 must be < 2^31)%s");
+    const dim3 grid((unsigned)blocks), block(256);
+    if (model == NDDM_BASIC_DDM_DC) {
+        if (staged) hipLaunchKernelGGL((wiener_quantile_kernel<NDDM_BASIC_DDM_DC, true>), grid, block, 0, st, A);
+        else hipLaunchKernelGGL((wiener_quantile_kernel<NDDM_BASIC_DDM_DC, false>), grid, block, 0, st, A);
+    } else {
+        if (staged) hipLaunchKernelGGL((wiener_quantile_kernel<NDDM_ALPHA_NOT_SCALED, true>), grid, block, 0, st, A);
+        else hipLaunchKernelGGL((wiener_quantile_kernel<NDDM_ALPHA_NOT_SCALED, false>), grid, block, 0, st, A);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener quantile kernel launch failed: %s", hipGetErrorString(e));
     return NDDM_OK;
 }
 

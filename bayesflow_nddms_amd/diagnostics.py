@@ -150,3 +150,45 @@ def ks_analytic(trials, params, model):
     dist = torch.maximum((i / n - gs).abs(), ((i - 1.0) / n - gs).abs())
     ks = dist.max(dim=1).values
     return torch.where(torch.isnan(g).any(dim=1), torch.full_like(ks, float("nan")), ks)
+
+
+def quantile_probability(sim_data, params, model, probs=(.1, .3, .5, .7, .9)):
+    """The numbers of a quantile-probability plot, on the device: sim_data [D, N, 2] in the simulator's format (model =
+    engine.BASIC_DDM_DC: (rt, choice); engine.ALPHA_NOT_SCALED: (y, acc)), params [D, S, P] (S parameter rows per data set, posterior draws
+    for instance) -> a dict of device tensors
+        'observed'          float32 [D, 2, Q]     empirical response-time quantiles (linear interpolation of the order statistics) of the
+                                                  lower ([:, 0]) and upper ([:, 1]) boundary's responses; NaN for a boundary with fewer than Q
+        'predicted'         float32 [D, S, 2, Q]  the exact law's quantiles of each boundary's own responses (engine.wiener_quantile, one launch)
+        'p_upper_observed'  float32 [D]           the share of upper-boundary responses among the responses (timeouts left out)
+        'p_upper_predicted' float32 [D, S]        P(upper boundary) (engine.wiener_cdf)
+    No host synchronisation: a sort along the trial axis and two kernel launches."""
+    from . import engine
+    torch = engine.require_device()
+    D, S, P = (int(x) for x in params.shape)
+    flat = params.reshape(D * S, P) if hasattr(params, "is_cuda") else np.asarray(params, dtype=np.float64).reshape(D * S, P)
+    pr = np.asarray(probs, dtype=np.float64).reshape(-1)
+    Q = pr.shape[0]
+    req = np.stack([np.concatenate([pr, pr]), np.concatenate([-np.ones(Q), np.ones(Q)])], -1)[None]
+    pred = engine.wiener_quantile(model, flat, req, draws_per_dataset=D * S, conditional=True)["quantile"].reshape(D, S, 2, Q)
+    dev = pred.device
+    t = sim_data if hasattr(sim_data, "is_cuda") else torch.as_tensor(np.asarray(sim_data, dtype=np.float32), device=dev)
+    if int(t.shape[0]) != D:
+        raise ValueError(f"params hold {D} data sets but sim_data holds {int(t.shape[0])}")
+    p_up = engine.wiener_cdf(model, flat, t, draws_per_dataset=S, want_cdf=False)["p_upper"].reshape(D, S)
+    rt = t[..., 0] if model == engine.BASIC_DDM_DC else t[..., 0].abs()
+    side = t[..., 1] if model == engine.BASIC_DDM_DC else t[..., 0]
+    pq = torch.as_tensor(pr, dtype=torch.float64, device=dev)[None, :]
+    obs, counts = [], []
+    for mask in (side < 0, side > 0):
+        n = mask.sum(dim=1)
+        srt = torch.sort(torch.where(mask, rt, torch.full_like(rt, float("inf"))), dim=1).values.double()
+        pos = pq * (n.clamp(min=1) - 1)[:, None].double()
+        lo = pos.floor().long()
+        hi = torch.minimum(lo + 1, (n.clamp(min=1) - 1)[:, None])
+        a, b = torch.gather(srt, 1, lo), torch.gather(srt, 1, hi)
+        val = a + (b - a) * (pos - lo.double())
+        obs.append(torch.where((n >= Q)[:, None], val, torch.full_like(val, float("nan"))).float())
+        counts.append(n)
+    n_lo, n_up = counts
+    return {"observed": torch.stack(obs, 1), "predicted": pred, "p_upper_observed": (n_up.double() / (n_lo + n_up).double()).float(),
+            "p_upper_predicted": p_up}

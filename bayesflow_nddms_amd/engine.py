@@ -332,10 +332,11 @@ def _wiener_check_params(model, p_np):
         raise ValueError("tau and Eta must be >= 0")
 
 
-def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs):
-    """The front end wiener_log_likelihood and wiener_cdf share: host inputs are refused here (ValueError), before any device work; a
-    device tensor's shape is checked where it is cast, after the split.  -> (S, params' and data's row descriptions, the host arrays or
-    None, R).  `what`: the quantity the model would have to have a closed form of; `outputs`: the caller's two output switches by name."""
+def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs, requests=False):
+    """The front end wiener_log_likelihood, wiener_cdf and wiener_quantile share: host inputs are refused here (ValueError), before any
+    device work; a device tensor's shape is checked where it is cast, after the split.  -> (S, params' and data's row descriptions, the
+    host arrays or None, R).  `what`: the quantity the model would have to have a closed form of; `outputs`: the caller's output
+    switches by name; `requests`: `data` holds wiener_quantile's (p, boundary code) pairs instead of trials."""
     if model not in (BASIC_DDM_DC, ALPHA_NOT_SCALED):
         raise ValueError(f"model {model} has no closed-form {what} here (BASIC_DDM_DC and ALPHA_NOT_SCALED only)")
     if not any(outputs.values()):
@@ -344,17 +345,23 @@ def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs):
     if S <= 0:
         raise ValueError("draws_per_dataset must be > 0")
     p_rows = (2, NPARAMS[model], f"params must have shape [R, {NPARAMS[model]}]")
-    d_rows = (3, 2, "data must have shape [D, n_trials, 2]")
+    d_rows = (3, 2, "probs must have shape [D, n, 2]" if requests else "data must have shape [D, n_trials, 2]")
     p_np = _host_rows(params, *p_rows)
     if p_np is not None:
         _wiener_check_params(model, p_np)
     d_np = _host_rows(data, *d_rows)
-    if d_np is not None and model == BASIC_DDM_DC and not np.all(np.isin(d_np[..., 1], (-1.0, 0.0, 1.0))):
+    if d_np is not None and requests:
+        if not np.all(np.isin(d_np[..., 1], (-1.0, 0.0, 1.0))):
+            raise ValueError("probs are (p, boundary code) with code in {1, -1, 0}")
+        if not np.all((d_np[..., 0] >= 0) & (d_np[..., 0] <= 1)):
+            raise ValueError("p must lie in [0, 1]")
+    elif d_np is not None and model == BASIC_DDM_DC and not np.all(np.isin(d_np[..., 1], (-1.0, 0.0, 1.0))):
         raise ValueError("basic_ddm_dc data are (rt, choice) with choice in {1, -1, 0}")
     R = p_np.shape[0] if p_np is not None else (1 if params.ndim == 1 else int(params.shape[0]))
     D = d_np.shape[0] if d_np is not None else (1 if data.ndim == 2 else int(data.shape[0]))
     if R != D * S:
-        raise ValueError(f"params has {R} rows but data holds {D} data sets x draws_per_dataset {S}")
+        raise ValueError(f"params has {R} rows but {'probs' if requests else 'data'} holds {D} {'request' if requests else 'data'} sets x "
+                         f"draws_per_dataset {S}")
     return S, p_rows, d_rows, p_np, d_np, R
 
 
@@ -421,6 +428,35 @@ def wiener_cdf(model, params, data, draws_per_dataset=1, want_cdf=True, want_p_u
     if out_p is not None:
         res["p_upper"] = out_p
     return res
+
+
+def wiener_quantile(model, params, probs, draws_per_dataset=1, conditional=False, device=None):
+    """Quantile function of the Wiener first-passage law (include/nddm.h: nddm_wiener_quantile), one kernel launch: RWiener / HDDM
+    qwiener, the inverse of wiener_cdf, whose model, params and draws_per_dataset these are.
+
+    probs: [D, n, 2] (or [n, 2]) = (p, boundary code) -- code 1 the upper boundary, -1 the lower one, 0 either boundary; R = D *
+    draws_per_dataset, row r answers request set r // draws_per_dataset.  conditional=False: p is DEFECTIVE, the response time rt with
+    P(T <= rt - tau, boundary) = p (NaN for a p beyond the boundary's probability, +inf at it); conditional=True: p is the share of that
+    boundary's responses, P(T <= rt - tau, boundary) = p P(boundary) (+inf at p = 1).  p = 0 gives tau.
+    Returns {'quantile': float32 [R, n]} on the device.  Host arrays are shape- and range-checked (ValueError: code in {1, -1, 0}, p in
+    [0, 1]); device tensors go to the kernel as they are, where an invalid row, a NaN or a negative p give NaN."""
+    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, probs, draws_per_dataset, "distribution function",
+                                                           {"quantile": True}, requests=True)
+    torch = require_device()
+    L = _lib.lib()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        p_dev = _device_rows(params, p_np, dev, *p_rows)
+        d_dev = _device_rows(probs, d_np, dev, *d_rows)
+        N = int(d_dev.shape[1])
+        out = torch.empty((R, N), dtype=torch.float32, device=dev)
+        if R > 0:
+            st = torch.cuda.current_stream(dev)
+            _lib.check(L.nddm_wiener_quantile(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, _lib.QUANTILE_CONDITIONAL if conditional else 0,
+                                              _ptr(out), st.cuda_stream))
+            p_dev.record_stream(st)
+            d_dev.record_stream(st)
+    return {"quantile": out}
 
 
 def decode_codes(model, codes, params, dt, out_trials=None):

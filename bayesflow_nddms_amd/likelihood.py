@@ -4,6 +4,8 @@
     dwiener_logpdf(y, alpha, tau, beta, delta)                  JAGS dwiener (basic_ddm_dc_pyjags.py:129-133, alpha_not_scaled.py:170-176)
     diffusion_lpdf(Y, boundary, ter, bias, drift, dc)           the Stan function of basic_ddm_dc_pystan2.py:119-131
     pwiener(q, alpha, tau, beta, delta)                         RWiener / HDDM pwiener, dwiener's distribution function (nddm_wiener_cdf)
+    qwiener(p, alpha, tau, beta, delta, resp)                   RWiener / HDDM qwiener, pwiener's inverse (nddm_wiener_quantile)
+    wiener_rt_quantiles(probs, alpha, tau, beta, delta, ...)    the response-time quantiles of each boundary's own responses
     wiener_choice_prob(alpha, beta, delta, eta, varsigma)       P(upper boundary), drift variability integrated out
 
 Both take numpy arrays, scalars or device tensors, broadcast them against each other (numpy rules), score every element in ONE kernel
@@ -106,3 +108,51 @@ def wiener_choice_prob(alpha, beta, delta, eta=0.0, varsigma=1.0, device=None):
         return torch.empty(shape, dtype=torch.float32, device=dev)
     data = torch.zeros((p.shape[0], 1, 2), dtype=torch.float32, device=dev)
     return engine.wiener_cdf(engine.ALPHA_NOT_SCALED, p, data, want_cdf=False, device=dev)["p_upper"].reshape(shape)
+
+
+_RESP_CODE = {"upper": 1.0, "lower": -1.0, "both": 0.0}
+
+
+def qwiener(p, alpha, tau, beta, delta, resp="upper", device=None):
+    """RWiener / HDDM `qwiener(p, alpha, tau, beta, delta, resp)`: the inverse of pwiener, the response time q with P(RT <= q, the boundary
+    `resp` names) = p -- resp "upper", "lower" or "both" (either boundary) -- in units of a diffusion coefficient of 1.  p is DEFECTIVE as
+    pwiener's values are: beyond the boundary's probability there is no such time and the result is NaN (+inf at it, tau at p = 0).
+    Broadcasts exactly as pwiener does, one kernel launch; returns a float32 device tensor of the broadcast shape (NaN for invalid
+    parameters)."""
+    if resp not in _RESP_CODE:
+        raise ValueError(f"resp must be one of {tuple(_RESP_CODE)}, got {resp!r}")
+    torch = engine.require_device()
+    dev = engine._device(device)
+    rows, data, shape = _basic_rows(p, delta, alpha, beta, tau, 1.0, dev)
+    if rows.shape[0] == 0 or data.shape[1] == 0:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    # _basic_rows split p into (|p|, sign): put the sign back (a negative p is NaN in the kernel) and name the boundary
+    req = torch.stack([data[..., 0] * data[..., 1], torch.full_like(data[..., 1], _RESP_CODE[resp])], -1).contiguous()
+    return engine.wiener_quantile(engine.BASIC_DDM_DC, rows, req, device=dev)["quantile"].reshape(shape)
+
+
+def _boundary_requests(probs, dev):
+    """A shared 1-D `probs` as the request set [1, 2Q, 2] of both boundaries: Q on the lower one (code -1), then Q on the upper one."""
+    torch = engine.require_device()
+    pr = _dev(probs, dev).reshape(-1)
+    code = torch.cat([torch.full_like(pr, -1.0), torch.full_like(pr, 1.0)])
+    return torch.stack([torch.cat([pr, pr]), code], -1)[None].contiguous(), int(pr.shape[0])
+
+
+def wiener_rt_quantiles(probs, alpha, tau, beta, delta, eta=0.0, varsigma=1.0, device=None):
+    """Response-time quantiles of each boundary's OWN responses (conditional on the boundary: what a quantile-probability plot and the
+    chi-square / G^2 quantile fits use): probs 1-D, shared; the parameters broadcast against each other (drift ~ N(delta, eta^2),
+    diffusion coefficient varsigma) -> float32 device tensor [..., 2, Q], [..., 0, :] the lower boundary and [..., 1, :] the upper one.
+    One launch, the request set shared by every row.  No clipping of the drift: |delta| > 5 is rescaled as wiener_choice_prob does."""
+    torch = engine.require_device()
+    dev = engine._device(device)
+    cols = [_dev(c, dev) for c in (delta, alpha, beta, tau, eta, varsigma)]
+    k = 5.0 / cols[0].abs().clamp(min=5.0)
+    cols = [cols[0] * k, cols[1] * k, cols[2], cols[3], cols[4] * k, cols[5] * k]
+    shape = tuple(torch.broadcast_shapes(*(c.shape for c in cols)))
+    p = torch.stack([c.expand(shape) for c in cols], -1).reshape(-1, 6).contiguous()
+    req, Q = _boundary_requests(probs, dev)
+    if p.shape[0] == 0 or Q == 0:
+        return torch.empty(shape + (2, Q), dtype=torch.float32, device=dev)
+    out = engine.wiener_quantile(engine.ALPHA_NOT_SCALED, p, req, draws_per_dataset=p.shape[0], conditional=True, device=dev)["quantile"]
+    return out.reshape(shape + (2, Q))

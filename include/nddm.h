@@ -69,6 +69,7 @@ extern "C" {
 /* 4: NDDM_STATE_F64 (flag 8), nddm_build_info, nddm_simulratcliff.  The random stream and every ABI-3 entry point are unchanged. */
 /* 4 (additive): nddm_wiener_log_likelihood.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_cdf.  No existing entry point changes. */
+/* 4 (additive): nddm_wiener_quantile. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -278,6 +279,27 @@ int nddm_wiener_log_likelihood(int32_t model, const float *params, int64_t R, in
 int nddm_wiener_cdf(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data, int32_t n_trials,
                     uint32_t flags /* 0, reserved */, float *out_cdf /* [R, n_trials] or NULL */,
                     float *out_p_upper /* [R] or NULL; not both NULL */, void *stream);
+
+/* The quantile function of the same first-passage law (RWiener / HDDM qwiener, the inverse of nddm_wiener_cdf): the response time by
+ * which a given share of the responses at a boundary has happened -- quantile-probability plots, posterior-predictive quantile checks,
+ * chi-square and G^2 quantile fitting.  (ABI 4, additive)
+ *   model, params, draws_per_dataset: exactly as nddm_wiener_cdf takes them; row r answers request set r / draws_per_dataset
+ *   probs              device f32 [D, n, 2] = (p, boundary code): code > 0 the upper boundary, code < 0 the lower one, code == 0 either
+ *                      boundary (G = F_lower + F_upper, limit 1), for both models
+ *   flags              0: p is DEFECTIVE, G(t) = p (p beyond the boundary's probability gives NaN, p equal to it +inf);
+ *                      NDDM_QUANTILE_CONDITIONAL: p is the share of that boundary's responses, G(t) = p P(boundary) (p > 1 gives NaN,
+ *                      p == 1 +inf, P(boundary) == 0 NaN); any other bit: NDDM_ERR_PARAM
+ *   out_q              device f32 [R, n]: rt = tau + t with G(t) = target; p == 0 gives tau; p NaN, p < 0 or a NaN code give NaN; a target
+ *                      the float32 G does not reach gives +inf
+ * nddm_wiener_cdf at the returned time is within 2e-5 of the target (measured: DESIGN.md section 13).  A value depends on (row, p, code)
+ * alone: the same bits whatever the layout, launch, stream or capture.  Invalid rows give NaN, their neighbours unaffected.  The solver
+ * is bracketed and its trip count is a compile-time constant.  Error checks, their order and their status codes are nddm_wiener_cdf's
+ * (NDDM_ERR_NULL for a NULL params / probs / out_q); R = 0 is NDDM_OK.  No scratch memory: a call made while `stream` is capturing is
+ * one kernel node.  The solver: csrc/nddm_wiener_quantile.h, DESIGN.md section 13. */
+#define NDDM_QUANTILE_CONDITIONAL 1u
+int nddm_wiener_quantile(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset,
+                         const float *probs /* [D, n, 2] = (p, boundary code) */, int32_t n,
+                         uint32_t flags /* 0 or NDDM_QUANTILE_CONDITIONAL */, float *out_q /* [R, n] */, void *stream);
 
 /* replaces the per-trial loop over diffusion_trial(drift, bound_trial, beta, ter, dc),
  * imputation_from_stahl_not_scaled.py:120-148, :207-213.  bounds: device f32 [B, n_trials].

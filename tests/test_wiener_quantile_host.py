@@ -1,0 +1,151 @@
+"""CPU tests of the Wiener quantile function (nddm_wiener_quantile): the symbol and its signature, the C ABI's argument checks (made
+before any HIP call, so they run without a device), the Python adapter's refusals of bad host input, and the kernel's compiler
+resources (no scratch, no spills)."""
+import ctypes
+import os
+import shutil
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+HAVE_HIPCC = shutil.which("hipcc") is not None or os.path.exists("/opt/rocm/bin/hipcc")
+
+
+def test_symbol_is_exported_with_its_signature_and_the_abi_is_still_4():
+    from bayesflow_nddms_amd import _lib
+    L = _lib.lib()
+    assert "nddm_wiener_quantile" in _lib.EXPORTS and hasattr(L, "nddm_wiener_quantile")
+    assert L.nddm_abi_version() == _lib.ABI_VERSION == 4
+    c = ctypes
+    f = L.nddm_wiener_quantile
+    # (model, params, R, draws_per_dataset, probs, n, flags, out_q, stream)
+    assert f.argtypes == [c.c_int32, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_int32, c.c_uint32, c.c_void_p, c.c_void_p]
+    assert f.restype == c.c_int
+    assert _lib.QUANTILE_CONDITIONAL == 1
+    hdr = open(os.path.join(ROOT, "include", "nddm.h")).read()
+    assert "/* 4 (additive): nddm_wiener_quantile. */" in hdr and "#define NDDM_ABI_VERSION 4" in hdr
+    assert "#define NDDM_QUANTILE_CONDITIONAL 1u" in hdr
+    from bayesflow_nddms_amd import build
+    assert any(p.endswith("nddm_wiener_quantile.h") for p in build.HEADERS)          # part of the source hash
+
+
+def test_status_codes_and_their_order_are_those_of_the_distribution_function():
+    from bayesflow_nddms_amd import _lib
+    L = _lib.lib()
+    d = ctypes.c_void_p(16)
+    q = L.nddm_wiener_quantile
+    cdf = lambda model, p, R, S, data, n, flags, out: L.nddm_wiener_cdf(model, p, R, S, data, n, flags, out, None, None)
+    # every case the distribution function's flags allow: the same status from both entries
+    for args in ((1, d, 4, 1, d, 10, 0, d), (7, d, 4, 1, d, 10, 0, d), (0, None, 4, 1, d, 10, 0, d), (3, d, 4, 1, None, 10, 0, d),
+                 (0, d, 4, 1, d, 10, 0, None), (0, d, -1, 1, d, 10, 0, d), (0, d, 4, 1, d, 0, 0, d), (0, d, 4, 0, d, 10, 0, d),
+                 (0, d, 4, 3, d, 10, 0, d), (0, d, 0, 1, d, 10, 0, d), (3, d, 1 << 36, 1, d, 10, 0, d),
+                 (7, None, -1, 0, None, 0, 0, None), (0, None, -1, 0, None, 0, 0, None), (0, None, 4, 1, None, 10, 0, None)):
+        want = cdf(*args)
+        assert q(*args, None) == want, args
+    assert q(1, d, 4, 1, d, 10, 0, d, None) == _lib.NDDM_ERR_PARAM and b"model 1" in L.nddm_last_error()
+    assert q(0, None, 4, 1, d, 10, 0, d, None) == _lib.NDDM_ERR_NULL
+    assert q(0, d, 4, 1, None, 10, 0, d, None) == _lib.NDDM_ERR_NULL
+    assert q(0, d, 4, 1, d, 10, 0, None, None) == _lib.NDDM_ERR_NULL
+    assert q(0, d, 4, 3, d, 10, 0, d, None) == _lib.NDDM_ERR_SHAPE
+    assert q(0, d, 0, 1, d, 10, 0, d, None) == _lib.NDDM_OK and q(0, None, 0, 1, None, 10, 1, None, None) == _lib.NDDM_OK      # empty batch
+    # the flag: NDDM_QUANTILE_CONDITIONAL is known, every other bit is not
+    for flags in (2, 3, 4, 1 << 31, 0xFFFFFFFE):
+        assert q(0, d, 4, 1, d, 10, flags, d, None) == _lib.NDDM_ERR_PARAM and b"flags" in L.nddm_last_error(), flags
+    assert q(0, d, 0, 1, d, 10, 1, d, None) == _lib.NDDM_OK
+    # the order: model, flags, shape, then pointers
+    assert q(7, None, -1, 0, None, 0, 2, None, None) == _lib.NDDM_ERR_PARAM and b"model 7" in L.nddm_last_error()
+    assert q(0, None, -1, 0, None, 0, 2, None, None) == _lib.NDDM_ERR_PARAM and b"flags" in L.nddm_last_error()
+    assert q(0, None, -1, 0, None, 0, 1, None, None) == _lib.NDDM_ERR_SHAPE
+    assert q(0, None, 4, 1, None, 10, 1, None, None) == _lib.NDDM_ERR_NULL
+    import torch
+    if not torch.cuda.is_available():
+        assert q(0, d, 4, 2, d, 10, 1, d, None) in (_lib.NDDM_ERR_HIP, _lib.NDDM_ERR_NO_DEVICE)
+
+
+def test_python_adapter_refuses_bad_host_input():
+    from bayesflow_nddms_amd import alpha_not_scaled, basic_ddm_dc, diagnostics, engine
+    from bayesflow_nddms_amd.likelihood import qwiener, wiener_rt_quantiles
+    import bayesflow_nddms_amd as pkg
+    assert {"wiener_quantile", "qwiener", "wiener_rt_quantiles"} <= set(pkg.__all__)
+    assert callable(basic_ddm_dc.quantile) and callable(alpha_not_scaled.quantile) and callable(diagnostics.quantile_probability)
+    assert callable(wiener_rt_quantiles)
+    good = np.array([[1.0, 1.0, 0.5, 0.3, 1.0]])
+    probs = np.array([[[0.1, 1.0], [0.5, -1.0], [0.9, 0.0]]])
+    wq = engine.wiener_quantile
+    with pytest.raises(ValueError, match="closed-form"):
+        wq(engine.SINGLE_TRIAL, np.zeros((1, 8)), probs)
+    with pytest.raises(ValueError, match=r"\[R, 5\]"):
+        wq(engine.BASIC_DDM_DC, np.zeros((1, 6)), probs)
+    for col, val, msg in ((1, 0.0, "> 0"), (4, -1.0, "> 0"), (2, 1.0, r"\(0, 1\)"), (2, 0.0, r"\(0, 1\)"), (3, -0.1, ">= 0"), (0, np.nan, "finite")):
+        p = good.copy()
+        p[0, col] = val
+        with pytest.raises(ValueError, match=msg):
+            wq(engine.BASIC_DDM_DC, p, probs)
+    ans = np.array([[1.0, 1.0, 0.5, 0.3, 0.2, 1.0]])
+    with pytest.raises(ValueError, match="Eta"):
+        wq(engine.ALPHA_NOT_SCALED, np.array([[1.0, 1.0, 0.5, 0.3, -0.2, 1.0]]), probs)
+    # the code is in {1, -1, 0} for BOTH models, p in [0, 1] (a NaN is outside it)
+    for model, row in ((engine.BASIC_DDM_DC, good), (engine.ALPHA_NOT_SCALED, ans)):
+        for code in (0.5, 2.0, np.nan):
+            with pytest.raises(ValueError, match="code"):
+                wq(model, row, np.array([[[0.5, code]]]))
+        for p in (-0.1, 1.5, np.nan):
+            with pytest.raises(ValueError, match=r"\[0, 1\]"):
+                wq(model, row, np.array([[[p, 1.0]]]))
+    with pytest.raises(ValueError, match=r"\[D, n, 2\]"):
+        wq(engine.BASIC_DDM_DC, good, np.zeros((1, 3, 3)))
+    with pytest.raises(ValueError, match="request sets"):
+        wq(engine.BASIC_DDM_DC, np.repeat(good, 3, 0), np.repeat(probs, 2, 0))
+    with pytest.raises(ValueError, match="draws_per_dataset"):
+        wq(engine.BASIC_DDM_DC, good, probs, draws_per_dataset=0)
+    with pytest.raises(ValueError, match="resp"):
+        qwiener(0.3, 1.0, 0.3, 0.5, 0.0, resp="sideways")
+    # what the distribution function's front end accepts is unchanged: a choice outside {1, -1, 0} is refused for the basic model only
+    with pytest.raises(ValueError, match="choice"):
+        engine.wiener_cdf(engine.BASIC_DDM_DC, good, np.array([[[0.6, 0.5]]]))
+    with pytest.raises(ValueError, match=r"\[D, n_trials, 2\]"):
+        engine.wiener_cdf(engine.BASIC_DDM_DC, good, np.zeros((1, 3, 3)))
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc missing")
+def test_kernel_compiles_with_no_scratch_and_no_spills():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import resource_table as rt
+    rows = {rt.pretty(r["name"]): r for r in rt.collect()}
+    names = [f"wiener_quantile_kernel<{m}, {lay}>" for m in ("basic", "alpha_ns") for lay in ("broadcast", "paired")]
+    for name in names:
+        assert name in rows, (name, sorted(k for k in rows if "wiener" in k))
+        r = rows[name]
+        assert r.get("ScratchSize [bytes/lane]", 0) == 0, name
+        assert r.get("VGPRs Spill", 0) == 0 and r.get("SGPRs Spill", 0) == 0, name
+        assert r.get("LDS Size [bytes/block]", 0) <= 16 * 1024, name          # the request tile (8 KB) and the rows' constants
+
+
+@pytest.mark.skipif(shutil.which("g++") is None and shutil.which("c++") is None and shutil.which("clang++") is None, reason="no host C++ compiler")
+def test_solver_compiled_for_the_host_meets_its_trip_bound_and_the_residual_bar():
+    """tools/wiener_quantile_host.py: the header's own per-request code under AddressSanitizer and UndefinedBehaviorSanitizer, as a
+    stand-alone program, over the rows of the device's accuracy test.  Every kept request is answered with a finite time, in fewer
+    evaluations than WQUANT_MAX_EVALS = 48 (16 secant steps, then at most 31 bisections), about five on average, and the header's own
+    distribution function at the answer is within 2e-5 of the target."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import wiener_quantile_host as H
+    r = H.survey(sanitize=True)
+    cases = dict(r["cases"])
+    for name, c in cases.items():
+        print(name, c)
+    extreme, golden = cases.pop("extreme_rows_conditional"), cases.pop("golden_tables_defective")
+    assert len(cases) == 6
+    for name, c in cases.items():
+        assert c["finite"] == c["requests"] > 1000, name
+        assert c["evals_max"] <= 16 + 31 and c["evals_mean"] <= 8.0, name
+        assert c["max_abs_residual"] <= 2e-5, name
+        if name.endswith("_conditional"):                      # the device test's bars (ii) and (iii), on the host's arithmetic
+            assert c["max_abs_yardstick_minus_target"] <= 6e-5, name
+        if name.endswith("_defective"):
+            assert c["max_abs_yardstick_minus_target"] <= 4e-5, name
+    assert extreme["finite"] == extreme["requests"] == 1600 and extreme["nan"] == 0 and extreme["max_abs_residual"] <= 2e-5
+    assert extreme["evals_max"] <= 16 + 31
+    assert golden["max_rank_distance"] <= 20 and golden["control_min"] > 200

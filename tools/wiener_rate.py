@@ -15,8 +15,20 @@ With --cdf: nddm_wiener_cdf (csrc/nddm_wiener_cdf.h) instead, every shape writin
   cdf_broadcast_eta    the same for alpha_not_scaled with Eta in (0, 1.5)
   cdf_torch_composed   the eta = 0 formula of the kernel as PyTorch elementwise ops (torch.special.erfcx) on 100 000 rows x 300 trials
 
+With --quantile: nddm_wiener_quantile (csrc/nddm_wiener_quantile.h), the .1 / .3 / .5 / .7 / .9 quantiles of each boundary's own responses
+(conditional, Q = 5 per boundary: 10 requests per row), beside what a user did before it existed -- a 32-step bisection of
+engine.wiener_cdf from Python on the bit pattern of t (32 launches and one more for the limit P(boundary), on the paired layout: every row has its
+own times):
+  q_paired_eta0        basic_ddm_dc, 200 000 rows, each with its own request set
+  q_paired_eta         alpha_not_scaled with Eta in (0, 1.5)
+  q_broadcast_eta0     100 request sets x 2 000 draws, basic_ddm_dc
+  q_broadcast_eta      the same for alpha_not_scaled with Eta in (0, 1.5)
+  q_bisect_eta0        the composed bisection on q_paired_eta0's rows and requests
+  q_bisect_eta         the composed bisection on q_paired_eta's rows and requests
+Every kernel shape also reports the largest |wiener_cdf(q) - target| over its first 20 000 rows.
+
 Each shape runs in a child process of its own under `timeout` (a step that faults or hangs ends the tool; nothing further starts).
-Usage: python tools/wiener_rate.py [--cdf] [--json OUT] [--reps 10]        (one shape: --only NAME)
+Usage: python tools/wiener_rate.py [--cdf | --quantile] [--json OUT] [--reps 10]        (one shape: --only NAME)
 """
 import argparse
 import json
@@ -28,6 +40,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = ("paired_sums", "paired_trials", "broadcast_sums", "broadcast_ans", "torch_composed")
 CDF_SHAPES = ("cdf_paired_eta0", "cdf_paired_eta", "cdf_broadcast_eta0", "cdf_broadcast_eta", "cdf_torch_composed")
+Q_SHAPES = ("q_paired_eta0", "q_paired_eta", "q_broadcast_eta0", "q_broadcast_eta", "q_bisect_eta0", "q_bisect_eta")
+Q_PROBS = (.1, .3, .5, .7, .9)
 HBM_BPS = 8e12
 
 
@@ -153,9 +167,81 @@ def run_cdf(name, reps):
     print(json.dumps(res), flush=True)
 
 
+def _signed_data(torch, model, rt, code):
+    """Response times and boundary codes [R, n] as trials of the model's format [R, n, 2]."""
+    if model == 0:
+        return torch.stack([rt, code], -1).contiguous()
+    return torch.stack([rt * code, (code + 1) / 2], -1).contiguous()
+
+
+def bisect_quantile(torch, engine, model, p, req, steps=32):
+    """What a user does without the kernel: conditional quantiles by `steps` bisections of engine.wiener_cdf on the bit pattern of t
+    between 0 and 1e15 (positive floats order as their integers: it ends on adjacent floats).  p [R, P], req [R, n, 2] -> rt [R, n]."""
+    R, n = req.shape[0], req.shape[1]
+    code, tau = req[..., 1], p[:, 3:4]
+    inf = torch.full((R, n), float("inf"), device=p.device)
+    target = req[..., 0] * engine.wiener_cdf(model, p, _signed_data(torch, model, inf, code), want_p_upper=False)["cdf"]
+    lo = torch.zeros((R, n), dtype=torch.int32, device=p.device)
+    hi = torch.full((R, n), 1.0e15, dtype=torch.float32, device=p.device).view(torch.int32)
+    for _ in range(steps):
+        mid = lo + (hi - lo) // 2
+        F = engine.wiener_cdf(model, p, _signed_data(torch, model, tau + mid.view(torch.float32), code), want_p_upper=False)["cdf"]
+        below = F < target
+        lo, hi = torch.where(below, mid, lo), torch.where(below, hi, mid)
+    return tau + hi.view(torch.float32)
+
+
+def run_quantile(name, reps):
+    sys.path.insert(0, ROOT)
+    import torch
+    from bayesflow_nddms_amd import _lib, engine
+    L = _lib.lib()
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(7)
+    st = lambda: torch.cuda.current_stream().cuda_stream
+    ans = name.endswith("_eta")
+    Q = len(Q_PROBS)
+    n = 2 * Q
+    D, S = (100, 2_000) if "broadcast" in name else (200_000, 1)
+    R = D * S
+    b = _basic_params(torch, R, gen)
+    if ans:
+        eta = torch.rand(R, generator=gen, device="cuda") * 1.5
+        p, model = torch.stack([b[:, 0], b[:, 1], b[:, 2], b[:, 3], eta, b[:, 4]], 1).contiguous(), engine.ALPHA_NOT_SCALED
+    else:
+        p, model = b, 0
+    pr = torch.tensor(Q_PROBS + Q_PROBS, device="cuda")
+    code = torch.tensor([-1.0] * Q + [1.0] * Q, device="cuda")
+    req = torch.stack([pr, code], -1)[None].repeat(D, 1, 1).contiguous()
+    res = {}
+    if "bisect" in name:
+        fn = lambda: bisect_quantile(torch, engine, model, p, req)
+        k = engine.wiener_quantile(model, p[:20_000], req[:20_000], conditional=True)["quantile"]
+        d = (bisect_quantile(torch, engine, model, p[:20_000], req[:20_000]) - k).abs()
+        res["max_abs_rt_diff_vs_kernel_first_20000_rows"] = d[torch.isfinite(d)].max().item()
+    else:
+        out = torch.empty((R, n), dtype=torch.float32, device="cuda")
+        fn = lambda: _lib.check(L.nddm_wiener_quantile(model, p.data_ptr(), R, S, req.data_ptr(), n, _lib.QUANTILE_CONDITIONAL, out.data_ptr(), st()))
+        fn()
+        m = min(R, 20_000)
+        pm, qm = p[:m], out[:m]
+        cm = code[None].expand(m, n)
+        inf = torch.full((m, n), float("inf"), device="cuda")
+        lim = engine.wiener_cdf(model, pm, _signed_data(torch, model, inf, cm), want_p_upper=False)["cdf"]
+        F = engine.wiener_cdf(model, pm, _signed_data(torch, model, qm, cm), want_p_upper=False)["cdf"]
+        res["finite_fraction_first_rows"] = torch.isfinite(qm).float().mean().item()
+        res["max_abs_cdf_residual_first_rows"] = (F - pr[None] * lim)[torch.isfinite(qm)].abs().max().item()
+    evals = R * n
+    med, best = _time(torch, fn, reps)
+    res = {"shape": name, "requests": evals, "ms_median": round(med, 4), "ms_best": round(best, 4), "requests_per_s": evals / (med * 1e-3), **res}
+    print(json.dumps(res), flush=True)
+
+
 def run_one(name, reps):
     if name in CDF_SHAPES:
         return run_cdf(name, reps)
+    if name in Q_SHAPES:
+        return run_quantile(name, reps)
     sys.path.insert(0, ROOT)
     import torch
     from bayesflow_nddms_amd import _lib, engine
@@ -209,6 +295,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only")
     ap.add_argument("--cdf", action="store_true", help="the shapes of nddm_wiener_cdf instead of the log-likelihood's")
+    ap.add_argument("--quantile", action="store_true", help="the shapes of nddm_wiener_quantile, beside a composed bisection of wiener_cdf")
     ap.add_argument("--json")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--timeout", type=int, default=300)
@@ -219,17 +306,22 @@ def main():
     sys.path.insert(0, ROOT)
     from bayesflow_nddms_amd import build
     out = {"tool": "tools/wiener_rate.py", "library_source_hash": build.source_hash(), "shapes": {}}
-    for name in (CDF_SHAPES if a.cdf else SHAPES):
+    for name in (Q_SHAPES if a.quantile else CDF_SHAPES if a.cdf else SHAPES):
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--only", name, "--reps", str(a.reps)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             sys.exit(f"{name}: exit status {r.returncode}; nothing further is started")
         out["shapes"][name] = json.loads(r.stdout.strip().splitlines()[-1])
-    yard = "cdf_torch_composed" if a.cdf else "torch_composed"
-    tc = out["shapes"][yard]["evals_per_s"]
-    for name in (CDF_SHAPES[:-1] if a.cdf else ("broadcast_sums", "broadcast_ans", "paired_sums")):
-        out["shapes"][name]["x_torch_composed"] = out["shapes"][name]["evals_per_s"] / tc
+    if a.quantile:                              # each kernel shape against the composed bisection of the same model
+        for name in Q_SHAPES[:4]:
+            yard = out["shapes"]["q_bisect_eta" if name.endswith("_eta") else "q_bisect_eta0"]["requests_per_s"]
+            out["shapes"][name]["x_composed_bisection"] = out["shapes"][name]["requests_per_s"] / yard
+    else:
+        yard = "cdf_torch_composed" if a.cdf else "torch_composed"
+        tc = out["shapes"][yard]["evals_per_s"]
+        for name in (CDF_SHAPES[:-1] if a.cdf else ("broadcast_sums", "broadcast_ans", "paired_sums")):
+            out["shapes"][name]["x_torch_composed"] = out["shapes"][name]["evals_per_s"] / tc
     line = json.dumps(out)
     print(line)
     if a.json:
