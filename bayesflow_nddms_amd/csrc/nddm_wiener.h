@@ -22,9 +22,11 @@
 // Special values (the math, none an error): t <= 0 (an RT at or below tau) gives -inf; a row with a non-finite parameter, a <= 0,
 // s <= 0, beta outside (0, 1), tau < 0 or eta < 0 gives NaN for every trial and its sum, its neighbours unaffected.
 //   basic_ddm_dc (rt, choice): choice 0 is the Euler-Maruyama simulator's timeout at rt = max_steps dt + tau, RIGHT-CENSORED:
-//     log P(T > t) from the large-time survival series of both boundaries,
+//     log P(T > t) of both boundaries, in one of two forms selected per trial (wiener_log_survival): below u = WIENER_SURV_U the method
+//     of images in the position domain (twelve erfcx-scaled terms, the leading exponent taken out: it does not cancel however wide the
+//     boundary or strong the drift), at and above it the large-time survival series
 //     S(t) = sum_{sides} (pi / a'^2) e^{-a' v w} sum_k k sin(k pi w) e^{-lambda_k t} / lambda_k,  lambda_k = v'^2/2 + k^2 pi^2 / (2 a'^2),
-//     terms added until the next is below 2^-24 of the sum, at most 64 (a loop: timeouts are rare; t <= 0 gives log 1 = 0).
+//     terms added until the next is below 2^-24 of the sum, at most 64 (loops: timeouts are rare; t <= 0 gives log 1 = 0).
 //   alpha_not_scaled (y, acc): rt = |y|, upper iff y > 0; Nu clipped to +-5 as the generator does (pyhddmjagsutils.py:102-103);
 //     y == 0 (the Euler-Maruyama form's timeout) carries no time: NaN.  simulratcliff never writes one.
 //
@@ -74,6 +76,7 @@ struct WienerRow {
     float d0[2];                // eta'^2 a'^2 w^2 / 2 - a' nu w
     float s1, cpb;              // sin(pi beta), cos(pi beta) (the survival series' recurrence)
     float la;                   // log a'
+    float ap, vp;               // a', v' (the survival's small-time form)
     float valid;                // 1 or NaN
 };
 constexpr int WIENER_ROW_WORDS = sizeof(WienerRow) / sizeof(float);
@@ -98,6 +101,7 @@ __device__ __forceinline__ WienerRow wiener_row(const float *p)
     c.hn2 = 0.5f * (vp * vp);
     c.e2 = e2;
     c.la = la;
+    c.ap = ap; c.vp = vp;
     const float sb = sinpif(beta), cb = cospif(beta);
     c.s1 = sb; c.cpb = cb;
     const float lsin = logf(sb);
@@ -117,11 +121,82 @@ __device__ __forceinline__ WienerRow wiener_row(const float *p)
     return c;
 }
 
-// log P(T > t) of the η = 0 process (basic_ddm_dc's censored timeouts): the large-time survival series of both boundaries, with
-// e^{-lambda_1 t} and the larger side weight taken out; sin(k pi w) by the Chebyshev recurrence (sin(k pi (1 - beta)) = (-1)^(k+1) sin(k pi beta))
-__device__ __forceinline__ float wiener_log_survival(const WienerRow &c, float t)
+// log P(T > t) of the η = 0 process (basic_ddm_dc's censored timeouts), in one of two forms selected per trial by u = t / a'^2:
+// the method of images below WIENER_SURV_U, the large-time series at and above it.
+//
+// Small time, in the position domain: the density of the evidence at x in (0, a), started at x0 = a w, is
+// e^{v (x - x0) - v^2 t / 2} sum_n [phi_t(x - x0 - 2na) - phi_t(x + x0 - 2na)], and integrated over (0, a) every image at c gives
+//     I(c) = e^{v (c - x0)} P(N(c + v t, t) in (0, a)) = 1/2 e^{v (c - x0)} [erfc(p) - erfc(q)],
+// p the distance (in sqrt(2t)) of the drifted centre c + v t OUTSIDE the interval (negative inside) and q > |p| its distance from the far
+// end: a difference of two tail values on the SAME side, which does not cancel.  S = sum_n I(x0 + 2na) - I(-x0 + 2na), n = -1, 0, 1 (the
+// next images are below e^{-3 / (2u)} = 1e-11 of the leading one at u < 0.06).  Every product is e^{G - p^2} erfcx(p), and the leading
+// image's e^{-p0^2} = e^{-sigma} (p0 > 0: the drift has carried the mass past a boundary) is taken out of all of them, so log S =
+// -sigma + log(...) keeps its relative accuracy and its range however small S is; with the leading centre inside, sigma = 0.
+// The series cannot serve there: below u of about 0.04 its terms must cancel to e^{-w^2 / (2u)} of their size, which float32 does not
+// hold (NaN, or a positive log S, on the wide-boundary rows of the prior); from 0.04 up it is exact to float32, and the images in turn
+// would need more terms above u of about 0.1.
+constexpr float WIENER_SURV_U = 0.06f;          // images below, series at and above (both within the tests' bars on [0.04, 0.1])
+
+// log(erfcx(z) / s), z >= 0: erfcx(z) = s e^{P(s)}, s = 1 / (1 + z / 2), P the degree-9 Chebyshev fit of Numerical Recipes' erfcc
+// (relative error <= 1.2e-7 at every z).  No branch and one reciprocal; its exponent joins the term's own, so a product e^{g} erfcx(z) is
+// one exponential.  (The library's erfcxf is three branches and, inlined beside the series, cost the basic kernels two waves per SIMD.)
+__device__ __forceinline__ float wiener_log_erfcx_poly(float s)
 {
-    if (!(t > 0.0f)) return t == t ? 0.0f : t;
+    float P = 0.17087277f;
+    P = fmaf(P, s, -0.82215223f); P = fmaf(P, s, 1.48851587f); P = fmaf(P, s, -1.13520398f); P = fmaf(P, s, 0.27886807f);
+    P = fmaf(P, s, -0.18628806f); P = fmaf(P, s, 0.09678418f); P = fmaf(P, s, 0.37409196f); P = fmaf(P, s, 1.00002368f);
+    return fmaf(P, s, -1.26551223f);
+}
+
+// 1/2 e^{g} erfcx(z), z >= 0
+__device__ __forceinline__ float wiener_half_exp_erfcx(float g, float z)
+{
+    const float s = __builtin_amdgcn_rcpf(fmaf(0.5f, z, 1.0f));
+    return (0.5f * s) * __expf(fminf(g + wiener_log_erfcx_poly(s), 80.0f));
+}
+
+// (The four row constants are read behind an empty asm per trial: without it the compiler hoists the row-uniform products of this rare
+// branch out of the trial loop into vector registers that stay live through the density's code, and each basic kernel loses a wave per SIMD.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WIENER_PER_TRIAL(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
+#else
+#define WIENER_PER_TRIAL(a, b, c, d) ((void)0)
+#endif
+__device__ __forceinline__ float wiener_log_survival_small(const WienerRow &row, float t)
+{
+    float ap = row.ap, vp = row.vp, w0 = row.w[0], w1 = row.w[1];
+    WIENER_PER_TRIAL(ap, vp, w0, w1);
+    t = fmaxf(t, 1.0e-30f);                                             // (S is 1 long before; 1 / sqrt(2t) stays finite)
+    float rs = __builtin_amdgcn_rsqf(2.0f * t);
+    rs = rs * fmaf(-t * rs, rs, 1.5f);                                  // one Newton step: 1 / sqrt(2t) to the last bit or two
+    const float x0 = ap * w0, a2 = 2.0f * ap;
+    const float mL = fmaf(t, vp, x0);                                 // the leading image's drifted centre, and its distance beyond a
+    const float mU = fmaf(t, vp, -(ap * w1));
+    const float p0 = fmaxf(mU, -mL) * rs;
+    const float sigma = p0 > 0.0f ? p0 * p0 : 0.0f;
+    // image i = 2 (n + 1) + (negative ? 1 : 0), n = -1, 0, 1, at c = x0 + d: G = sigma + v d; dU, dL = its drifted centre's distance beyond a
+    // and below 0 in sqrt(2t) (dU + dL = -a / sqrt(2t) < 0: at most one is positive), p the larger and q minus the smaller.  Trip 2i is
+    // the p term, trip 2i + 1 the q term: a loop of twelve and not twelve inlined copies, so that it holds one term's registers
+    float acc = 0.0f;
+#pragma nounroll
+    for (int k = 0; k < 12; ++k) {
+        const int i = k >> 1;
+        const bool neg = i & 1, far = k & 1;
+        const float d = (float)((i >> 1) - 1) * a2 - (neg ? 2.0f * x0 : 0.0f);
+        const float G = fmaf(vp, d, sigma), dU = (mU + d) * rs, dL = -(mL + d) * rs;
+        const float p = fmaxf(dU, dL), z = far ? -fminf(dU, dL) : p;
+        const float h = wiener_half_exp_erfcx(fmaf(-z, z, G), fabsf(z));
+        const float term = far ? -h : (p >= 0.0f ? h : __expf(fminf(G, 80.0f)) - h);
+        acc = neg ? acc - term : acc + term;
+    }
+    // acc = S e^{sigma}; with the leading centre inside, sigma = 0 and its image's e^{G} is the 1 that S stays near
+    return fminf(0.693147180559945309f * __builtin_amdgcn_logf(fmaxf(acc, 1.17549435e-38f)) - sigma, 0.0f);
+}
+
+// Large time: the survival series of both boundaries, with e^{-lambda_1 t} and the larger side weight taken out; sin(k pi w) by the
+// Chebyshev recurrence (sin(k pi (1 - beta)) = (-1)^(k+1) sin(k pi beta)); terms added until the next is below 2^-24 of the sum.
+__device__ __forceinline__ float wiener_log_survival_large(const WienerRow &c, float t)
+{
     const float m = fmaxf(c.d0[0], c.d0[1]);
     const float wl = __expf(c.d0[0] - m), wu = __expf(c.d0[1] - m);
     const float kk = -c.lq;                                             // pi^2 / (2 a'^2)
@@ -140,6 +215,12 @@ __device__ __forceinline__ float wiener_log_survival(const WienerRow &c, float t
         sk_1 = sk; sk = sn;
     }
     return -lam1 * t + m + (1.14472988584940017f - 2.0f * c.la) + 0.693147180559945309f * __builtin_amdgcn_logf(sum);
+}
+
+__device__ __forceinline__ float wiener_log_survival(const WienerRow &c, float t)
+{
+    if (!(t > 0.0f)) return t == t ? 0.0f : t;
+    return t < (WIENER_SURV_U / WIENER_U_STAR) * c.tstar ? wiener_log_survival_small(c, t) : wiener_log_survival_large(c, t);
 }
 
 // log f of one trial on one boundary: a pure function of (row constants, rt, side)

@@ -2,12 +2,17 @@
 identities, the fixed-trip scheme the kernel evaluates is exact to 1e-9 against it, and the C ABI / Python adapter refuse bad input
 before any device work."""
 import ctypes
+import os
+import shutil
+import sys
 
 import numpy as np
 import pytest
 from scipy import integrate
 
+import wiener_cdf_ref as C
 import wiener_ref as W
+from conftest import GOLDEN, ROOT
 
 U_GRID = np.geomspace(1e-3, 50.0, 400)[:, None]
 W_GRID = np.linspace(0.01, 0.99, 99)[None, :]
@@ -58,6 +63,100 @@ def test_survival_is_one_minus_the_integrated_density(a, v, beta, s, t):
     F = integrate.quad(f, 0, t, epsrel=1e-12, limit=400)[0]
     assert abs(W.survival(t, a, v, beta, s) - (1.0 - F)) < 1e-9
     assert abs(W.log_survival(t, a, v, beta, s) - np.log(W.survival(t, a, v, beta, s))) < 1e-9
+
+
+def test_survival_yardsticks_agree_where_both_apply():
+    """log1p(-(F_lower + F_upper)) of the distribution function's yardstick against the survival series at the precision it needs, to
+    1e-9 where S >= 1e-3: on the four rows of the censoring defect's report and on rows of every set of the censoring tests, small u
+    and wide boundaries (a'|v'| up to 500) included -- where the float64 series of W.log_survival is off or not finite."""
+    pytest.importorskip("mpmath")
+    sets = C.censor_sets(n_prior=400, n_box=100, with_fixture=False)
+    rng = np.random.default_rng(3)
+    n_checked, widest, smallest_u, series_off = 0, 0.0, np.inf, 0
+    cases = [(C.REPORTED_ROWS, C._times(C.REPORTED_ROWS, C.REPORTED_T[:, None])[1])] + [(p32, t) for p32, _, t in sets.values()]
+    for k, (p32, t) in enumerate(cases):
+        a, v, beta, _, s, _ = C.row_columns(p32, True)
+        ref, ok = C.log_survival(t, a[:, None], v[:, None], beta[:, None], s[:, None])
+        # the series' cost grows with the precision it needs, a'|v'| + v'^2 t / 2 + 1 / (2u) digits-times-ln-10: points within 1200 of it
+        ap, vp = (a / s)[:, None], (v / s)[:, None]
+        cand = np.argwhere(ok & (ap * np.abs(vp) + vp * vp * t / 2 + ap * ap / (2 * t) <= 1200.0))
+        idx = cand
+        if k > 0:                                                       # the widest of them and a random few
+            order = np.argsort(-(ap * np.abs(vp))[cand[:, 0], 0], kind="stable")
+            idx = np.concatenate([cand[order[:8]], cand[rng.choice(len(cand), 8, replace=False)]])
+        for i, j in idx:
+            mp = W.mp_log_survival(t[i, j], a[i], v[i], beta[i], s[i])
+            assert abs(mp - ref[i, j]) <= 1e-9, (k, p32[i], t[i, j], mp, ref[i, j])
+            with np.errstate(all="ignore"):
+                old = W.log_survival(t[i, j], a[i], v[i], beta[i], s[i])
+            series_off += not abs(old - ref[i, j]) <= 1e-9
+            n_checked += 1
+            widest, smallest_u = max(widest, a[i] * abs(v[i]) / s[i] ** 2), min(smallest_u, t[i, j] * s[i] ** 2 / a[i] ** 2)
+    print(f"{n_checked} points, a'|v'| up to {widest:.0f}, u down to {smallest_u:.2g}; the float64 series alone is off on {series_off}")
+    assert n_checked >= 50 and widest > 100 and smallest_u < 0.01 and series_off > 0
+    assert np.max(np.abs(C.log_survival(C.REPORTED_T, *[x for x in C.row_columns(C.REPORTED_ROWS, True)[:3]], C.REPORTED_ROWS[:, 4].astype(np.float64))[0]
+                         - C.REPORTED_LOG_S)) < 1e-5
+
+
+def test_survival_fixture_is_the_yardsticks_output():
+    """tests/golden/wiener_survival.npz (tests/golden/make_wiener_survival.py): where S >= 1e-3 its values are C.log_survival's to 1e-12;
+    below, they lie under log 1e-3 and continue each row's non-increasing sequence; the report's four rows lead it."""
+    g = np.load(os.path.join(GOLDEN, "wiener_survival.npz"))
+    p32, rt, log_s, deep = g["params"], g["rt"], g["log_s"], g["mp"]
+    assert p32.dtype == rt.dtype == np.float32 and log_s.dtype == np.float64 and rt.shape == log_s.shape == deep.shape == (p32.shape[0], C.CENSOR_TIMES)
+    t = (rt - p32[:, 3:4]).astype(np.float32).astype(np.float64)
+    a, v, beta, _, s, _ = C.row_columns(p32, True)
+    ref, ok = C.log_survival(t, a[:, None], v[:, None], beta[:, None], s[:, None])
+    assert np.array_equal(ok, ~deep) and deep.sum() > 1000 and ok.sum() > 1000
+    assert np.max(np.abs(log_s - ref)[ok]) <= 1e-12
+    assert np.all(log_s[deep] < np.log(C.S_FLOOR)) and np.all(np.diff(log_s, axis=1) <= 0) and np.all(log_s <= 0)
+    assert np.array_equal(p32[:4], C.REPORTED_ROWS) and np.array_equal(rt[:4, -1], C.REPORTED_RT)
+    assert np.max(np.abs(log_s[:4, -1] - C.REPORTED_LOG_S)) < 1e-5
+    assert np.any((t / (a / s)[:, None] ** 2 < 0.06) & deep)              # deep tails in the small-time form's own range
+
+
+def test_prior_rows_cover_what_the_models_draw():
+    p32, rt32, up, t = C.prior_rows(20_000, basic=True)
+    assert p32.shape == (20_000, 5) and p32[:, 4].min() >= 0.05 and np.all(t > 0) and 0.45 < up.mean() < 0.55
+    assert (p32[:, 1] / p32[:, 4]).max() > 20 and (np.abs(p32[:, 0]) / p32[:, 4]).max() > 60             # (27.8 and 79.7)
+    p32, rt32, up, t = C.prior_rows(20_000, basic=False)
+    s, eta = p32[:, 5], p32[:, 4]
+    assert p32.shape == (20_000, 6) and np.all(t > 0)
+    assert s[:10_000].min() >= 0.8 and s[:10_000].max() <= 1.4 and eta[:10_000].max() <= 2.0           # the model's prior
+    assert s[10_000:].min() < 0.52 and s[10_000:].max() > 1.98 and eta[10_000:].max() > 2.9            # the box, Varsigma in [0.5, 2]
+    assert np.mean((s != 1.0) & (eta > 0)) > 0.8
+    # the same draw of u as accuracy_rows: log-uniform in [1e-3, 50] with a quarter in [0.3, 0.5]
+    u = t / (p32[:, 1].astype(np.float64) / s) ** 2
+    assert 0.24 < np.mean((u > 0.29) & (u < 0.51)) < 0.32 and u.min() < 2e-3 and u.max() > 40
+
+
+@pytest.mark.skipif(shutil.which("g++") is None and shutil.which("c++") is None and shutil.which("clang++") is None, reason="no host C++ compiler")
+def test_per_trial_code_compiled_for_the_host_meets_the_device_tests_bars():
+    """tools/wiener_host.py: wiener_row, wiener_trial (choice 0 included), wiener_cdf_side and wiener_cdf_trial of the headers as a
+    stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer, over the rows of tests/test_gpu_wiener_priors.py and at its
+    bars.  Density: |d log f| <= 1e-4 where |log f| <= 20, 1e-5 relative beyond; F and P(upper): 2e-5.  Censored: never NaN, never above
+    0, non-increasing along each row's 16 times; 2e-5 + 1e-5 |ref| where S >= 1e-3, 1e-3 |ref| below (the fixture); 1 - S through the
+    distribution function at 2e-5.  With the large-time series alone (before the small-time form) this test fails on the report's four
+    rows: NaN, +9.3, +15.7 and -0.16 for log S = -0.000000, -2.507289, -0.009398 and -6.160853."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import wiener_host as H
+    r = H.survey(sanitize=True)
+    cases = r["cases"]
+    for name, c in cases.items():
+        print(name, c)
+    for name in ("basic_prior", "alpha_ns_prior_and_box"):
+        c = cases[name]
+        assert c["rows"] == 20_000
+        assert c["max_abs_dlogf_inner"] <= 1e-4 and c["max_rel_dlogf_beyond"] <= 1e-5, name
+        assert c["max_abs_dF"] <= 2e-5 and c["max_abs_dp_upper"] <= 2e-5, name
+    for name in ("prior_1s", "prior_4s", "box", "fixture"):
+        c = cases["censored_" + name]
+        assert c["nan"] == 0 and c["above_0"] == 0 and c["increasing_pairs"] == 0, name
+        assert c["points_S_ge_1e-3"] > 1000 and c["max_err_over_bar"] <= 1.0 and c["max_abs_dcdf"] <= 2e-5, name
+    fx = cases["censored_fixture"]
+    assert fx["points_S_lt_1e-3"] > 1000 and fx["max_rel_err_S_lt_1e-3"] <= 1e-3 and fx["max_abs_dcdf_S_lt_1e-3"] <= 2e-5
+    got = np.array(fx["reported_rows_log_S"])
+    assert np.all(np.abs(got - C.REPORTED_LOG_S) <= 2e-5 + 1e-5 * np.abs(C.REPORTED_LOG_S) + 1e-5), got       # (+ the table's own rounding)
 
 
 def test_c_abi_exports_the_entry_and_validates_before_any_hip_call():

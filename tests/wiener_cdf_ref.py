@@ -158,6 +158,94 @@ def accuracy_rows(n, basic=False, seed=11):
     return p32, rt32, up, t
 
 
+def _basic_prior_rows(n, seed, dc_min=0.05):
+    """The first n rows of priors.basic_prior_matrix(seed) with dc >= dc_min (99.5 % of the draws; a / dc up to 28-39 and |v| / dc up to
+    80-96 on 20 000 of them, by the seed).  Below it the quotients grow without bound: DESIGN section 10."""
+    from bayesflow_nddms_amd import priors
+    rows = priors.basic_prior_matrix(n + n // 20 + 64, seed=seed)
+    rows = rows[rows[:, 4] >= dc_min]
+    assert rows.shape[0] >= n
+    return rows[:n]
+
+
+def prior_rows(n, basic=False, seed=11):
+    """accuracy_rows on the parameters the two models draw, with the same draw of u and of the boundary.  basic: rows of
+    priors.basic_prior_matrix with dc >= 0.05.  alpha_not_scaled: the first half rows of priors.alpha_ns_prior_matrix (Varsigma in
+    [0.8, 1.4], Eta in [0, 2]), the second half accuracy_rows' box with Varsigma ~ U(0.5, 2.0) in place of 1.  Returns what
+    accuracy_rows returns."""
+    from bayesflow_nddms_amd import priors
+    rng = np.random.default_rng(seed)
+    u = np.concatenate([np.exp(rng.uniform(np.log(1e-3), np.log(50.0), n - n // 4)), rng.uniform(0.3, 0.5, n // 4)])
+    up = rng.random(n) < 0.5
+    if basic:
+        p32 = _basic_prior_rows(n, seed)
+    else:
+        h = n // 2
+        m = n - h
+        nu, a, beta, tau = rng.uniform(-5, 5, m), rng.uniform(0.5, 2.5, m), rng.uniform(0.02, 0.98, m), rng.uniform(0.0, 0.5, m)
+        eta = np.where(rng.random(m) < 0.3, 0.0, rng.uniform(0, 3, m))
+        box = np.stack([nu, a, beta, tau, eta, rng.uniform(0.5, 2.0, m)], 1).astype(np.float32)
+        p32 = np.concatenate([priors.alpha_ns_prior_matrix(h, seed=seed), box])
+        rng.shuffle(u)                                                  # (the quarter in [0.3, 0.5] falls on both halves)
+    ap = p32[:, 1].astype(np.float64) / p32[:, -1].astype(np.float64)
+    rt32 = (p32[:, 3].astype(np.float64) + u * ap ** 2).astype(np.float32)
+    t = (rt32 - p32[:, 3]).astype(np.float32).astype(np.float64)
+    return p32, rt32, up, t
+
+
+S_FLOOR = 1e-3            # log_survival is the yardstick where S >= S_FLOOR; below it, wiener_ref.mp_log_survival (tests/golden/wiener_survival.npz)
+
+
+def log_survival(t, a, v, beta, s=1.0):
+    """log P(T > t) of the eta = 0 process as log1p(-(F_lower + F_upper)) of the distribution function above, which does not cancel at
+    small u as the survival series does: -> (log S, ok), ok where S >= S_FLOOR (float64 keeps 12 digits of S there); NaN elsewhere.
+    t <= 0 gives 0."""
+    t, a, v, beta, s = (np.array(x, np.float64) for x in np.broadcast_arrays(t, a, v, beta, s))
+    F = cdf(t, False, a, v, beta, s) + cdf(t, True, a, v, beta, s)
+    ok = 1.0 - F >= S_FLOOR
+    with np.errstate(all="ignore"):
+        return np.where(ok, np.log1p(-np.where(ok, F, 0.0)), np.nan), ok
+
+
+CENSOR_TIMES = 16         # increasing times per row of the censoring tests
+
+
+def _times(p32, t):
+    """float32 rt = tau + t [R, m] and the kernel's t = rt - tau in float32, as float64."""
+    rt32 = (p32[:, 3:4].astype(np.float64) + t).astype(np.float32)
+    return rt32, (rt32 - p32[:, 3:4]).astype(np.float32).astype(np.float64)
+
+
+def censor_sets(n_prior=5000, n_box=2000, seed=5, with_fixture=True):
+    """The rows of the censoring tests, basic_ddm_dc, CENSOR_TIMES increasing times each: name -> (float32 params [R, 5], float32 rt
+    [R, 16], float64 t = the kernel's float32 rt - tau).  `prior_1s` / `prior_4s`: prior_rows' basic rows at k / 16 of a 1 s and a 4 s
+    horizon (dt .01 x 100 and x 400 steps); `box`: the shipped tests' box (nu +-5, a .5-2.5, beta .02-.98, tau 0-.5, dc .8-1.3) at 16 sorted
+    draws of u log-uniform in [1e-3, 50]; `fixture`: tests/golden/wiener_survival.npz's own rows."""
+    rows = _basic_prior_rows(n_prior, seed)
+    k = np.arange(1, CENSOR_TIMES + 1, dtype=np.float64)[None, :] / CENSOR_TIMES
+    out = {"prior_1s": (rows,) + _times(rows, 1.0 * k + 0.0 * rows[:, :1]), "prior_4s": (rows,) + _times(rows, 4.0 * k + 0.0 * rows[:, :1])}
+    rng = np.random.default_rng(seed + 1)
+    box = np.stack([rng.uniform(-5, 5, n_box), rng.uniform(0.5, 2.5, n_box), rng.uniform(0.02, 0.98, n_box), rng.uniform(0.0, 0.5, n_box),
+                    rng.uniform(0.8, 1.3, n_box)], 1).astype(np.float32)
+    u = np.sort(np.exp(rng.uniform(np.log(1e-3), np.log(50.0), (n_box, CENSOR_TIMES))), axis=1)
+    ap = box[:, 1].astype(np.float64) / box[:, 4].astype(np.float64)
+    out["box"] = (box,) + _times(box, u * ap[:, None] ** 2)
+    if with_fixture:
+        import os
+        g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wiener_survival.npz"))
+        out["fixture"] = (g["params"], g["rt"], (g["rt"] - g["params"][:, 3:4]).astype(np.float32).astype(np.float64))
+    return out
+
+
+# the four rows of the censoring defect's report (drift, a, beta, tau, dc) and their decision times: the float32 large-time series gave
+# NaN, +9.3, +15.7 and -0.16 for log S = -0.000000, -2.507289, -0.009398 and -6.160853
+REPORTED_ROWS = np.array([[0.5261412, 1.9813986, 0.4452605, 0.4539135, 0.1136013], [1.6254113, 1.6473216, 0.1531147, 0.3260034, 0.1724049],
+                          [0.1823803, 1.2271703, 0.1858106, 0.4585065, 0.0559113], [0.2977207, 1.4949200, 0.4268077, 0.1464299, 0.0596928]], np.float32)
+REPORTED_T = np.array([1.0, 1.0, 4.0, 4.0])
+REPORTED_RT = np.array([1.4539136, 1.3260034, 4.4585066, 4.1464300], np.float32)
+REPORTED_LOG_S = np.array([-0.000000, -2.507289, -0.009398, -6.160853])
+
+
 def row_columns(p32, basic=False):
     """float64 (a, v, beta, tau, s, eta) of float32 parameter rows in either model's order."""
     p = p32.astype(np.float64)

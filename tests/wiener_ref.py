@@ -87,7 +87,10 @@ def survival(t, a, v, beta, s=1.0, K=LARGE_TERMS):
 
 
 def log_survival(t, a, v, beta, s=1.0):
-    """log P(T > t), the e^{-lambda_1 t} factor taken out so that long censoring times do not underflow."""
+    """log P(T > t), the e^{-lambda_1 t} factor taken out so that long censoring times do not underflow.  The series only: in float64 its
+    terms cancel once a'|v'|w exceeds about 36 at small u (inf or nan beyond), so it serves the wide-boundary rows of the priors no
+    better than the kernel's float32 did.  The yardstick that is right there is wiener_cdf_ref.log_survival (1 - F_lower - F_upper where
+    S >= 1e-3) and mp_log_survival below it."""
     ap, vp = a / s, v / s
     k = np.arange(1, LARGE_TERMS + 1, dtype=np.float64)
     lam = vp * vp / 2.0 + k * k * np.pi ** 2 / (2.0 * ap * ap)
@@ -107,3 +110,24 @@ def mp_g(u, w, small, K=400, dps=60):
         return mp.log(s / mp.sqrt(2 * mp.pi * u ** 3))
     s = mp.fsum(k * mp.exp(-k * k * mp.pi ** 2 * u / 2) * mp.sin(k * mp.pi * w) for k in range(1, K + 1))
     return mp.log(mp.pi * s)
+
+
+def mp_log_survival(t, a, v, beta, s=1.0, extra_digits=30):
+    """log P(T > t) from the large-time survival series at the precision the series needs (mpmath): its terms are up to e^{a'|v'|} large
+    and must cancel down to S ~ e^{-a'|v'|w - v'^2 t / 2} and, at small u, to e^{-1/(2u)} of their size, so the working precision is
+    sized by a'|v'| + v'^2 t / 2 + pi^2 u / 2 + 1 / (2u) (at a fixed 50 digits the sum comes out negative on the priors' rows), and the
+    number of terms by e^{-k^2 pi^2 u / 2} falling below that precision."""
+    import mpmath as mp
+    ap, vp = float(a) / float(s), float(v) / float(s)
+    u = float(t) / (ap * ap)
+    need = ap * abs(vp) + vp * vp * float(t) / 2.0 + np.pi ** 2 * u / 2.0 + 1.0 / (2.0 * u)
+    dps = int(extra_digits + need / np.log(10.0)) + 1
+    K = int(np.sqrt(2.0 * dps * np.log(10.0) / (np.pi ** 2 * u))) + 10
+    with mp.workdps(dps):
+        t_, a_, v_, b_ = mp.mpf(float(t)), mp.mpf(float(a)) / mp.mpf(float(s)), mp.mpf(float(v)) / mp.mpf(float(s)), mp.mpf(float(beta))
+        kk = mp.pi ** 2 / (2 * a_ * a_)
+        tot = mp.mpf(0)
+        for w, nu in ((b_, v_), (1 - b_, -v_)):
+            tot += mp.exp(-a_ * nu * w) * mp.fsum(k * mp.sin(k * mp.pi * w) * mp.exp(-(nu * nu / 2 + k * k * kk) * t_) / (nu * nu / 2 + k * k * kk)
+                                                  for k in range(1, K + 1))
+        return float(mp.log(mp.pi / (a_ * a_) * tot))

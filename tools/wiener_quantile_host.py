@@ -99,7 +99,8 @@ int main(int argc, char **argv) {
 """
 
 
-def build(td, sanitize=False):
+def build(td, sanitize=False, main=None, name="wiener_quantile_host"):
+    """Compile `main` (this tool's own program by default) against the stand-in header; tools/wiener_host.py builds its program here too."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if not cxx:
         raise RuntimeError("no host C++ compiler found")
@@ -107,8 +108,8 @@ def build(td, sanitize=False):
     with open(os.path.join(td, "hip", "hip_runtime.h"), "w") as f:
         f.write(SHIM)
     with open(os.path.join(td, "main.cpp"), "w") as f:
-        f.write(MAIN)
-    exe = os.path.join(td, "wiener_quantile_host")
+        f.write(MAIN if main is None else main)
+    exe = os.path.join(td, name)
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
     subprocess.check_call([cxx, "-std=c++17", "-w"] + flags + ["-I", td, "-I", CSRC, "-o", exe, os.path.join(td, "main.cpp")])
     return exe
