@@ -113,6 +113,26 @@ def log_likelihood(params, y, per_trial=False):
     return (r["loglik"], r["trial_logp"]) if per_trial else r["loglik"]
 
 
+def log_likelihood_and_grad(params, y):
+    """log p(y | params) and its gradient in (Nu, Alpha, Beta, Tau, Eta, Varsigma), one launch (engine.wiener_log_likelihood_grad): the
+    arguments of log_likelihood.  Returns (float64 [R], float64 [R, 6]) on the device; the first has log_likelihood's bits.  Where Nu is
+    clipped to +-5 its gradient is 0; y == 0 gives NaN in both.  For a differentiable torch value see likelihood.wiener_loglik."""
+    p = params if hasattr(params, "is_cuda") else np.asarray(params, dtype=np.float64).reshape(-1, 6)
+    if hasattr(y, "is_cuda"):
+        import torch
+        yy = y[None] if y.ndim == 1 else y
+        d = torch.stack([yy, (torch.sign(yy) + 1) / 2], -1)
+    else:
+        yy = np.asarray(y, dtype=np.float64)
+        yy = yy[None] if yy.ndim == 1 else yy
+        d = np.stack([yy, (np.sign(yy) + 1) / 2], -1)
+    R, D = (p.shape[0] if p.ndim == 2 else 1), d.shape[0]
+    if R % D:
+        raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
+    r = engine.wiener_log_likelihood_grad(engine.ALPHA_NOT_SCALED, p, d, draws_per_dataset=R // D)
+    return r["loglik"], r["grad"]
+
+
 def cdf(params, y):
     """P(T <= |y| - Tau, the boundary the sign of y names | params) of the generator's model (drift ~ N(Nu, Eta) integrated out, Nu clipped
     to +-5), one launch (engine.wiener_cdf): the arguments of log_likelihood.  y == 0 gives NaN.  Returns float32 [R, n_trials] on the

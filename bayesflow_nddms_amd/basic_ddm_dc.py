@@ -96,6 +96,21 @@ def log_likelihood(params, sim_data, per_trial=False):
     return (r["loglik"], r["trial_logp"]) if per_trial else r["loglik"]
 
 
+def log_likelihood_and_grad(params, sim_data):
+    """log p(sim_data | params) and its gradient in (drift, boundary, beta, tau, dc), one launch (engine.wiener_log_likelihood_grad): the
+    arguments of log_likelihood.  Returns (float64 [R], float64 [R, 5]) on the device; the first has log_likelihood's bits.
+    NOT IMPLEMENTED: the gradient of a censored timeout (choice 0) -- a row that holds one keeps its value and gets NaN in every
+    gradient column.  For a differentiable torch value see likelihood.wiener_loglik."""
+    p = params if hasattr(params, "is_cuda") else np.asarray(params, dtype=np.float64).reshape(-1, 5)
+    d = sim_data if hasattr(sim_data, "is_cuda") else np.asarray(sim_data, dtype=np.float64)
+    R = p.shape[0] if p.ndim == 2 else 1
+    D = d.shape[0] if d.ndim == 3 else 1
+    if R % D:
+        raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
+    r = engine.wiener_log_likelihood_grad(MODEL, p, d, draws_per_dataset=R // D)
+    return r["loglik"], r["grad"]
+
+
 def cdf(params, sim_data):
     """P(T <= rt - tau, the boundary each trial ended on | params), one launch (engine.wiener_cdf): the arguments of log_likelihood.  A
     timeout (choice 0) gives P(T <= rt - tau) over both boundaries.  Returns float32 [R, n_trials] on the device."""

@@ -34,6 +34,7 @@
 //
 // This translation unit: nddm_rng.h (random stream) -> nddm_sim.h (sim_kernel) -> nddm_prepass.h (pre-pass, combine, prior)
 // -> nddm_ratcliff.h (the exact first-passage sampler) -> nddm_wiener.h (the Wiener first-passage log-likelihood) -> nddm_wiener_cdf.h (its distribution function) -> nddm_wiener_quantile.h (its quantile function)
+// -> nddm_wiener_grad.h (the log-likelihood's value and gradient)
 // -> below: the host side (launch slots, sizing, dispatch) and the extern "C" entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -52,6 +53,7 @@
 #include "nddm_sim.h"
 #include "nddm_wiener.h"
 #include "nddm_wiener_cdf.h"
+#include "nddm_wiener_grad.h"
 #include "nddm_wiener_quantile.h"
 
 namespace nddm {
@@ -1153,6 +1155,50 @@ int nddm_wiener_quantile(int32_t model, const float *params, int64_t R, int64_t 
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener quantile kernel launch failed: %s", hipGetErrorString(e));
+    return NDDM_OK;
+}
+
+/* the value and the gradient of the Wiener first-passage log-likelihood in one launch: csrc/nddm_wiener_grad.h.  The argument checks, their
+ * order and their status codes are nddm_wiener_log_likelihood's.  One kernel launch, no scratch memory: capturable like a plain kernel. */
+int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
+                                    int32_t n_trials, uint32_t flags, double *out_loglik, double *out_grad, void *stream)
+{
+    using namespace nddm;
+    g_err[0] = 0;
+    if (model != NDDM_BASIC_DDM_DC && model != NDDM_ALPHA_NOT_SCALED) {
+        char m[16];
+        snprintf(m, sizeof m, "%d", (int)model);
+        return fail(NDDM_ERR_PARAM, "nddm_wiener_log_likelihood_grad: model %s has no closed-form likelihood here (NDDM_BASIC_DDM_DC and "
+                                    "NDDM_ALPHA_NOT_SCALED only)", m);
+    }
+    if (flags != 0u) return fail(NDDM_ERR_PARAM, "nddm_wiener_log_likelihood_grad: flags must be 0 (reserved)%s");
+    if (R < 0 || n_trials <= 0 || draws_per_dataset <= 0 || R % draws_per_dataset != 0)
+        return fail(NDDM_ERR_SHAPE, "R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required%s");
+    if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
+    if (R == 0) return NDDM_OK;
+    if (!params || !data) return fail(NDDM_ERR_NULL, "params or data is NULL%s");
+    if (!out_grad) return fail(NDDM_ERR_NULL, "out_grad is NULL%s");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = check_stream(st)) return rc;
+    WienerGradArgs A;
+    A.params = params; A.data = data; A.out_sum = out_loglik; A.out_grad = out_grad;
+    A.R = R; A.S = draws_per_dataset; A.N = n_trials; A.P = nddm_model_nparams(model);
+    // the layouts and the dispatch rule of nddm_wiener_log_likelihood, a workgroup owning WIENER_GRAD_ROWS rows; the values do not depend
+    // on the choice (nddm_wiener_grad.h)
+    const bool staged = draws_per_dataset >= WIENER_ROWS;
+    A.chunks = (draws_per_dataset + WIENER_GRAD_ROWS - 1) / WIENER_GRAD_ROWS;
+    const long long blocks = staged ? (R / draws_per_dataset) * A.chunks : (R + WIENER_GRAD_ROWS - 1) / WIENER_GRAD_ROWS;
+    if (blocks >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / 4 must be < 2^31)%s");
+    const dim3 grid((unsigned)blocks), block(256);
+    if (model == NDDM_BASIC_DDM_DC) {
+        if (staged) hipLaunchKernelGGL((wiener_grad_kernel<NDDM_BASIC_DDM_DC, true>), grid, block, 0, st, A);
+        else hipLaunchKernelGGL((wiener_grad_kernel<NDDM_BASIC_DDM_DC, false>), grid, block, 0, st, A);
+    } else {
+        if (staged) hipLaunchKernelGGL((wiener_grad_kernel<NDDM_ALPHA_NOT_SCALED, true>), grid, block, 0, st, A);
+        else hipLaunchKernelGGL((wiener_grad_kernel<NDDM_ALPHA_NOT_SCALED, false>), grid, block, 0, st, A);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener gradient kernel launch failed: %s", hipGetErrorString(e));
     return NDDM_OK;
 }
 

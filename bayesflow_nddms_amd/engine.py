@@ -398,6 +398,44 @@ def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=Fa
     return res
 
 
+# kernel launches wiener_log_likelihood_grad has made in this process (tests count them: one per forward plus backward)
+_WIENER_GRAD_LAUNCHES = [0]
+
+
+def wiener_grad_launches():
+    """Developer aid: how many launches wiener_log_likelihood_grad has made in this process."""
+    return _WIENER_GRAD_LAUNCHES[0]
+
+
+def wiener_log_likelihood_grad(model, params, data, draws_per_dataset=1, device=None):
+    """Log-likelihood of observed trials under the Wiener first-passage density AND its gradient in the parameter columns, one kernel
+    launch (include/nddm.h: nddm_wiener_log_likelihood_grad): what a gradient-based fit consumes per step.  The arguments of
+    wiener_log_likelihood.  Returns {'loglik': float64 [R], 'grad': float64 [R, P]} on the device; 'loglik' has the bits of
+    wiener_log_likelihood's.  alpha_not_scaled's Nu is clipped to +-5: where the clip is active d/dNu is 0.
+
+    An invalid row gives NaN in both; a trial at or below tau (-inf in the value) or an alpha_not_scaled y == 0 gives a NaN gradient.
+    NOT IMPLEMENTED: the gradient of basic_ddm_dc's censored timeouts (choice 0).  They are scored in 'loglik' exactly as
+    wiener_log_likelihood scores them, and the row's gradient is NaN in every column -- never a partial gradient.
+    Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are."""
+    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, data, draws_per_dataset, "likelihood", {"grad": True})
+    torch = require_device()
+    L = _lib.lib()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        p_dev = _device_rows(params, p_np, dev, *p_rows)
+        d_dev = _device_rows(data, d_np, dev, *d_rows)
+        N = int(d_dev.shape[1])
+        out_s = torch.empty((R,), dtype=torch.float64, device=dev)
+        out_g = torch.empty((R, NPARAMS[model]), dtype=torch.float64, device=dev)
+        if R > 0:
+            st = torch.cuda.current_stream(dev)
+            _lib.check(L.nddm_wiener_log_likelihood_grad(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, 0, _ptr(out_s), _ptr(out_g), st.cuda_stream))
+            _WIENER_GRAD_LAUNCHES[0] += 1
+            p_dev.record_stream(st)
+            d_dev.record_stream(st)
+    return {"loglik": out_s, "grad": out_g}
+
+
 def wiener_cdf(model, params, data, draws_per_dataset=1, want_cdf=True, want_p_upper=True, device=None):
     """Distribution function of observed trials under the Wiener first-passage law and the choice probability (include/nddm.h:
     nddm_wiener_cdf), one kernel launch: RWiener / HDDM pwiener, the companion of wiener_log_likelihood, whose arguments these are.

@@ -7,8 +7,9 @@
     qwiener(p, alpha, tau, beta, delta, resp)                   RWiener / HDDM qwiener, pwiener's inverse (nddm_wiener_quantile)
     wiener_rt_quantiles(probs, alpha, tau, beta, delta, ...)    the response-time quantiles of each boundary's own responses
     wiener_choice_prob(alpha, beta, delta, eta, varsigma)       P(upper boundary), drift variability integrated out
+    wiener_loglik(model, params, data, draws_per_dataset)       a row's log-likelihood, DIFFERENTIABLE in params (nddm_wiener_log_likelihood_grad)
 
-Both take numpy arrays, scalars or device tensors, broadcast them against each other (numpy rules), score every element in ONE kernel
+The first two take numpy arrays, scalars or device tensors, broadcast them against each other (numpy rules), score every element in ONE kernel
 launch and return a float32 device tensor of the broadcast shape.  The sign of y / Y is the response: positive = upper boundary.
 Invalid parameters give NaN, an RT at or below the non-decision time -inf (the math; see `stan_floor` for Stan's substitution).
 """
@@ -156,3 +157,47 @@ def wiener_rt_quantiles(probs, alpha, tau, beta, delta, eta=0.0, varsigma=1.0, d
         return torch.empty(shape + (2, Q), dtype=torch.float32, device=dev)
     out = engine.wiener_quantile(engine.ALPHA_NOT_SCALED, p, req, draws_per_dataset=p.shape[0], conditional=True, device=dev)["quantile"]
     return out.reshape(shape + (2, Q))
+
+
+_WienerLoglik = None
+
+
+def _wiener_loglik_function():
+    """The torch.autograd.Function behind wiener_loglik (made on first use: importing this module does not import torch)."""
+    global _WienerLoglik
+    if _WienerLoglik is None:
+        torch = engine._torch()
+
+        class WienerLoglik(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, params, data, model, draws_per_dataset, device):
+                r = engine.wiener_log_likelihood_grad(model, params.detach(), data.detach() if hasattr(data, "detach") else data,
+                                                      draws_per_dataset=draws_per_dataset, device=device)
+                ctx.save_for_backward(r["grad"])
+                ctx.params_shape, ctx.params_dtype, ctx.params_device = params.shape, params.dtype, params.device
+                return r["loglik"]
+
+            @staticmethod
+            def backward(ctx, grad_output):
+                (grad,) = ctx.saved_tensors                             # the forward's launch computed it: nothing is launched here
+                g = (grad_output.to(grad.dtype)[:, None] * grad).reshape(ctx.params_shape)
+                return g.to(device=ctx.params_device, dtype=ctx.params_dtype), None, None, None, None
+
+        _WienerLoglik = WienerLoglik
+    return _WienerLoglik
+
+
+def wiener_loglik(model, params, data, draws_per_dataset=1, device=None):
+    """A row's log-likelihood under the Wiener first-passage density, float64 [R] on the device, DIFFERENTIABLE with respect to `params`
+    (a torch tensor; [R, P] in the model's column order): the arguments of engine.wiener_log_likelihood_grad, whose ONE launch the forward
+    makes; it keeps the gradient, and the backward is grad_output[:, None] * grad cast to params' dtype -- no second launch.  `data` gets no
+    gradient.  With nothing requiring grad the values are the same.
+
+        loss = -likelihood.wiener_loglik(engine.BASIC_DDM_DC, theta, data).sum(); loss.backward()
+
+    alpha_not_scaled's Nu is clipped to +-5 (zero gradient where the clip is active).  NOT IMPLEMENTED: the gradient of basic_ddm_dc's
+    censored timeouts (choice 0) -- such a row's value is right and its gradient is NaN in every column, never a partial one."""
+    torch = engine._torch()                                             # (the engine call refuses bad host input before it asks for a device)
+    if not isinstance(params, torch.Tensor):
+        params = torch.as_tensor(np.asarray(params, dtype=np.float64))
+    return _wiener_loglik_function().apply(params, data, model, int(draws_per_dataset), device)

@@ -70,6 +70,7 @@ extern "C" {
 /* 4 (additive): nddm_wiener_log_likelihood.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_cdf.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_quantile. */
+/* 4 (additive): nddm_wiener_log_likelihood_grad.  No existing entry point changes. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -263,6 +264,26 @@ int nddm_simulratcliff(const float *params, int64_t B, int32_t n_trials, uint64_
 int nddm_wiener_log_likelihood(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
                                int32_t n_trials, uint32_t flags, float *out_trial_logp /* [R, n_trials] or NULL */,
                                double *out_loglik /* [R] or NULL */, void *stream);
+
+/* The same log-likelihood AND its gradient in the model's parameter columns, one fused launch: what a gradient-based fit consumes per
+ * step (Stan's NUTS over wiener_lpdf, MAP refinement, Laplace / variational fits, HMC or MALA on many data sets at once).  (ABI 4, additive)
+ *   model, params, draws_per_dataset, data, n_trials: exactly as nddm_wiener_log_likelihood takes them
+ *   flags              must be 0 (reserved): NDDM_ERR_PARAM otherwise
+ *   out_loglik         device f64 [R] or NULL: the row's log-likelihood, BIT FOR BIT nddm_wiener_log_likelihood's out_loglik
+ *   out_grad           device f64 [R, P] (NULL: NDDM_ERR_NULL): d out_loglik[r] / d params[r, j], in params' column order; alpha_not_scaled's Nu
+ *                      is clipped to +-5: where the clip is active the Nu column is 0 and the others are those of the clipped value
+ * Special values (none an error): an invalid row (nddm_wiener_log_likelihood's conditions) gives NaN in out_loglik and in every gradient
+ * column, the other rows unaffected; a trial with rt <= tau (-inf in the value) or an alpha_not_scaled y == 0 (NaN in the value) gives NaN
+ * in every gradient column of its row.
+ * NOT IMPLEMENTED: the gradient of basic_ddm_dc's censored timeouts (choice 0).  out_loglik scores them exactly as
+ * nddm_wiener_log_likelihood does (log P(T > rt - tau)); the row's gradient is NaN in EVERY column, never a partial gradient.
+ * The bits of both outputs are a function of (the row's parameters, its data set, n_trials) alone: the same whatever the layout, the
+ * draws_per_dataset factorisation, the stream or a capture.  No scratch memory, no atomics: a call made while `stream` is capturing is one
+ * kernel node.  Error checks, their order and their status codes are nddm_wiener_log_likelihood's; R = 0 is NDDM_OK.  The math:
+ * csrc/nddm_wiener_grad.h, DESIGN.md section 14. */
+int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
+                                    int32_t n_trials, uint32_t flags /* 0, reserved */, double *out_loglik /* [R] or NULL */,
+                                    double *out_grad /* [R, P] */, void *stream);
 
 /* The distribution function of the same first-passage law (RWiener / HDDM pwiener, the companion of dwiener) and the choice
  * probability: where in its distribution an observed response time falls -- posterior predictive p-values, probability-integral
