@@ -34,7 +34,7 @@
 //
 // This translation unit: nddm_rng.h (random stream) -> nddm_sim.h (sim_kernel) -> nddm_prepass.h (pre-pass, combine, prior)
 // -> nddm_ratcliff.h (the exact first-passage sampler) -> nddm_wiener.h (the Wiener first-passage log-likelihood) -> nddm_wiener_cdf.h (its distribution function) -> nddm_wiener_quantile.h (its quantile function)
-// -> nddm_wiener_grad.h (the log-likelihood's value and gradient)
+// -> nddm_wiener_grad.h (the log-likelihood's value and gradient) -> nddm_wiener_marginal.h (the single-trial model's marginal log-likelihood)
 // -> below: the host side (launch slots, sizing, dispatch) and the extern "C" entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -54,6 +54,7 @@
 #include "nddm_wiener.h"
 #include "nddm_wiener_cdf.h"
 #include "nddm_wiener_grad.h"
+#include "nddm_wiener_marginal.h"
 #include "nddm_wiener_quantile.h"
 
 namespace nddm {
@@ -1199,6 +1200,46 @@ int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t 
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener gradient kernel launch failed: %s", hipGetErrorString(e));
+    return NDDM_OK;
+}
+
+/* the single-trial model's marginal log-likelihood (the latent per-trial boundary integrated out by quadrature): csrc/nddm_wiener_marginal.h.
+ * The argument checks, their order and their status codes are nddm_wiener_log_likelihood's.  One kernel launch, no scratch memory: capturable
+ * like a plain kernel. */
+int nddm_wiener_marginal_log_likelihood(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
+                                        int32_t n_trials, float t_censor, uint32_t flags, float *out_trial, double *out_sum, void *stream)
+{
+    using namespace nddm;
+    g_err[0] = 0;
+    if (model != NDDM_SINGLE_TRIAL) {
+        char m[16];
+        snprintf(m, sizeof m, "%d", (int)model);
+        return fail(NDDM_ERR_PARAM, "nddm_wiener_marginal_log_likelihood: model %s has no marginal likelihood here (NDDM_SINGLE_TRIAL only)", m);
+    }
+    if (flags != 0u) return fail(NDDM_ERR_PARAM, "nddm_wiener_marginal_log_likelihood: flags must be 0 (reserved)%s");
+    if (R < 0 || n_trials <= 0 || draws_per_dataset <= 0 || R % draws_per_dataset != 0)
+        return fail(NDDM_ERR_SHAPE, "R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required%s");
+    if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
+    if (R == 0) return NDDM_OK;
+    if (!params || !data) return fail(NDDM_ERR_NULL, "params or data is NULL%s");
+    if (!out_trial && !out_sum) return fail(NDDM_ERR_NULL, "no output buffer given%s");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = check_stream(st)) return rc;
+    WienerMarginalArgs A;
+    A.params = params; A.data = data; A.out_trial = out_trial; A.out_sum = out_sum;
+    A.R = R; A.S = draws_per_dataset; A.N = n_trials; A.P = nddm_model_nparams(model);
+    A.t_censor = t_censor;
+    // the layouts and the dispatch rule of nddm_wiener_log_likelihood, a workgroup owning WMARG_ROWS rows; the values do not depend on the
+    // choice (nddm_wiener_marginal.h)
+    const bool staged = draws_per_dataset >= WIENER_ROWS;
+    A.chunks = (draws_per_dataset + WMARG_ROWS - 1) / WMARG_ROWS;
+    const long long blocks = staged ? (R / draws_per_dataset) * A.chunks : (R + WMARG_ROWS - 1) / WMARG_ROWS;
+    if (blocks >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / 4 must be < 2^31)%s");
+    const dim3 grid((unsigned)blocks), block(256);
+    if (staged) hipLaunchKernelGGL((wiener_marginal_kernel<true>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((wiener_marginal_kernel<false>), grid, block, 0, st, A);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener marginal kernel launch failed: %s", hipGetErrorString(e));
     return NDDM_OK;
 }
 

@@ -332,12 +332,28 @@ def _wiener_check_params(model, p_np):
         raise ValueError("tau and Eta must be >= 0")
 
 
-def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs, requests=False):
-    """The front end wiener_log_likelihood, wiener_cdf and wiener_quantile share: host inputs are refused here (ValueError), before any
-    device work; a device tensor's shape is checked where it is cast, after the split.  -> (S, params' and data's row descriptions, the
-    host arrays or None, R).  `what`: the quantity the model would have to have a closed form of; `outputs`: the caller's output
-    switches by name; `requests`: `data` holds wiener_quantile's (p, boundary code) pairs instead of trials."""
-    if model not in (BASIC_DDM_DC, ALPHA_NOT_SCALED):
+def _marginal_check_params(p_np):
+    """Range checks of host-side SINGLE_TRIAL parameters for the marginal likelihood (ValueError, before any device work)."""
+    if not np.all(np.isfinite(p_np)):
+        raise ValueError("parameters must be finite")
+    if np.any(p_np[:, 4] <= 0) or np.any(p_np[:, 6] <= 0) or np.any(p_np[:, 5] <= 0):
+        raise ValueError("std_alpha, sigma1 and dc must be > 0")
+    if np.any(p_np[:, 2] <= 0) or np.any(p_np[:, 2] >= 1):
+        raise ValueError("beta must lie in (0, 1)")
+    if np.any(p_np[:, 3] < 0):
+        raise ValueError("ter must be >= 0")
+
+
+def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs, requests=False, marginal=False):
+    """The front end wiener_log_likelihood, wiener_cdf, wiener_quantile and wiener_marginal_log_likelihood share: host inputs are refused
+    here (ValueError), before any device work; a device tensor's shape is checked where it is cast, after the split.  -> (S, params' and
+    data's row descriptions, the host arrays or None, R).  `what`: the quantity the model would have to have a closed form of; `outputs`:
+    the caller's output switches by name; `requests`: `data` holds wiener_quantile's (p, boundary code) pairs instead of trials;
+    `marginal`: the caller integrates SINGLE_TRIAL's latent boundary out -- that model and no other, its columns and (choicert, z1) data."""
+    if marginal:
+        if model != SINGLE_TRIAL:
+            raise ValueError(f"model {model} has no {what} here (SINGLE_TRIAL only)")
+    elif model not in (BASIC_DDM_DC, ALPHA_NOT_SCALED):
         raise ValueError(f"model {model} has no closed-form {what} here (BASIC_DDM_DC and ALPHA_NOT_SCALED only)")
     if not any(outputs.values()):
         raise ValueError("ask for " + " and/or ".join(outputs))
@@ -348,7 +364,7 @@ def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs, r
     d_rows = (3, 2, "probs must have shape [D, n, 2]" if requests else "data must have shape [D, n_trials, 2]")
     p_np = _host_rows(params, *p_rows)
     if p_np is not None:
-        _wiener_check_params(model, p_np)
+        _marginal_check_params(p_np) if marginal else _wiener_check_params(model, p_np)
     d_np = _host_rows(data, *d_rows)
     if d_np is not None and requests:
         if not np.all(np.isin(d_np[..., 1], (-1.0, 0.0, 1.0))):
@@ -388,6 +404,43 @@ def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=Fa
         if R > 0:
             st = torch.cuda.current_stream(dev)
             _lib.check(L.nddm_wiener_log_likelihood(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, 0, _ptr(out_t), _ptr(out_s), st.cuda_stream))
+            p_dev.record_stream(st)
+            d_dev.record_stream(st)
+    res = {}
+    if out_s is not None:
+        res["loglik"] = out_s
+    if out_t is not None:
+        res["trial_logp"] = out_t
+    return res
+
+
+def wiener_marginal_log_likelihood(model, params, data, draws_per_dataset=1, t_censor=None, per_trial=False, want_sum=True, device=None):
+    """Marginal log-likelihood of observed trials under the single-trial model, the latent per-trial boundary integrated out (include/nddm.h:
+    nddm_wiener_marginal_log_likelihood), one kernel launch.
+
+    model: SINGLE_TRIAL (params [R, 8] = drift, mu_alpha, beta, ter, std_alpha, dc, sigma1, gamma; data (choicert, z1)).  data: [D, n_trials,
+    2] in the simulator's output format, R = D * draws_per_dataset, row r scored against data set r // draws_per_dataset.  t_censor: the
+    decision time a timeout (choicert == 0) is censored at, the simulator's max_steps * dt; None: timeouts give NaN.
+    Returns a dict of device tensors: 'loglik' float64 [R] (want_sum) and 'trial_logp' float32 [R, n_trials] (per_trial).
+    Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN."""
+    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, data, draws_per_dataset, "marginal likelihood",
+                                                           {"per_trial": per_trial, "want_sum": want_sum}, marginal=True)
+    tc = 0.0 if t_censor is None else float(t_censor)
+    if math.isnan(tc) or tc < 0:
+        raise ValueError("t_censor must be >= 0 (or None: timeouts then give NaN)")
+    torch = require_device()
+    L = _lib.lib()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        p_dev = _device_rows(params, p_np, dev, *p_rows)
+        d_dev = _device_rows(data, d_np, dev, *d_rows)
+        N = int(d_dev.shape[1])
+        out_t = torch.empty((R, N), dtype=torch.float32, device=dev) if per_trial else None
+        out_s = torch.empty((R,), dtype=torch.float64, device=dev) if want_sum else None
+        if R > 0:
+            st = torch.cuda.current_stream(dev)
+            _lib.check(L.nddm_wiener_marginal_log_likelihood(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, tc, 0, _ptr(out_t), _ptr(out_s),
+                                                             st.cuda_stream))
             p_dev.record_stream(st)
             d_dev.record_stream(st)
     res = {}

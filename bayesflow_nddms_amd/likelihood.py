@@ -8,6 +8,8 @@
     wiener_rt_quantiles(probs, alpha, tau, beta, delta, ...)    the response-time quantiles of each boundary's own responses
     wiener_choice_prob(alpha, beta, delta, eta, varsigma)       P(upper boundary), drift variability integrated out
     wiener_loglik(model, params, data, draws_per_dataset)       a row's log-likelihood, DIFFERENTIABLE in params (nddm_wiener_log_likelihood_grad)
+    single_trial_logpdf(y, z, drift, mu_alpha, beta, ter, ...)  the single-trial model's joint log density of (choicert, z1), the latent
+                                                                boundary integrated out (nddm_wiener_marginal_log_likelihood)
 
 The first two take numpy arrays, scalars or device tensors, broadcast them against each other (numpy rules), score every element in ONE kernel
 launch and return a float32 device tensor of the broadcast shape.  The sign of y / Y is the response: positive = upper boundary.
@@ -201,3 +203,30 @@ def wiener_loglik(model, params, data, draws_per_dataset=1, device=None):
     if not isinstance(params, torch.Tensor):
         params = torch.as_tensor(np.asarray(params, dtype=np.float64))
     return _wiener_loglik_function().apply(params, data, model, int(draws_per_dataset), device)
+
+
+def single_trial_logpdf(y, z, drift, mu_alpha, beta, ter, std_alpha, dc, sigma1, gamma=1.0, t_censor=None, device=None):
+    """Joint log density of one trial (choicert y, external datum z) of the single-trial model, the per-trial boundary
+    a ~ N(mu_alpha, std_alpha^2) | a > 0 integrated out (engine.wiener_marginal_log_likelihood).  Every argument
+    broadcasts as dwiener_logpdf's do (numpy rules), one kernel launch; returns a float32 device tensor of the broadcast shape.
+    y == 0 is a timeout, scored as log P(no response before t_censor) -- NaN with t_censor=None; |y| <= ter gives -inf, invalid parameters NaN."""
+    torch = engine.require_device()
+    dev = engine._device(device)
+    y, z = _dev(y, dev), _dev(z, dev)
+    cols = [_dev(c, dev) for c in (drift, mu_alpha, beta, ter, std_alpha, dc, sigma1, gamma)]
+    shape = tuple(torch.broadcast_shapes(y.shape, z.shape, *(c.shape for c in cols)))
+    full = shape if shape else (1,)
+    pad = lambda x: x.reshape((1,) * (len(full) - x.dim()) + tuple(x.shape))
+    y, z, cols = pad(y), pad(z), [pad(c) for c in cols]
+    n, lead = full[-1], full[:-1]
+    if all(c.shape[-1] == 1 for c in cols):       # parameters constant along the last axis: one row per leading index, n trials each
+        p = torch.stack([c.expand(lead + (1,)) for c in cols], -1).reshape(-1, 8)
+        data = torch.stack([y.expand(full).reshape(-1, n), z.expand(full).reshape(-1, n)], -1)
+    else:                                         # one row per element
+        p = torch.stack([c.expand(full) for c in cols], -1).reshape(-1, 8)
+        data = torch.stack([y.expand(full).reshape(-1, 1), z.expand(full).reshape(-1, 1)], -1)
+    if p.shape[0] == 0 or data.shape[1] == 0:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    out = engine.wiener_marginal_log_likelihood(engine.SINGLE_TRIAL, p.contiguous(), data.contiguous(), t_censor=t_censor, per_trial=True,
+                                                want_sum=False, device=dev)
+    return out["trial_logp"].reshape(shape)

@@ -71,6 +71,7 @@ extern "C" {
 /* 4 (additive): nddm_wiener_cdf.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_quantile. */
 /* 4 (additive): nddm_wiener_log_likelihood_grad.  No existing entry point changes. */
+/* 4 (additive): nddm_wiener_marginal_log_likelihood.  No existing entry point changes. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -284,6 +285,32 @@ int nddm_wiener_log_likelihood(int32_t model, const float *params, int64_t R, in
 int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
                                     int32_t n_trials, uint32_t flags /* 0, reserved */, double *out_loglik /* [R] or NULL */,
                                     double *out_grad /* [R, P] */, void *stream);
+
+/* The single-trial model's MARGINAL log-likelihood: the per-trial boundary a ~ N(mu_alpha, std_alpha^2) | a > 0 is latent, z1 ~ N(gamma a,
+ * sigma1^2) observes it, and the response is the first passage of the Wiener process with boundary a; the latent is integrated out, one
+ * one-dimensional quadrature per (parameter row, trial), one launch.  What importance weights, posterior-predictive log scores and
+ * likelihood-based fits of this model need.  (ABI 4, additive)
+ *   model              NDDM_SINGLE_TRIAL only: NDDM_ERR_PARAM otherwise.  NDDM_SINGLE_TRIAL_ALT (a latent diffusion coefficient) is OUT OF
+ *                      SCOPE: its latent enters the process differently and it has no likelihood here
+ *   params             device f32 [R, 8]: drift, mu_alpha, beta, ter, std_alpha, dc, sigma1, gamma
+ *   draws_per_dataset, data, n_trials: as nddm_wiener_log_likelihood takes them; data device f32 [D, n_trials, 2] = (choicert, z1), the
+ *                      simulator's output format: choicert = +-(ter + decision time), positive the upper boundary, 0 a timeout
+ *   t_censor           the decision time a timeout (choicert == 0) is censored at, in seconds: the simulator's max_steps * dt.  A timeout
+ *                      carries no time in this model's output
+ *   flags              must be 0 (reserved): NDDM_ERR_PARAM otherwise
+ *   out_trial          device f32 [R, n_trials] or NULL: the joint log density of (choicert, z1) of trial i under row r
+ *   out_sum            device f64 [R] or NULL (not both NULL): its sum over the trials, in a fixed order
+ * Special values (none an error): a row with a non-finite parameter, std_alpha <= 0, sigma1 <= 0, dc <= 0, beta outside (0, 1) or ter < 0
+ * gives NaN for every trial and its sum, the other rows unaffected; |choicert| <= ter gives -inf; choicert == 0 is scored as
+ * log P(no response before t_censor) when t_censor > 0 and gives NaN otherwise; a non-finite z1 gives NaN.  A valid row with a valid
+ * trial never gives NaN or +inf.
+ * The bits of out_sum are a function of (the row's parameters, its data set, n_trials, t_censor) alone: the same whatever the layout, the
+ * draws_per_dataset factorisation, the stream or a capture.  No scratch memory, no atomics: a call made while `stream` is capturing is one
+ * kernel node.  Error checks, their order and their status codes are nddm_wiener_log_likelihood's; R = 0 is NDDM_OK.  No gradient.  The
+ * math, the quadrature and its accuracy: csrc/nddm_wiener_marginal.h, DESIGN.md section 15. */
+int nddm_wiener_marginal_log_likelihood(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
+                                        int32_t n_trials, float t_censor, uint32_t flags /* 0, reserved */,
+                                        float *out_trial /* [R, n_trials] or NULL */, double *out_sum /* [R] or NULL */, void *stream);
 
 /* The distribution function of the same first-passage law (RWiener / HDDM pwiener, the companion of dwiener) and the choice
  * probability: where in its distribution an observed response time falls -- posterior predictive p-values, probability-integral
