@@ -38,7 +38,8 @@ def simulratcliff_em(N=100, Alpha=1, Tau=.4, Nu=1, Beta=.5, Eta=.3, Varsigma=1, 
 
 def simulratcliff(N=100, Alpha=1, Tau=.4, Nu=1, Beta=.5, rangeTau=0, rangeBeta=0, Eta=.3, Varsigma=1, seed=None, set_offset=None, fast=None):
     """pyhddmjagsutils.simulratcliff (:47-176) with its own signature, on the device: signed RTs float64 [N] (negative = response B)
-    from the exact first-passage sampler.  rangeTau / rangeBeta must be 0 (the generator never passes them: alpha_not_scaled.py:96-97)."""
+    from the exact first-passage sampler.  rangeTau / rangeBeta must be 0 (the generator never passes them: alpha_not_scaled.py:96-97).
+    A trial the sampler cannot finish (parameters beyond its domain: engine.simulratcliff) is NaN."""
     if rangeTau != 0 or rangeBeta != 0:
         raise ValueError("the device sampler takes rangeTau = rangeBeta = 0 (as alpha_not_scaled.py:96-97 calls it)")
     r = engine.simulratcliff([[Nu, Alpha, Beta, Tau, Eta, Varsigma]], N, seed=seed, set_offset=set_offset, fast=fast, want_summary=False)

@@ -1008,7 +1008,7 @@ int nddm_simulratcliff(const float *params, int64_t B, int32_t n_trials, uint64_
     if ((long long)group > vB) group = (int)vB;
     A.group = group;
     A.tile_magic = (uint32_t)((0x100000000ull + (unsigned long long)tile_slots - 1ull) / (unsigned long long)tile_slots);
-    // uniform rings | drift FIFO | round keys | table | staged results
+    // table | uniform rings | drift FIFO | round keys | staged results (the kernel's order: the table first)
     const size_t lds = ((size_t)WAVE * 8 + RATCLIFF_FIFO + RATCLIFF_KEYS + (size_t)group * RT_WORDS + (size_t)group * (size_t)tile_slots) * sizeof(float);
     const long long n_groups = (vB + group - 1) / group;
     const dim3 grid((unsigned)n_groups), block(WAVE);

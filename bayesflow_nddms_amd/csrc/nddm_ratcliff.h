@@ -12,10 +12,22 @@
 //   at mu = 0);  P(up) = 1 / (1 + e) or e / (1 + e), e = exp(-|r mu / D|);  an attempt (s2, s1) is accepted when
 //   s2 e^-a <= e^-a + sum_{k = 3, 5, ..} (-+) k e^{-a k^2},  a = -F ln s1  (the reference's s2 <= 1 + s1^-F * series, without a positive
 //   exponent); the series stops when a term no longer changes the float32 sum (<= 64 terms); a < 2^-6 is rejected without it (the bound
-//   is below 2^-33, the smallest uniform); the sphere's time is -ln(s1) / lambda.  Caps that make every loop finite: 4096 attempts
-//   (then accepted), 4096 spheres (then ended on the nearer boundary).  The FAST mode evaluates the same acceptance function without
-//   the loop: three terms of the series or of its Jacobi-dual form, whichever converges (see the attempt below).  Laid out for
-//   64-lane waves:
+//   is below 2^-33, the smallest uniform); the sphere's time is -ln(s1) / lambda.  The FAST mode evaluates the same acceptance function
+//   without the loop: three terms of the series or of its Jacobi-dual form, whichever converges (see the attempt below).
+// What the sampler cannot sample it FLAGS -- two rules, the same in both modes and in the checker:
+//   1. an INVALID ROW -- any of the six columns non-finite, Alpha <= 0, Varsigma <= 0, Beta outside [0, 1] or Eta < 0: what
+//      engine.simulratcliff refuses for host arrays -- is decided once, where the per-tile table is written, and not simulated: every
+//      trial is (NaN, NaN), the summary is finalize_summary's for n_total missing trials (n_upper = n_lower = 0, n_missing = n_total,
+//      moments NaN); ext keeps its formula.  Beta = 0 or 1 is valid: the trial ends at once on that boundary;
+//   2. the caps that make every loop finite -- 4096 attempts per sphere, 4096 spheres per trial -- ARE reached by valid rows: an attempt
+//      is accepted on a = F (-ln s1), and a float32 uniform gives -ln s1 <= 22.9, so once G passes ~7 (F = 1 / (1 + G^2)) no attempt
+//      can be accepted.  A trial that reaches either cap ends there, at the first hit, as (NaN, NaN), is counted in n_missing and enters
+//      no other count and no moment (also through the partial sums of a split set).  THE DOMAIN: G = r mu / (D pi) on the first sphere
+//      (r = Alpha min(Beta, 1 - Beta), mu the trial's drift, D = Varsigma^2 / 2) below roughly 6: all of the generator's box
+//      (alpha_not_scaled.py:66-72) but the far tail of the per-trial drift at its corner of large Nu, Alpha and Eta with small
+//      Varsigma.  Beyond G ~ 7 n_missing says how much of the row is lost (DESIGN.md 5.5 has the table).  (A decision time that is
+//      no number -- a valid row whose Varsigma^2 leaves float32's range -- is missing in the same way.)
+// Laid out for 64-lane waves:
 //   * a single-wave workgroup works on a GROUP of consecutive tiles (a tile = one parameter set of <= 512 trials; ~1000 trials per
 //     group) with PERSISTENT LANES: the trial loop, the sphere loop and the rejection loop of the reference are flattened into ONE
 //     loop whose trip is one rejection attempt, and a lane whose trial ended takes the group's next trial at the top of the next trip
@@ -29,7 +41,7 @@
 //   * results are staged in LDS as one float per trial (the decision time with the response as its sign bit) and flushed as whole
 //     float2 (y, acc) lines with the fused summary reduction (integer sums of the decision time in 2^-16 s: bit-reproducible).
 // The path is VALU-issue bound (per trial ~2.6 attempts, ~1.8 spheres, ~3.2 Philox blocks; the vector pipe is saturated at an exec-mask
-// utilisation of 0.70: profiles/r6_ratcliff_summary.md, tools/ratcliff_isa_mix.py); 8 B are written per trial.
+// utilisation of 0.77: profiles/r6_ratcliff_summary.md, tools/ratcliff_isa_mix.py); 8 B are written per trial.
 #pragma once
 #include "nddm_sim.h"
 
@@ -117,6 +129,7 @@ __device__ __forceinline__ unsigned long long wave_sum_dpp64(unsigned long long 
 }
 
 // per-tile constants in LDS (RT_WORDS dwords per tile of the group), written by lane l for tile l when a group opens
+constexpr uint32_t RT_INVALID = 0x80000000u;     // in RT_NHERE: the tile of an invalid parameter row (as an int the count is < 0)
 enum { RT_NU = 0, RT_ETA, RT_INVD, RT_CLAM2, RT_DU0, RT_DL0, RT_TAU, RT_ALPHA, RT_SETLO, RT_SETHI, RT_NHERE, RT_T0, RT_WORDS };
 
 template <bool FAST>
@@ -165,13 +178,18 @@ __global__ __launch_bounds__(WAVE) void ratcliff_kernel(const RatArgs A)
             const float D = (Vs * Vs) * 0.5f, inv_D = 1.0f / D;                         // :117
             const float c_lam2 = (0.25f * D) * 9.86960440108935862f;                    // 0.25 D pi^2
             const float zz = Beta * Alpha, du0 = Alpha - zz, dl0 = zz;
+            // rule 1: what engine.simulratcliff refuses for host arrays (a NaN fails its comparison; the RAW Nu: the clip hides an
+            // infinite one).  The row's tile is marked in the sign bit of its trial count: the hand-out then sees no trial in it
+            // (every slot a hole: nothing is simulated) and the flush writes the tile as missing
+            bool valid = (Alpha > 0.0f) & (Vs > 0.0f) & (Beta >= 0.0f) & (Beta <= 1.0f) & (Eta >= 0.0f);
+            for (int c = 0; c < 6; ++c) valid &= __builtin_isfinite(p[c]) != 0;
             const unsigned long long gset = A.set_offset + (unsigned long long)set;
             uint32_t *t = tbl + lane * RT_WORDS;
             t[RT_NU] = __float_as_uint(Nu); t[RT_ETA] = __float_as_uint(Eta); t[RT_INVD] = __float_as_uint(inv_D);
             t[RT_CLAM2] = __float_as_uint(c_lam2); t[RT_DU0] = __float_as_uint(du0); t[RT_DL0] = __float_as_uint(dl0);
             t[RT_TAU] = __float_as_uint(Tau); t[RT_ALPHA] = __float_as_uint(Alpha);
             t[RT_SETLO] = (uint32_t)gset; t[RT_SETHI] = (uint32_t)(gset >> 32) & 0x0fffffffu;
-            t[RT_NHERE] = (uint32_t)n_here; t[RT_T0] = (uint32_t)t0;
+            t[RT_NHERE] = (uint32_t)n_here | (valid ? 0u : RT_INVALID); t[RT_T0] = (uint32_t)t0;
         }
         __syncthreads();
 
@@ -193,15 +211,17 @@ __global__ __launch_bounds__(WAVE) void ratcliff_kernel(const RatArgs A)
         auto slot_tile = [&](int idx) { return (int)__umulhi((uint32_t)idx, A.tile_magic); };      // (n_trials >= 2: see the launch)
 
         // the sphere that starts at the current position: its constants and its direction (one uniform) -- or the end of the
-        // trial, when the position lies on a boundary (Beta = 0 or 1) or the safety cap is reached; returns "the trial goes on"
+        // trial, when the position lies on a boundary (Beta = 0 or 1) or the sphere cap is reached; returns "the trial goes on"
         auto setup_sphere = [&]() -> bool {
             // (straight-line but for the store: every level of nested divergence costs the loop ~10 scalar instructions of exec-mask
             //  bookkeeping and copies of the loop-carried state at its edges -- tools/ratcliff_isa_mix.py; a trial that ends computes a
             //  sphere nobody uses)
             float radius;                                 // min(du, dl): ONE v_min_f32 (fminf() quiets its operands first: two more instructions)
             asm("v_min_f32 %0, %1, %2" : "=v"(radius) : "v"(du), "v"(dl));
+            // (a valid row's radius is >= 0, and 0 only at its first sphere: Beta = 0 or 1, the trial ends at once on that boundary;
+            //  a trial that reaches the sphere cap ends as missing -- rule 2)
             const bool dead = !(radius > 0.0f) | (sphere >= RATCLIFF_MAX_SPHERES);
-            if (dead) staged[slot] = copysignf(total, du <= dl ? 1.0f : -1.0f);
+            if (dead) staged[slot] = radius > 0.0f ? __builtin_nanf("") : copysignf(total, du <= dl ? 1.0f : -1.0f);
             lam = lam1 + rat_div<FAST>(c_lam2, radius * radius);                         // :138
             const float Gr = radius * g1;
             F = rat_div<FAST>(1.0f, __builtin_fmaf(Gr, Gr, 1.0f));                       // :140-141, F0^2 / (1 + F0^2) with F0 = 1 / G
@@ -243,7 +263,7 @@ __global__ __launch_bounds__(WAVE) void ratcliff_kernel(const RatArgs A)
                     const int tile = slot_tile(idc);
                     const int tr = idc - __mul24(tile, A.n_trials);
                     const uint32_t *t = tbl + __mul24(tile, RT_WORDS);
-                    if (!has & (idx < n_slots) & (tr < (int)t[RT_NHERE])) {
+                    if (!has & (idx < n_slots) & (tr < (int)t[RT_NHERE])) {           // (an invalid row's count is negative)
                         slot = idx;
                         const uint32_t trial = t[RT_T0] + (uint32_t)tr;
                         const float inv_D = __uint_as_float(t[RT_INVD]);
@@ -295,7 +315,7 @@ __global__ __launch_bounds__(WAVE) void ratcliff_kernel(const RatArgs A)
                     const float rhs = P * (dual ? (0.696040999f * (rs * ra)) * E : 1.0f);
                     accept = has & ((att >= RATCLIFF_MAX_ATTEMPTS) | (!(a < 0.015625f) & (lhs <= rhs)));
                 } else {
-                    if (att >= RATCLIFF_MAX_ATTEMPTS) accept = true;
+                    if (att >= RATCLIFF_MAX_ATTEMPTS) accept = true;      // (the cap: ends the trial below)
                     else if (!(a < 0.015625f)) {
                         const float ea = rat_exp_neg<FAST>(a);
                         // (k = 3, 5, 7, .. and the alternating sign are carried as floats: k + 2 and -sgn are exact, and fma(+-1, term, told)
@@ -314,12 +334,15 @@ __global__ __launch_bounds__(WAVE) void ratcliff_kernel(const RatArgs A)
                     }
                 }
                 if (accept) {
+                    // rule 2: the attempt the cap "accepted" was never tested -- the trial ends here as missing (att is compared again,
+                    // here where a trip in ~2.6 comes, instead of carrying a flag through the loop)
+                    const bool capped = att >= RATCLIFF_MAX_ATTEMPTS;
                     total += rat_div<FAST>(nl, lam);                                     // :161-163
                     // the distances ahead of and behind the step: the nearer boundary is reached when the one ahead is the smaller
                     // (:165-172: du <= dl going up, dl <= du going down) -- and then it is the radius, else the one behind is
                     const float ahead = up ? du : dl, behind = up ? dl : du;
-                    const bool hit = ahead <= behind;
-                    if (hit) staged[slot] = copysignf(total, up ? 1.0f : -1.0f);
+                    const bool hit = capped | (ahead <= behind);
+                    if (hit) staged[slot] = capped ? __builtin_nanf("") : copysignf(total, up ? 1.0f : -1.0f);
                     // else the position moves by the radius (:174-175); a trial that ended moves too, unobserved
                     const float radius = hit ? ahead : behind;                           // = min(du, dl)
                     const float d = up ? radius : -radius;
@@ -333,24 +356,27 @@ __global__ __launch_bounds__(WAVE) void ratcliff_kernel(const RatArgs A)
         // ---- flush, tile by tile: whole float2 lines + the fused summary's integer sums (decision time in 2^-16 s), reduced over the
         // wave by DPP (as shuffles the five sums are 54 ds_bpermute round trips per tile; as LDS atomics on one address 200 cycles of
         // the CU's LDS pipe each: 11.5 ms instead of 4.3) and parked in LDS -- lane `tile`'s uniform ring: nobody draws any more --
-        // for the group's epilogue.  [0] sum k + (n_upper << 40)  [1] sum k^2  [2] sum k (upper)  [3] sum k^2 (upper);  k < 2^26
+        // for the group's epilogue.  [0] sum k + (n_upper << 40) + (n_missing << 52)  [1] sum k^2  [2] sum k (upper)  [3] sum k^2 (upper);  k < 2^26
         for (int tile = 0; tile < g_here; ++tile) {
             const uint32_t *t = tbl + tile * RT_WORDS;
             const long long vset = v0 + tile;
             const long long set = TPS == 1 ? vset : vset / TPS;
-            const int n_here = (int)t[RT_NHERE], t0 = (int)t[RT_T0];
+            const int n_here = (int)(t[RT_NHERE] & ~RT_INVALID), t0 = (int)t[RT_T0];
+            const bool invalid = (t[RT_NHERE] & RT_INVALID) != 0u;     // (nothing was staged for this tile)
             const float Tau = __uint_as_float(t[RT_TAU]);
             const float *st = staged + tile * A.n_trials;
             float2 *out = A.out_trials ? reinterpret_cast<float2 *>(A.out_trials) + set * A.n_total + t0 : nullptr;
-            int n_up = 0;
+            int n_up = 0, n_miss = 0;
             unsigned long long sk = 0, sk2 = 0, sk_up = 0, sk2_up = 0;
             for (int j = lane; j < n_here; j += WAVE) {
-                const float sv = st[j];
+                const float sv = invalid ? __builtin_nanf("") : st[j];
+                const bool missing = sv != sv;                         // an invalid row's trial, or one a cap ended: (NaN, NaN)
                 const bool upper = (__float_as_uint(sv) >> 31) == 0u;
                 const float tot = __builtin_fabsf(sv);
                 const float rt = Tau + tot;
-                if (out) { float2 o; o.x = upper ? rt : -rt; o.y = upper ? 1.0f : 0.0f; out[j] = o; }
-                if (A.out_summary) {
+                if (out) { float2 o; o.x = missing ? sv : (upper ? rt : -rt); o.y = missing ? sv : (upper ? 1.0f : 0.0f); out[j] = o; }
+                if (missing) n_miss++;
+                else if (A.out_summary) {
                     const uint32_t tfix = (uint32_t)__builtin_fmaf(fminf(tot, 1024.0f), 65536.0f, 0.5f);
                     const unsigned long long sq = (unsigned long long)tfix * tfix;
                     sk += tfix; sk2 += sq;
@@ -358,11 +384,11 @@ __global__ __launch_bounds__(WAVE) void ratcliff_kernel(const RatArgs A)
                 }
             }
             if (A.out_summary) {
-                n_up = (int)wave_sum_dpp((uint32_t)n_up);
+                n_up = (int)wave_sum_dpp((uint32_t)n_up); n_miss = (int)wave_sum_dpp((uint32_t)n_miss);
                 sk = wave_sum_dpp64(sk); sk2 = wave_sum_dpp64(sk2); sk_up = wave_sum_dpp64(sk_up); sk2_up = wave_sum_dpp64(sk2_up);
                 if (lane == WAVE - 1) {                                // (the DPP reductions leave the totals in the last lane)
                     unsigned long long *q = reinterpret_cast<unsigned long long *>(rings + tile * 8);
-                    q[0] = sk | ((unsigned long long)n_up << 40);                                  // (sk < 2^36, n_up <= 512)
+                    q[0] = sk | ((unsigned long long)n_up << 40) | ((unsigned long long)n_miss << 52);    // (sk < 2^36; n_up, n_miss <= 512)
                     q[1] = sk2; q[2] = sk_up; q[3] = sk2_up;
                 }
             }
@@ -375,17 +401,17 @@ __global__ __launch_bounds__(WAVE) void ratcliff_kernel(const RatArgs A)
             const uint32_t *t = tbl + lane * RT_WORDS;
             const long long vset = v0 + lane;
             const long long set = TPS == 1 ? vset : vset / TPS;
-            const int n_here = (int)t[RT_NHERE];
+            const int n_here = (int)(t[RT_NHERE] & ~RT_INVALID);
             if (A.out_summary) {
                 const unsigned long long *q = reinterpret_cast<const unsigned long long *>(rings + lane * 8);
-                const int n_up = (int)(q[0] >> 40);
+                const int n_up = (int)(q[0] >> 40) & 0xfff, n_miss = (int)(q[0] >> 52), n_lo = n_here - n_up - n_miss;
                 const unsigned long long sk = q[0] & ((1ull << 40) - 1ull);
                 if (A.partials) {                                      // a tile of a split set: combine_partials_kernel adds the tiles up
                     unsigned long long *w = A.partials + vset * 5;
-                    w[0] = (unsigned long long)n_up | ((unsigned long long)(n_here - n_up) << 21);
+                    w[0] = (unsigned long long)n_up | ((unsigned long long)n_lo << 21) | ((unsigned long long)n_miss << 42);
                     w[1] = sk; w[2] = q[1]; w[3] = q[2]; w[4] = q[3];
                 } else {
-                    finalize_summary(A.out_summary + set * NDDM_SUMMARY_K, n_up, n_here - n_up, 0, sk, q[1], q[2], q[3], 0, 0, A.n_total,
+                    finalize_summary(A.out_summary + set * NDDM_SUMMARY_K, n_up, n_lo, n_miss, sk, q[1], q[2], q[3], 0, 0, A.n_total,
                                      1.52587890625e-05f, __uint_as_float(t[RT_TAU]));
                 }
             }

@@ -286,7 +286,15 @@ def simulratcliff(params, n_trials, seed=None, set_offset=None, fast=None, ext_s
     fast=False: the reference's series term by term, bit-equal to the test suite's CPU restatement (its section D).  fast (the default,
     as for simulate()): hardware log / exp / reciprocal and the same acceptance function from three terms of its series or of the
     series' Jacobi-dual form -- on 6e6 trials no response differs from fast=False and no response time by more than 1e-6 s
-    (profiles/r6_ratcliff_agreement.txt), at twice the rate."""
+    (profiles/r6_ratcliff_agreement.txt), at twice the rate.
+
+    What cannot be sampled is flagged, in both modes.  (1) Invalid rows: host arrays are refused here (ValueError: a non-finite column,
+    Alpha <= 0, Varsigma <= 0, Beta outside [0, 1], Eta < 0); a device tensor is not read on the host, and the kernel gives such a row
+    no trial -- every (y, acc) NaN, n_upper = n_lower = 0, n_missing = n_trials, moments NaN, 'ext' by its formula.  (2) The domain: the
+    rejection step cannot accept once G = r mu / (D pi) on a sphere passes about 7 (r = Alpha min(Beta, 1 - Beta), mu the trial's
+    drift, D = Varsigma^2 / 2); a trial that runs into the sampler's loop caps there is (NaN, NaN) and counted in n_missing, never
+    returned as a number.  G below about 6 -- the generator's box (alpha_not_scaled.py:66-72) but for the drift's far tail at its
+    extreme corner -- is in range; check summary[:, 2] (or isnan(y)) on rows beyond it."""
     torch = require_device()
     L = _lib.lib()
     dev = _device(device)

@@ -234,11 +234,18 @@ int nddm_alpha_not_scaled_simulate(const float *params, int64_t B, int32_t n_tri
  *                from three terms of its series or of the series' Jacobi-dual form, whichever converges: no loop; on 6e6 trials no
  *                response differs from the exact mode's and no response time by more than 1e-6 s); nothing else
  *   out_trials   [B, n_trials, 2] = (y, acc): y = +-(Tau + decision time) signed by the response, acc = (sign + 1) / 2  (:98-102)
- *   out_summary  [B, NDDM_SUMMARY_K] from integer sums of the decision time in 2^-16 s (n_missing is 0: the sampler has no timeout)
+ *   out_summary  [B, NDDM_SUMMARY_K] from integer sums of the decision time in 2^-16 s; n_missing counts the trials written (NaN, NaN)
  *   out_extdata  [B]: (ext_mode == 0 ? Alpha[b] : 1) + ext_sigma * N(0,1)  (alpha_not_scaled.py:103-106), as nddm_alpha_not_scaled_simulate
  * Randomness: per-trial drift = auxiliary normal 0 of (set, trial) -- the draw the Euler-Maruyama form uses -- and stream 3 of the
  * trial for the sampler's uniforms; a pure function of (seed, set_offset + row, trial).  Sets of more than 512 trials are tiled
- * (same bits); with summaries such a launch cannot be captured into a hipGraph. */
+ * (same bits); with summaries such a launch cannot be captured into a hipGraph.
+ * What cannot be sampled is flagged, never returned as a number (both modes):
+ *   1. an invalid row -- a non-finite column, Alpha <= 0, Varsigma <= 0, Beta outside [0, 1], Eta < 0 -- is not simulated: every trial
+ *      (NaN, NaN), n_upper = n_lower = 0, n_missing = n_trials, moments NaN; out_extdata keeps its formula.  Beta = 0 or 1 is valid;
+ *   2. a trial that reaches one of the sampler's loop caps (4096 rejection attempts on a sphere, 4096 spheres) is (NaN, NaN) and counted
+ *      in n_missing only.  The rejection step cannot accept once G = r mu / (D pi) passes ~7 (r = Alpha min(Beta, 1 - Beta), mu the
+ *      trial's drift, D = Varsigma^2 / 2): rows with G below ~6 -- the generator's box but for its extreme corner's drift tail -- are
+ *      the domain; Nu 5, Alpha 2, Varsigma .6 (G 8.8) loses 62 % of its trials.  csrc/nddm_ratcliff.h, DESIGN.md 5.5. */
 int nddm_simulratcliff(const float *params, int64_t B, int32_t n_trials, uint64_t seed, uint64_t set_offset, uint32_t flags,
                        float ext_sigma, int32_t ext_mode, float *out_trials, float *out_summary, float *out_extdata, void *stream);
 
