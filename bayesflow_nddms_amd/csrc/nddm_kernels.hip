@@ -35,7 +35,7 @@
 // This translation unit: nddm_rng.h (random stream) -> nddm_sim.h (sim_kernel) -> nddm_prepass.h (pre-pass, combine, prior)
 // -> nddm_ratcliff.h (the exact first-passage sampler) -> nddm_wiener.h (the Wiener first-passage log-likelihood) -> nddm_wiener_cdf.h (its distribution function) -> nddm_wiener_quantile.h (its quantile function)
 // -> nddm_wiener_grad.h (the log-likelihood's value and gradient) -> nddm_wiener_marginal.h (the single-trial model's marginal log-likelihood)
-// -> below: the host side (launch slots, sizing, dispatch) and the extern "C" entry points.
+// -> below: the host side (launch slots, sizing, dispatch; the Wiener family's one launch path, wiener_launch) and the extern "C" entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -698,6 +698,75 @@ static int simulate(int model, const float *params, const float *bounds, int64_t
     return rc;
 }
 
+// ---- the Wiener family's launch path: nddm_wiener_log_likelihood, _cdf, _quantile, _log_likelihood_grad, _marginal_log_likelihood ----------
+// The five entry points differ in their kernels, their outputs and their words; the checks, the layout rule and the launch are here, once.
+// What an entry point says about itself (every message but model_msg and launch_msg ends in fail's unused %s):
+struct WienerEntry {
+    const char *model_msg;                                              // %s: the model number
+    const char *flags_msg, *shape_msg, *null_in_msg, *null_out_msg;
+    const char *launch_msg;                                             // %s: the HIP error
+    int rows;                                                           // rows per workgroup: WIENER_ROWS, WIENER_GRAD_ROWS or WMARG_ROWS
+};
+
+// the words most of the entry points share
+constexpr const char *WIENER_SHAPE_MSG = "R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required%s";
+constexpr const char *WIENER_NULL_IN_MSG = "params or data is NULL%s", *WIENER_NULL_OUT_MSG = "no output buffer given%s";
+
+static bool wiener_closed_form(int32_t model) { return model == NDDM_BASIC_DDM_DC || model == NDDM_ALPHA_NOT_SCALED; }
+
+// The argument checks in their one order: model, flags, shape, R / 16, the empty batch (*empty: NDDM_OK and nothing to launch, before any
+// pointer is looked at), NULL inputs, NULL outputs, the stream.  The entry point evaluates the conditions that are its own.
+static int wiener_checks(const WienerEntry &E, int32_t model, bool model_ok, bool flags_ok, int64_t R, int64_t S, int32_t n, bool in_ok,
+                         bool out_ok, hipStream_t st, bool *empty)
+{
+    *empty = false;
+    if (!model_ok) {
+        char m[16];
+        snprintf(m, sizeof m, "%d", (int)model);
+        return fail(NDDM_ERR_PARAM, E.model_msg, m);
+    }
+    if (!flags_ok) return fail(NDDM_ERR_PARAM, E.flags_msg);
+    if (R < 0 || n <= 0 || S <= 0 || R % S != 0) return fail(NDDM_ERR_SHAPE, E.shape_msg);
+    if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
+    if (R == 0) { *empty = true; return NDDM_OK; }
+    if (!in_ok) return fail(NDDM_ERR_NULL, E.null_in_msg);
+    if (!out_ok) return fail(NDDM_ERR_NULL, E.null_out_msg);
+    return check_stream(st);
+}
+
+// The layout and the grid of S rows per data set, R rows, `rows` per workgroup.  Broadcast layout (a data set scored by many rows: S >=
+// WIENER_ROWS, whatever `rows` is): a workgroup's rows share its data set, staged in LDS, `chunks` workgroups to a data set; otherwise
+// (paired layout) each row reads its own trials.  The values do not depend on the choice (nddm_wiener.h: wiener_block_rows).
+static int wiener_plan(int64_t S, int64_t R, int rows, bool *staged, long long *chunks, long long *blocks)
+{
+    *staged = S >= WIENER_ROWS;
+    *chunks = (S + rows - 1) / rows;
+    *blocks = *staged ? (R / S) * *chunks : (R + rows - 1) / rows;
+    if (*blocks < (1ll << 31)) return NDDM_OK;
+    char r[16];
+    snprintf(r, sizeof r, "%d", rows);
+    return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / %s must be < 2^31)", r);
+}
+
+// Checks, plan and the one kernel launch (no scratch memory, nothing to synchronise: capturable like a plain kernel).  A: the entry point's
+// outputs and extra fields; kernels: its model's {paired, staged} instantiations.
+template <class Args>
+static int wiener_launch(const WienerEntry &E, int32_t model, bool model_ok, bool flags_ok, const float *params, const float *data, int64_t R,
+                         int64_t S, int32_t n, bool in_ok, bool out_ok, void *stream, Args A, void (*const kernels[2])(Args))
+{
+    g_err[0] = 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    bool empty, staged;
+    if (const int rc = wiener_checks(E, model, model_ok, flags_ok, R, S, n, in_ok, out_ok, st, &empty)) return rc;
+    if (empty) return NDDM_OK;
+    A.params = params; A.data = data; A.R = R; A.S = S; A.N = n; A.P = nddm_model_nparams(model);
+    long long blocks;
+    if (const int rc = wiener_plan(S, R, E.rows, &staged, &A.chunks, &blocks)) return rc;
+    hipLaunchKernelGGL(kernels[staged], dim3((unsigned)blocks), dim3(256), 0, st, A);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? NDDM_OK : fail(NDDM_ERR_HIP, E.launch_msg, hipGetErrorString(e));
+}
+
 }  // namespace nddm
 
 // ================================================================================================
@@ -1027,220 +1096,89 @@ int nddm_simulratcliff(const float *params, int64_t B, int32_t n_trials, uint64_
     return rc;
 }
 
-/* the Wiener first-passage log-likelihood (JAGS dwiener / Stan wiener_lpdf of the reference's likelihood-based fits): csrc/nddm_wiener.h.
- * One kernel launch, no scratch memory, nothing to synchronise: capturable like a plain kernel. */
+/* ---- the Wiener family.  Each entry point states its models, its flags, which pointers may be NULL, its outputs and extra fields, its
+ * kernels and the words of its messages; nddm::wiener_launch makes the checks (one order and one set of status codes for all five),
+ * chooses the layout and makes the one launch. ---- */
+
+/* the Wiener first-passage log-likelihood (JAGS dwiener / Stan wiener_lpdf of the reference's likelihood-based fits): csrc/nddm_wiener.h */
 int nddm_wiener_log_likelihood(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data, int32_t n_trials,
                                uint32_t flags, float *out_trial_logp, double *out_loglik, void *stream)
 {
     using namespace nddm;
-    g_err[0] = 0;
-    if (model != NDDM_BASIC_DDM_DC && model != NDDM_ALPHA_NOT_SCALED) {
-        char m[16];
-        snprintf(m, sizeof m, "%d", (int)model);
-        return fail(NDDM_ERR_PARAM, "nddm_wiener_log_likelihood: model %s has no closed-form likelihood here (NDDM_BASIC_DDM_DC and "
-                                    "NDDM_ALPHA_NOT_SCALED only)", m);
-    }
-    if (flags != 0u) return fail(NDDM_ERR_PARAM, "nddm_wiener_log_likelihood: flags must be 0 (reserved)%s");
-    if (R < 0 || n_trials <= 0 || draws_per_dataset <= 0 || R % draws_per_dataset != 0)
-        return fail(NDDM_ERR_SHAPE, "R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required%s");
-    if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
-    if (R == 0) return NDDM_OK;
-    if (!params || !data) return fail(NDDM_ERR_NULL, "params or data is NULL%s");
-    if (!out_trial_logp && !out_loglik) return fail(NDDM_ERR_NULL, "no output buffer given%s");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (const int rc = check_stream(st)) return rc;
+    static const WienerEntry E = {"nddm_wiener_log_likelihood: model %s has no closed-form likelihood here (NDDM_BASIC_DDM_DC and "
+                                  "NDDM_ALPHA_NOT_SCALED only)", "nddm_wiener_log_likelihood: flags must be 0 (reserved)%s", WIENER_SHAPE_MSG,
+                                  WIENER_NULL_IN_MSG, WIENER_NULL_OUT_MSG, "wiener kernel launch failed: %s", WIENER_ROWS};
+    static void (*const K[2][2])(WienerArgs) = {{wiener_kernel<NDDM_BASIC_DDM_DC, false>, wiener_kernel<NDDM_BASIC_DDM_DC, true>},
+                                                {wiener_kernel<NDDM_ALPHA_NOT_SCALED, false>, wiener_kernel<NDDM_ALPHA_NOT_SCALED, true>}};
     WienerArgs A;
-    A.params = params; A.data = data; A.out_trial = out_trial_logp; A.out_sum = out_loglik;
-    A.R = R; A.S = draws_per_dataset; A.N = n_trials; A.P = nddm_model_nparams(model);
-    // broadcast layout (a data set scored by many rows): a workgroup's rows share its data set, staged in LDS; otherwise each row
-    // reads its own trials.  The values do not depend on the choice (nddm_wiener.h).
-    const bool staged = draws_per_dataset >= WIENER_ROWS;
-    A.chunks = (draws_per_dataset + WIENER_ROWS - 1) / WIENER_ROWS;
-    const long long blocks = staged ? (R / draws_per_dataset) * A.chunks : (R + WIENER_ROWS - 1) / WIENER_ROWS;
-    if (blocks >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / 16 must be < 2^31)%s");
-    const dim3 grid((unsigned)blocks), block(256);
-    if (model == NDDM_BASIC_DDM_DC) {
-        if (staged) hipLaunchKernelGGL((wiener_kernel<NDDM_BASIC_DDM_DC, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((wiener_kernel<NDDM_BASIC_DDM_DC, false>), grid, block, 0, st, A);
-    } else {
-        if (staged) hipLaunchKernelGGL((wiener_kernel<NDDM_ALPHA_NOT_SCALED, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((wiener_kernel<NDDM_ALPHA_NOT_SCALED, false>), grid, block, 0, st, A);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener kernel launch failed: %s", hipGetErrorString(e));
-    return NDDM_OK;
+    A.out_trial = out_trial_logp; A.out_sum = out_loglik;
+    return wiener_launch(E, model, wiener_closed_form(model), flags == 0u, params, data, R, draws_per_dataset, n_trials, params && data,
+                         out_trial_logp || out_loglik, stream, A, K[model == NDDM_ALPHA_NOT_SCALED]);
 }
 
-/* the Wiener first-passage distribution function (RWiener / HDDM pwiener) and P(upper): csrc/nddm_wiener_cdf.h.  The argument checks, their
- * order and their status codes are nddm_wiener_log_likelihood's.  One kernel launch, no scratch memory: capturable like a plain kernel. */
+/* the Wiener first-passage distribution function (RWiener / HDDM pwiener) and P(upper): csrc/nddm_wiener_cdf.h.  data is read only for out_cdf. */
 int nddm_wiener_cdf(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data, int32_t n_trials,
                     uint32_t flags, float *out_cdf, float *out_p_upper, void *stream)
 {
     using namespace nddm;
-    g_err[0] = 0;
-    if (model != NDDM_BASIC_DDM_DC && model != NDDM_ALPHA_NOT_SCALED) {
-        char m[16];
-        snprintf(m, sizeof m, "%d", (int)model);
-        return fail(NDDM_ERR_PARAM, "nddm_wiener_cdf: model %s has no closed-form distribution function here (NDDM_BASIC_DDM_DC and "
-                                    "NDDM_ALPHA_NOT_SCALED only)", m);
-    }
-    if (flags != 0u) return fail(NDDM_ERR_PARAM, "nddm_wiener_cdf: flags must be 0 (reserved)%s");
-    if (R < 0 || n_trials <= 0 || draws_per_dataset <= 0 || R % draws_per_dataset != 0)
-        return fail(NDDM_ERR_SHAPE, "R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required%s");
-    if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
-    if (R == 0) return NDDM_OK;
-    if (!params || (!data && out_cdf)) return fail(NDDM_ERR_NULL, "params or data is NULL%s");
-    if (!out_cdf && !out_p_upper) return fail(NDDM_ERR_NULL, "no output buffer given%s");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (const int rc = check_stream(st)) return rc;
+    static const WienerEntry E = {"nddm_wiener_cdf: model %s has no closed-form distribution function here (NDDM_BASIC_DDM_DC and "
+                                  "NDDM_ALPHA_NOT_SCALED only)", "nddm_wiener_cdf: flags must be 0 (reserved)%s", WIENER_SHAPE_MSG,
+                                  WIENER_NULL_IN_MSG, WIENER_NULL_OUT_MSG, "wiener cdf kernel launch failed: %s", WIENER_ROWS};
+    static void (*const K[2][2])(WienerCdfArgs) = {{wiener_cdf_kernel<NDDM_BASIC_DDM_DC, false>, wiener_cdf_kernel<NDDM_BASIC_DDM_DC, true>},
+                                                   {wiener_cdf_kernel<NDDM_ALPHA_NOT_SCALED, false>, wiener_cdf_kernel<NDDM_ALPHA_NOT_SCALED, true>}};
     WienerCdfArgs A;
-    A.params = params; A.data = data; A.out_cdf = out_cdf; A.out_p_upper = out_p_upper;
-    A.R = R; A.S = draws_per_dataset; A.N = n_trials; A.P = nddm_model_nparams(model);
-    // the layouts of nddm_wiener_log_likelihood; the values do not depend on the choice (nddm_wiener_cdf.h)
-    const bool staged = draws_per_dataset >= WIENER_ROWS;
-    A.chunks = (draws_per_dataset + WIENER_ROWS - 1) / WIENER_ROWS;
-    const long long blocks = staged ? (R / draws_per_dataset) * A.chunks : (R + WIENER_ROWS - 1) / WIENER_ROWS;
-    if (blocks >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / 16 must be < 2^31)%s");
-    const dim3 grid((unsigned)blocks), block(256);
-    if (model == NDDM_BASIC_DDM_DC) {
-        if (staged) hipLaunchKernelGGL((wiener_cdf_kernel<NDDM_BASIC_DDM_DC, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((wiener_cdf_kernel<NDDM_BASIC_DDM_DC, false>), grid, block, 0, st, A);
-    } else {
-        if (staged) hipLaunchKernelGGL((wiener_cdf_kernel<NDDM_ALPHA_NOT_SCALED, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((wiener_cdf_kernel<NDDM_ALPHA_NOT_SCALED, false>), grid, block, 0, st, A);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener cdf kernel launch failed: %s", hipGetErrorString(e));
-    return NDDM_OK;
+    A.out_cdf = out_cdf; A.out_p_upper = out_p_upper;
+    return wiener_launch(E, model, wiener_closed_form(model), flags == 0u, params, data, R, draws_per_dataset, n_trials,
+                         params && (data || !out_cdf), out_cdf || out_p_upper, stream, A, K[model == NDDM_ALPHA_NOT_SCALED]);
 }
 
-/* the Wiener first-passage quantile function (RWiener / HDDM qwiener), the inverse of nddm_wiener_cdf: csrc/nddm_wiener_quantile.h.  The
- * argument checks, their order and their status codes are nddm_wiener_cdf's.  One kernel launch, no scratch memory: capturable like a
- * plain kernel. */
+/* the Wiener first-passage quantile function (RWiener / HDDM qwiener), the inverse of nddm_wiener_cdf: csrc/nddm_wiener_quantile.h */
 int nddm_wiener_quantile(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *probs, int32_t n,
                          uint32_t flags, float *out_q, void *stream)
 {
     using namespace nddm;
-    g_err[0] = 0;
-    if (model != NDDM_BASIC_DDM_DC && model != NDDM_ALPHA_NOT_SCALED) {
-        char m[16];
-        snprintf(m, sizeof m, "%d", (int)model);
-        return fail(NDDM_ERR_PARAM, "nddm_wiener_quantile: model %s has no closed-form distribution function here (NDDM_BASIC_DDM_DC and "
-                                    "NDDM_ALPHA_NOT_SCALED only)", m);
-    }
-    if ((flags & ~NDDM_QUANTILE_CONDITIONAL) != 0u)
-        return fail(NDDM_ERR_PARAM, "nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL%s");
-    if (R < 0 || n <= 0 || draws_per_dataset <= 0 || R % draws_per_dataset != 0)
-        return fail(NDDM_ERR_SHAPE, "R >= 0, n > 0 and draws_per_dataset > 0 dividing R are required%s");
-    if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
-    if (R == 0) return NDDM_OK;
-    if (!params || !probs) return fail(NDDM_ERR_NULL, "params or probs is NULL%s");
-    if (!out_q) return fail(NDDM_ERR_NULL, "no output buffer given%s");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (const int rc = check_stream(st)) return rc;
+    static const WienerEntry E = {"nddm_wiener_quantile: model %s has no closed-form distribution function here (NDDM_BASIC_DDM_DC and "
+                                  "NDDM_ALPHA_NOT_SCALED only)", "nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL%s",
+                                  "R >= 0, n > 0 and draws_per_dataset > 0 dividing R are required%s", "params or probs is NULL%s",
+                                  WIENER_NULL_OUT_MSG, "wiener quantile kernel launch failed: %s", WIENER_ROWS};
+    static void (*const K[2][2])(WienerQuantileArgs) = {
+        {wiener_quantile_kernel<NDDM_BASIC_DDM_DC, false>, wiener_quantile_kernel<NDDM_BASIC_DDM_DC, true>},
+        {wiener_quantile_kernel<NDDM_ALPHA_NOT_SCALED, false>, wiener_quantile_kernel<NDDM_ALPHA_NOT_SCALED, true>}};
     WienerQuantileArgs A;
-    A.params = params; A.probs = probs; A.out_q = out_q;
-    A.R = R; A.S = draws_per_dataset; A.N = n; A.P = nddm_model_nparams(model); A.flags = flags;
-    // the layouts of nddm_wiener_cdf; the values do not depend on the choice (nddm_wiener_quantile.h)
-    const bool staged = draws_per_dataset >= WIENER_ROWS;
-    A.chunks = (draws_per_dataset + WIENER_ROWS - 1) / WIENER_ROWS;
-    const long long blocks = staged ? (R / draws_per_dataset) * A.chunks : (R + WIENER_ROWS - 1) / WIENER_ROWS;
-    if (blocks >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / 16 must be < 2^31)%s");
-    const dim3 grid((unsigned)blocks), block(256);
-    if (model == NDDM_BASIC_DDM_DC) {
-        if (staged) hipLaunchKernelGGL((wiener_quantile_kernel<NDDM_BASIC_DDM_DC, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((wiener_quantile_kernel<NDDM_BASIC_DDM_DC, false>), grid, block, 0, st, A);
-    } else {
-        if (staged) hipLaunchKernelGGL((wiener_quantile_kernel<NDDM_ALPHA_NOT_SCALED, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((wiener_quantile_kernel<NDDM_ALPHA_NOT_SCALED, false>), grid, block, 0, st, A);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener quantile kernel launch failed: %s", hipGetErrorString(e));
-    return NDDM_OK;
+    A.out_q = out_q; A.flags = flags;
+    return wiener_launch(E, model, wiener_closed_form(model), (flags & ~NDDM_QUANTILE_CONDITIONAL) == 0u, params, probs, R, draws_per_dataset, n,
+                         params && probs, out_q != nullptr, stream, A, K[model == NDDM_ALPHA_NOT_SCALED]);
 }
 
-/* the value and the gradient of the Wiener first-passage log-likelihood in one launch: csrc/nddm_wiener_grad.h.  The argument checks, their
- * order and their status codes are nddm_wiener_log_likelihood's.  One kernel launch, no scratch memory: capturable like a plain kernel. */
+/* the value and the gradient of the Wiener first-passage log-likelihood in one launch: csrc/nddm_wiener_grad.h.  out_loglik may be NULL. */
 int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
                                     int32_t n_trials, uint32_t flags, double *out_loglik, double *out_grad, void *stream)
 {
     using namespace nddm;
-    g_err[0] = 0;
-    if (model != NDDM_BASIC_DDM_DC && model != NDDM_ALPHA_NOT_SCALED) {
-        char m[16];
-        snprintf(m, sizeof m, "%d", (int)model);
-        return fail(NDDM_ERR_PARAM, "nddm_wiener_log_likelihood_grad: model %s has no closed-form likelihood here (NDDM_BASIC_DDM_DC and "
-                                    "NDDM_ALPHA_NOT_SCALED only)", m);
-    }
-    if (flags != 0u) return fail(NDDM_ERR_PARAM, "nddm_wiener_log_likelihood_grad: flags must be 0 (reserved)%s");
-    if (R < 0 || n_trials <= 0 || draws_per_dataset <= 0 || R % draws_per_dataset != 0)
-        return fail(NDDM_ERR_SHAPE, "R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required%s");
-    if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
-    if (R == 0) return NDDM_OK;
-    if (!params || !data) return fail(NDDM_ERR_NULL, "params or data is NULL%s");
-    if (!out_grad) return fail(NDDM_ERR_NULL, "out_grad is NULL%s");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (const int rc = check_stream(st)) return rc;
+    static const WienerEntry E = {"nddm_wiener_log_likelihood_grad: model %s has no closed-form likelihood here (NDDM_BASIC_DDM_DC and "
+                                  "NDDM_ALPHA_NOT_SCALED only)", "nddm_wiener_log_likelihood_grad: flags must be 0 (reserved)%s", WIENER_SHAPE_MSG,
+                                  WIENER_NULL_IN_MSG, "out_grad is NULL%s", "wiener gradient kernel launch failed: %s", WIENER_GRAD_ROWS};
+    static void (*const K[2][2])(WienerGradArgs) = {{wiener_grad_kernel<NDDM_BASIC_DDM_DC, false>, wiener_grad_kernel<NDDM_BASIC_DDM_DC, true>},
+                                                    {wiener_grad_kernel<NDDM_ALPHA_NOT_SCALED, false>, wiener_grad_kernel<NDDM_ALPHA_NOT_SCALED, true>}};
     WienerGradArgs A;
-    A.params = params; A.data = data; A.out_sum = out_loglik; A.out_grad = out_grad;
-    A.R = R; A.S = draws_per_dataset; A.N = n_trials; A.P = nddm_model_nparams(model);
-    // the layouts and the dispatch rule of nddm_wiener_log_likelihood, a workgroup owning WIENER_GRAD_ROWS rows; the values do not depend
-    // on the choice (nddm_wiener_grad.h)
-    const bool staged = draws_per_dataset >= WIENER_ROWS;
-    A.chunks = (draws_per_dataset + WIENER_GRAD_ROWS - 1) / WIENER_GRAD_ROWS;
-    const long long blocks = staged ? (R / draws_per_dataset) * A.chunks : (R + WIENER_GRAD_ROWS - 1) / WIENER_GRAD_ROWS;
-    if (blocks >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / 4 must be < 2^31)%s");
-    const dim3 grid((unsigned)blocks), block(256);
-    if (model == NDDM_BASIC_DDM_DC) {
-        if (staged) hipLaunchKernelGGL((wiener_grad_kernel<NDDM_BASIC_DDM_DC, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((wiener_grad_kernel<NDDM_BASIC_DDM_DC, false>), grid, block, 0, st, A);
-    } else {
-        if (staged) hipLaunchKernelGGL((wiener_grad_kernel<NDDM_ALPHA_NOT_SCALED, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((wiener_grad_kernel<NDDM_ALPHA_NOT_SCALED, false>), grid, block, 0, st, A);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener gradient kernel launch failed: %s", hipGetErrorString(e));
-    return NDDM_OK;
+    A.out_sum = out_loglik; A.out_grad = out_grad;
+    return wiener_launch(E, model, wiener_closed_form(model), flags == 0u, params, data, R, draws_per_dataset, n_trials, params && data,
+                         out_grad != nullptr, stream, A, K[model == NDDM_ALPHA_NOT_SCALED]);
 }
 
-/* the single-trial model's marginal log-likelihood (the latent per-trial boundary integrated out by quadrature): csrc/nddm_wiener_marginal.h.
- * The argument checks, their order and their status codes are nddm_wiener_log_likelihood's.  One kernel launch, no scratch memory: capturable
- * like a plain kernel. */
+/* the single-trial model's marginal log-likelihood (the latent per-trial boundary integrated out by quadrature): csrc/nddm_wiener_marginal.h */
 int nddm_wiener_marginal_log_likelihood(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
                                         int32_t n_trials, float t_censor, uint32_t flags, float *out_trial, double *out_sum, void *stream)
 {
     using namespace nddm;
-    g_err[0] = 0;
-    if (model != NDDM_SINGLE_TRIAL) {
-        char m[16];
-        snprintf(m, sizeof m, "%d", (int)model);
-        return fail(NDDM_ERR_PARAM, "nddm_wiener_marginal_log_likelihood: model %s has no marginal likelihood here (NDDM_SINGLE_TRIAL only)", m);
-    }
-    if (flags != 0u) return fail(NDDM_ERR_PARAM, "nddm_wiener_marginal_log_likelihood: flags must be 0 (reserved)%s");
-    if (R < 0 || n_trials <= 0 || draws_per_dataset <= 0 || R % draws_per_dataset != 0)
-        return fail(NDDM_ERR_SHAPE, "R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required%s");
-    if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
-    if (R == 0) return NDDM_OK;
-    if (!params || !data) return fail(NDDM_ERR_NULL, "params or data is NULL%s");
-    if (!out_trial && !out_sum) return fail(NDDM_ERR_NULL, "no output buffer given%s");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (const int rc = check_stream(st)) return rc;
+    static const WienerEntry E = {"nddm_wiener_marginal_log_likelihood: model %s has no marginal likelihood here (NDDM_SINGLE_TRIAL only)",
+                                  "nddm_wiener_marginal_log_likelihood: flags must be 0 (reserved)%s", WIENER_SHAPE_MSG, WIENER_NULL_IN_MSG,
+                                  WIENER_NULL_OUT_MSG, "wiener marginal kernel launch failed: %s", WMARG_ROWS};
+    static void (*const K[2])(WienerMarginalArgs) = {wiener_marginal_kernel<false>, wiener_marginal_kernel<true>};
     WienerMarginalArgs A;
-    A.params = params; A.data = data; A.out_trial = out_trial; A.out_sum = out_sum;
-    A.R = R; A.S = draws_per_dataset; A.N = n_trials; A.P = nddm_model_nparams(model);
-    A.t_censor = t_censor;
-    // the layouts and the dispatch rule of nddm_wiener_log_likelihood, a workgroup owning WMARG_ROWS rows; the values do not depend on the
-    // choice (nddm_wiener_marginal.h)
-    const bool staged = draws_per_dataset >= WIENER_ROWS;
-    A.chunks = (draws_per_dataset + WMARG_ROWS - 1) / WMARG_ROWS;
-    const long long blocks = staged ? (R / draws_per_dataset) * A.chunks : (R + WMARG_ROWS - 1) / WMARG_ROWS;
-    if (blocks >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / 4 must be < 2^31)%s");
-    const dim3 grid((unsigned)blocks), block(256);
-    if (staged) hipLaunchKernelGGL((wiener_marginal_kernel<true>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((wiener_marginal_kernel<false>), grid, block, 0, st, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(NDDM_ERR_HIP, "wiener marginal kernel launch failed: %s", hipGetErrorString(e));
-    return NDDM_OK;
+    A.out_trial = out_trial; A.out_sum = out_sum; A.t_censor = t_censor;
+    return wiener_launch(E, model, model == NDDM_SINGLE_TRIAL, flags == 0u, params, data, R, draws_per_dataset, n_trials, params && data,
+                         out_trial || out_sum, stream, A, K);
 }
 
 static int draw_prior_impl(int32_t model, int64_t B, uint64_t seed, uint64_t set_offset, const uint64_t *set_offset_dev,

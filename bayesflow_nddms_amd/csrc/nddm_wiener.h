@@ -52,6 +52,10 @@ constexpr int WIENER_ROWS = 4 * WIENER_RPW;     // rows per workgroup (4 waves)
 constexpr int WIENER_TILE = 1024;               // trials staged in LDS at a time (8 KB); a constant, not a knob
 constexpr int WIENER_SURV_TERMS = 64;
 
+// The five *Args structs of the family begin alike -- params, data, two outputs (one for the quantile), R, S, chunks, N, P -- and
+// wiener_launch (nddm_kernels.hip) fills those fields by name.  They are not derived from one base: that would move the outputs behind
+// the common fields in the kernel-argument segment, the prologues would fetch their arguments differently, and the forward kernel's
+// broadcast launch measured 0.3 % slower, outside the spread of the layout below (profiles/r15_wiener_refactor_ab.txt).
 struct WienerArgs {
     const float *params;        // [R, P]
     const float *data;          // [D, N, 2]
@@ -274,6 +278,29 @@ __device__ __forceinline__ float wiener_trial(const WienerRow &c, float x0, floa
 
 __device__ __forceinline__ float wiener_bcast(float x, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), k)); }
 
+// The rows [rbase, rend) of workgroup blockIdx.x, ROWS at most.  STAGED (broadcast layout): the `chunks` workgroups of a data set split
+// its S rows, the last one ragged; else (paired layout) the workgroups split all R rows.  The one mapping of the family's kernels.
+template <bool STAGED, int ROWS>
+__device__ __forceinline__ void wiener_block_rows(long long R, long long S, long long chunks, long long &rbase, long long &rend)
+{
+    if (STAGED) {
+        const long long d = blockIdx.x / chunks, ch = blockIdx.x - d * chunks;
+        rbase = d * S + ch * ROWS;
+        rend = rbase + ROWS < (d + 1) * S ? rbase + ROWS : (d + 1) * S;
+    } else {
+        rbase = (long long)blockIdx.x * ROWS;
+        rend = rbase + ROWS < R ? rbase + ROWS : R;
+    }
+}
+
+// The workgroup's 256 threads stage nt <= WIENER_TILE pairs of its data set in LDS; every thread of the workgroup calls it
+__device__ __forceinline__ void wiener_stage_tile(float2 *tile, const float *src, int nt)
+{
+    __syncthreads();                                                   // the previous tile is no longer read
+    for (int j = threadIdx.x; j < nt; j += 256) tile[j] = make_float2(src[2 * j], src[2 * j + 1]);
+    __syncthreads();
+}
+
 // STAGED: the workgroup's rows all score one data set, read from LDS (broadcast layout); else every row reads its own (paired layout)
 template <int MODEL, bool STAGED>
 __global__ __launch_bounds__(256) void wiener_kernel(WienerArgs A)
@@ -281,14 +308,7 @@ __global__ __launch_bounds__(256) void wiener_kernel(WienerArgs A)
     __shared__ float2 tile[STAGED ? WIENER_TILE : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long rbase, rend;
-    if (STAGED) {
-        const long long d = blockIdx.x / A.chunks, ch = blockIdx.x - d * A.chunks;
-        rbase = d * A.S + ch * WIENER_ROWS;
-        rend = rbase + WIENER_ROWS < (d + 1) * A.S ? rbase + WIENER_ROWS : (d + 1) * A.S;
-    } else {
-        rbase = (long long)blockIdx.x * WIENER_ROWS;
-        rend = rbase + WIENER_ROWS < A.R ? rbase + WIENER_ROWS : A.R;
-    }
+    wiener_block_rows<STAGED, WIENER_ROWS>(A.R, A.S, A.chunks, rbase, rend);
     const long long wrow0 = rbase + wave;                               // the wave's rows: wrow0 + 4k, k < WIENER_RPW
     const bool has_rows = wrow0 < rend;
     if (!STAGED && !has_rows) return;
@@ -306,12 +326,7 @@ __global__ __launch_bounds__(256) void wiener_kernel(WienerArgs A)
     static_assert(WIENER_RPW == 4, "one partial sum per row of the wave");
     for (int t0 = 0; t0 < A.N; t0 += WIENER_TILE) {
         const int nt = A.N - t0 < WIENER_TILE ? A.N - t0 : WIENER_TILE;
-        if (STAGED) {
-            const float *src = A.data + ((rbase / A.S) * (long long)A.N + t0) * 2;
-            __syncthreads();                                           // the previous tile is no longer read
-            for (int j = threadIdx.x; j < nt; j += 256) tile[j] = make_float2(src[2 * j], src[2 * j + 1]);
-            __syncthreads();
-        }
+        if (STAGED) wiener_stage_tile(tile, A.data + ((rbase / A.S) * (long long)A.N + t0) * 2, nt);
 #pragma nounroll
         for (int k = 0; k < WIENER_RPW; ++k) {
             const long long row = wrow0 + 4ll * k;

@@ -195,15 +195,9 @@ __global__ __launch_bounds__(256) void wiener_cdf_kernel(WienerCdfArgs A)
     __shared__ WienerCdfSide sides[WIENER_ROWS][2];
     __shared__ WienerRow wrows[MODEL == NDDM_BASIC_DDM_DC ? WIENER_ROWS : 1];     // (the timeouts' survival series)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long rbase, rend;
-    if (STAGED) {
-        const long long d = blockIdx.x / A.chunks, ch = blockIdx.x - d * A.chunks;
-        rbase = d * A.S + ch * WIENER_ROWS;
-        rend = rbase + WIENER_ROWS < (d + 1) * A.S ? rbase + WIENER_ROWS : (d + 1) * A.S;
-    } else {
-        rbase = (long long)blockIdx.x * WIENER_ROWS;
-        rend = rbase + WIENER_ROWS < A.R ? rbase + WIENER_ROWS : A.R;
-    }
+    long long rb, re;
+    wiener_block_rows<STAGED, WIENER_ROWS>(A.R, A.S, A.chunks, rb, re);
+    const long long rbase = rb, rend = re;                              // (constants from here on: the p_upper guard below compiles to one scalar instruction more otherwise)
     // thread 2k + side works out the constants of row k on that boundary (rows past the end repeat the last one and are never read)
     if (threadIdx.x < 2 * WIENER_ROWS) {
         const int lr = threadIdx.x >> 1, side = threadIdx.x & 1;
@@ -220,12 +214,7 @@ __global__ __launch_bounds__(256) void wiener_cdf_kernel(WienerCdfArgs A)
     const long long wrow0 = rbase + wave;                               // the wave's rows: wrow0 + 4k, k < WIENER_RPW
     for (int t0 = 0; t0 < A.N; t0 += WIENER_TILE) {
         const int nt = A.N - t0 < WIENER_TILE ? A.N - t0 : WIENER_TILE;
-        if (STAGED) {
-            const float *src = A.data + ((rbase / A.S) * (long long)A.N + t0) * 2;
-            __syncthreads();                                           // the previous tile is no longer read
-            for (int j = threadIdx.x; j < nt; j += 256) tile[j] = make_float2(src[2 * j], src[2 * j + 1]);
-            __syncthreads();
-        }
+        if (STAGED) wiener_stage_tile(tile, A.data + ((rbase / A.S) * (long long)A.N + t0) * 2, nt);
 #pragma nounroll
         for (int k = 0; k < WIENER_RPW; ++k) {
             const long long row = wrow0 + 4ll * k;

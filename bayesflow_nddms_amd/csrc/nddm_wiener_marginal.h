@@ -232,14 +232,7 @@ __global__ __launch_bounds__(256) void wiener_marginal_kernel(WienerMarginalArgs
     static_assert(WMARG_RPW == 1, "a wave holds one row");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long rbase, rend;
-    if (STAGED) {
-        const long long d = blockIdx.x / G.chunks, ch = blockIdx.x - d * G.chunks;
-        rbase = d * G.S + ch * WMARG_ROWS;
-        rend = rbase + WMARG_ROWS < (d + 1) * G.S ? rbase + WMARG_ROWS : (d + 1) * G.S;
-    } else {
-        rbase = (long long)blockIdx.x * WMARG_ROWS;
-        rend = rbase + WMARG_ROWS < G.R ? rbase + WMARG_ROWS : G.R;
-    }
+    wiener_block_rows<STAGED, WMARG_ROWS>(G.R, G.S, G.chunks, rbase, rend);
     const bool has_row = rbase + wave < rend;                           // wave-uniform
     if (!STAGED && !has_row) return;
     const long long row = has_row ? rbase + wave : rend - 1;            // (a wave without a row still stages: it repeats the last one's constants)
@@ -262,10 +255,7 @@ __global__ __launch_bounds__(256) void wiener_marginal_kernel(WienerMarginalArgs
     for (int t0 = 0; t0 < G.N; t0 += WIENER_TILE) {
         const int nt = G.N - t0 < WIENER_TILE ? G.N - t0 : WIENER_TILE;
         if (STAGED) {
-            const float *src = G.data + ((rbase / G.S) * (long long)G.N + t0) * 2;
-            __syncthreads();                                           // the previous tile is no longer read
-            for (int j = threadIdx.x; j < nt; j += 256) tile[j] = make_float2(src[2 * j], src[2 * j + 1]);
-            __syncthreads();
+            wiener_stage_tile(tile, G.data + ((rbase / G.S) * (long long)G.N + t0) * 2, nt);
             if (!has_row) continue;
         }
         const float *src = STAGED ? nullptr : G.data + ((row / G.S) * (long long)G.N + t0) * 2;

@@ -45,7 +45,7 @@ constexpr float WQUANT_TOL_ABS = 5.9604644775390625e-08f;       // 2^-24
 
 struct WienerQuantileArgs {
     const float *params;        // [R, P]
-    const float *probs;         // [D, N, 2] = (p, boundary code)
+    const float *data;          // [D, N, 2] = (p, boundary code): the requests `probs`, under the name wiener_launch fills
     float *out_q;               // [R, N]
     long long R, S;             // rows, rows per request set
     long long chunks;           // workgroups per request set (broadcast layout)
@@ -157,14 +157,7 @@ __global__ __launch_bounds__(256) void wiener_quantile_kernel(WienerQuantileArgs
     __shared__ WienerQuantileSide qsides[WIENER_ROWS][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long rbase, rend;
-    if (STAGED) {
-        const long long d = blockIdx.x / A.chunks, ch = blockIdx.x - d * A.chunks;
-        rbase = d * A.S + ch * WIENER_ROWS;
-        rend = rbase + WIENER_ROWS < (d + 1) * A.S ? rbase + WIENER_ROWS : (d + 1) * A.S;
-    } else {
-        rbase = (long long)blockIdx.x * WIENER_ROWS;
-        rend = rbase + WIENER_ROWS < A.R ? rbase + WIENER_ROWS : A.R;
-    }
+    wiener_block_rows<STAGED, WIENER_ROWS>(A.R, A.S, A.chunks, rbase, rend);
     // thread 2k + side works out the constants of row k on that boundary (rows past the end repeat the last one and are never read)
     if (threadIdx.x < 2 * WIENER_ROWS) {
         const int lr = threadIdx.x >> 1, side = threadIdx.x & 1;
@@ -179,18 +172,13 @@ __global__ __launch_bounds__(256) void wiener_quantile_kernel(WienerQuantileArgs
     const long long wrow0 = rbase + wave;                               // the wave's rows: wrow0 + 4k, k < WIENER_RPW
     for (int t0 = 0; t0 < A.N; t0 += WIENER_TILE) {
         const int nt = A.N - t0 < WIENER_TILE ? A.N - t0 : WIENER_TILE;
-        if (STAGED) {
-            const float *src = A.probs + ((rbase / A.S) * (long long)A.N + t0) * 2;
-            __syncthreads();                                           // the previous tile is no longer read
-            for (int j = threadIdx.x; j < nt; j += 256) tile[j] = make_float2(src[2 * j], src[2 * j + 1]);
-            __syncthreads();
-        }
+        if (STAGED) wiener_stage_tile(tile, A.data + ((rbase / A.S) * (long long)A.N + t0) * 2, nt);
 #pragma nounroll
         for (int k = 0; k < WIENER_RPW; ++k) {
             const long long row = wrow0 + 4ll * k;
             if (row >= rend) break;                                     // wave-uniform
             const int lr = wave + 4 * k;
-            const float *src = STAGED ? nullptr : A.probs + ((row / A.S) * (long long)A.N + t0) * 2;
+            const float *src = STAGED ? nullptr : A.data + ((row / A.S) * (long long)A.N + t0) * 2;
             float *dst = A.out_q + row * (long long)A.N + t0;
             for (int i = lane; i < nt; i += 64) {
                 float x0, x1;

@@ -389,6 +389,29 @@ def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs, r
     return S, p_rows, d_rows, p_np, d_np, R
 
 
+def _wiener_device_call(checked, params, data, device, outputs, call):
+    """The device half wiener_log_likelihood, wiener_marginal_log_likelihood, wiener_log_likelihood_grad, wiener_cdf and wiener_quantile
+    share.  `checked`: what _wiener_host_checks returned; `outputs`: (result key, wanted?, shape with None for n_trials, torch dtype's name)
+    in the result's order; `call(L, params pointer, data pointer, n_trials, {key: output pointer or None}, stream handle)` makes the one
+    library call and checks its status -- it is not called for an empty batch.  -> {key: device tensor} of the wanted outputs."""
+    S, p_rows, d_rows, p_np, d_np, R = checked
+    torch = require_device()
+    L = _lib.lib()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        p_dev = _device_rows(params, p_np, dev, *p_rows)
+        d_dev = _device_rows(data, d_np, dev, *d_rows)
+        N = int(d_dev.shape[1])
+        res = {key: torch.empty(tuple(N if n is None else n for n in shape), dtype=getattr(torch, dtype), device=dev)
+               for key, wanted, shape, dtype in outputs if wanted}
+        if R > 0:
+            st = torch.cuda.current_stream(dev)
+            call(L, _ptr(p_dev), _ptr(d_dev), N, {key: _ptr(res.get(key)) for key, _, _, _ in outputs}, st.cuda_stream)
+            p_dev.record_stream(st)
+            d_dev.record_stream(st)
+    return res
+
+
 def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=False, want_sum=True, device=None):
     """Log-likelihood of observed trials under the Wiener first-passage density (include/nddm.h: nddm_wiener_log_likelihood), one
     kernel launch: the density JAGS dwiener / Stan wiener_lpdf evaluate in the reference's likelihood-based fits.
@@ -398,28 +421,11 @@ def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=Fa
     in the simulator's output format, R = D * draws_per_dataset, row r scored against data set r // draws_per_dataset.
     Returns a dict of device tensors: 'loglik' float64 [R] (want_sum) and 'trial_logp' float32 [R, n_trials] (per_trial).
     Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN."""
-    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, data, draws_per_dataset, "likelihood",
-                                                           {"per_trial": per_trial, "want_sum": want_sum})
-    torch = require_device()
-    L = _lib.lib()
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        p_dev = _device_rows(params, p_np, dev, *p_rows)
-        d_dev = _device_rows(data, d_np, dev, *d_rows)
-        N = int(d_dev.shape[1])
-        out_t = torch.empty((R, N), dtype=torch.float32, device=dev) if per_trial else None
-        out_s = torch.empty((R,), dtype=torch.float64, device=dev) if want_sum else None
-        if R > 0:
-            st = torch.cuda.current_stream(dev)
-            _lib.check(L.nddm_wiener_log_likelihood(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, 0, _ptr(out_t), _ptr(out_s), st.cuda_stream))
-            p_dev.record_stream(st)
-            d_dev.record_stream(st)
-    res = {}
-    if out_s is not None:
-        res["loglik"] = out_s
-    if out_t is not None:
-        res["trial_logp"] = out_t
-    return res
+    checked = _wiener_host_checks(model, params, data, draws_per_dataset, "likelihood", {"per_trial": per_trial, "want_sum": want_sum})
+    S, R = checked[0], checked[-1]
+    return _wiener_device_call(
+        checked, params, data, device, [("loglik", want_sum, (R,), "float64"), ("trial_logp", per_trial, (R, None), "float32")],
+        lambda L, p, d, N, o, st: _lib.check(L.nddm_wiener_log_likelihood(int(model), p, R, S, d, N, 0, o["trial_logp"], o["loglik"], st)))
 
 
 def wiener_marginal_log_likelihood(model, params, data, draws_per_dataset=1, t_censor=None, per_trial=False, want_sum=True, device=None):
@@ -431,32 +437,16 @@ def wiener_marginal_log_likelihood(model, params, data, draws_per_dataset=1, t_c
     decision time a timeout (choicert == 0) is censored at, the simulator's max_steps * dt; None: timeouts give NaN.
     Returns a dict of device tensors: 'loglik' float64 [R] (want_sum) and 'trial_logp' float32 [R, n_trials] (per_trial).
     Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN."""
-    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, data, draws_per_dataset, "marginal likelihood",
-                                                           {"per_trial": per_trial, "want_sum": want_sum}, marginal=True)
+    checked = _wiener_host_checks(model, params, data, draws_per_dataset, "marginal likelihood", {"per_trial": per_trial, "want_sum": want_sum},
+                                  marginal=True)
+    S, R = checked[0], checked[-1]
     tc = 0.0 if t_censor is None else float(t_censor)
     if math.isnan(tc) or tc < 0:
         raise ValueError("t_censor must be >= 0 (or None: timeouts then give NaN)")
-    torch = require_device()
-    L = _lib.lib()
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        p_dev = _device_rows(params, p_np, dev, *p_rows)
-        d_dev = _device_rows(data, d_np, dev, *d_rows)
-        N = int(d_dev.shape[1])
-        out_t = torch.empty((R, N), dtype=torch.float32, device=dev) if per_trial else None
-        out_s = torch.empty((R,), dtype=torch.float64, device=dev) if want_sum else None
-        if R > 0:
-            st = torch.cuda.current_stream(dev)
-            _lib.check(L.nddm_wiener_marginal_log_likelihood(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, tc, 0, _ptr(out_t), _ptr(out_s),
-                                                             st.cuda_stream))
-            p_dev.record_stream(st)
-            d_dev.record_stream(st)
-    res = {}
-    if out_s is not None:
-        res["loglik"] = out_s
-    if out_t is not None:
-        res["trial_logp"] = out_t
-    return res
+    return _wiener_device_call(
+        checked, params, data, device, [("loglik", want_sum, (R,), "float64"), ("trial_logp", per_trial, (R, None), "float32")],
+        lambda L, p, d, N, o, st: _lib.check(L.nddm_wiener_marginal_log_likelihood(int(model), p, R, S, d, N, tc, 0, o["trial_logp"], o["loglik"],
+                                                                                   st)))
 
 
 # kernel launches wiener_log_likelihood_grad has made in this process (tests count them: one per forward plus backward)
@@ -478,23 +468,15 @@ def wiener_log_likelihood_grad(model, params, data, draws_per_dataset=1, device=
     NOT IMPLEMENTED: the gradient of basic_ddm_dc's censored timeouts (choice 0).  They are scored in 'loglik' exactly as
     wiener_log_likelihood scores them, and the row's gradient is NaN in every column -- never a partial gradient.
     Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are."""
-    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, data, draws_per_dataset, "likelihood", {"grad": True})
-    torch = require_device()
-    L = _lib.lib()
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        p_dev = _device_rows(params, p_np, dev, *p_rows)
-        d_dev = _device_rows(data, d_np, dev, *d_rows)
-        N = int(d_dev.shape[1])
-        out_s = torch.empty((R,), dtype=torch.float64, device=dev)
-        out_g = torch.empty((R, NPARAMS[model]), dtype=torch.float64, device=dev)
-        if R > 0:
-            st = torch.cuda.current_stream(dev)
-            _lib.check(L.nddm_wiener_log_likelihood_grad(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, 0, _ptr(out_s), _ptr(out_g), st.cuda_stream))
-            _WIENER_GRAD_LAUNCHES[0] += 1
-            p_dev.record_stream(st)
-            d_dev.record_stream(st)
-    return {"loglik": out_s, "grad": out_g}
+    checked = _wiener_host_checks(model, params, data, draws_per_dataset, "likelihood", {"grad": True})
+    S, R = checked[0], checked[-1]
+
+    def call(L, p, d, N, o, st):
+        _lib.check(L.nddm_wiener_log_likelihood_grad(int(model), p, R, S, d, N, 0, o["loglik"], o["grad"], st))
+        _WIENER_GRAD_LAUNCHES[0] += 1
+
+    return _wiener_device_call(checked, params, data, device,
+                               [("loglik", True, (R,), "float64"), ("grad", True, (R, NPARAMS[model]), "float64")], call)
 
 
 def wiener_cdf(model, params, data, draws_per_dataset=1, want_cdf=True, want_p_upper=True, device=None):
@@ -505,28 +487,12 @@ def wiener_cdf(model, params, data, draws_per_dataset=1, want_cdf=True, want_p_u
     defective distribution function -- 0 for rt <= tau; a basic_ddm_dc timeout (choice 0) gives P(T <= rt - tau) over both boundaries,
     an alpha_not_scaled y == 0 NaN -- and 'p_upper' [R] (want_p_upper) = P(upper boundary), drift variability integrated out.
     Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN."""
-    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, data, draws_per_dataset, "distribution function",
-                                                           {"want_cdf": want_cdf, "want_p_upper": want_p_upper})
-    torch = require_device()
-    L = _lib.lib()
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        p_dev = _device_rows(params, p_np, dev, *p_rows)
-        d_dev = _device_rows(data, d_np, dev, *d_rows)
-        N = int(d_dev.shape[1])
-        out_c = torch.empty((R, N), dtype=torch.float32, device=dev) if want_cdf else None
-        out_p = torch.empty((R,), dtype=torch.float32, device=dev) if want_p_upper else None
-        if R > 0:
-            st = torch.cuda.current_stream(dev)
-            _lib.check(L.nddm_wiener_cdf(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, 0, _ptr(out_c), _ptr(out_p), st.cuda_stream))
-            p_dev.record_stream(st)
-            d_dev.record_stream(st)
-    res = {}
-    if out_c is not None:
-        res["cdf"] = out_c
-    if out_p is not None:
-        res["p_upper"] = out_p
-    return res
+    checked = _wiener_host_checks(model, params, data, draws_per_dataset, "distribution function",
+                                  {"want_cdf": want_cdf, "want_p_upper": want_p_upper})
+    S, R = checked[0], checked[-1]
+    return _wiener_device_call(
+        checked, params, data, device, [("cdf", want_cdf, (R, None), "float32"), ("p_upper", want_p_upper, (R,), "float32")],
+        lambda L, p, d, N, o, st: _lib.check(L.nddm_wiener_cdf(int(model), p, R, S, d, N, 0, o["cdf"], o["p_upper"], st)))
 
 
 def wiener_quantile(model, params, probs, draws_per_dataset=1, conditional=False, device=None):
@@ -539,23 +505,12 @@ def wiener_quantile(model, params, probs, draws_per_dataset=1, conditional=False
     boundary's responses, P(T <= rt - tau, boundary) = p P(boundary) (+inf at p = 1).  p = 0 gives tau.
     Returns {'quantile': float32 [R, n]} on the device.  Host arrays are shape- and range-checked (ValueError: code in {1, -1, 0}, p in
     [0, 1]); device tensors go to the kernel as they are, where an invalid row, a NaN or a negative p give NaN."""
-    S, p_rows, d_rows, p_np, d_np, R = _wiener_host_checks(model, params, probs, draws_per_dataset, "distribution function",
-                                                           {"quantile": True}, requests=True)
-    torch = require_device()
-    L = _lib.lib()
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        p_dev = _device_rows(params, p_np, dev, *p_rows)
-        d_dev = _device_rows(probs, d_np, dev, *d_rows)
-        N = int(d_dev.shape[1])
-        out = torch.empty((R, N), dtype=torch.float32, device=dev)
-        if R > 0:
-            st = torch.cuda.current_stream(dev)
-            _lib.check(L.nddm_wiener_quantile(int(model), _ptr(p_dev), R, S, _ptr(d_dev), N, _lib.QUANTILE_CONDITIONAL if conditional else 0,
-                                              _ptr(out), st.cuda_stream))
-            p_dev.record_stream(st)
-            d_dev.record_stream(st)
-    return {"quantile": out}
+    checked = _wiener_host_checks(model, params, probs, draws_per_dataset, "distribution function", {"quantile": True}, requests=True)
+    S, R = checked[0], checked[-1]
+    flags = _lib.QUANTILE_CONDITIONAL if conditional else 0
+    return _wiener_device_call(
+        checked, params, probs, device, [("quantile", True, (R, None), "float32")],
+        lambda L, p, d, N, o, st: _lib.check(L.nddm_wiener_quantile(int(model), p, R, S, d, N, flags, o["quantile"], st)))
 
 
 def decode_codes(model, codes, params, dt, out_trials=None):

@@ -220,3 +220,75 @@ def test_density_shapes_against_float64(basic, D, S, N):
     assert torch.allclose(ll, lp.double().sum(1), rtol=1e-12, atol=0)
     only = engine.wiener_log_likelihood(model, pd, dd, draws_per_dataset=S, per_trial=False)["loglik"]
     assert torch.equal(only.view(torch.int64), ll.view(torch.int64))
+
+
+MAPPING_S, MAPPING_D, MAPPING_N = (1, 5, 16, 17, 35), (1, 3), (1, 65, 1030)
+_MAPPING = {}
+
+
+def _mapping_inputs(model_name):
+    """Prior rows (distinct per row) and data sets (distinct per set) for the largest shape, drawn once per model; a shape takes the
+    leading rows, sets and trials.  -> (params [105, P], {kernel: data [3, 1030, 2]})."""
+    if model_name not in _MAPPING:
+        import prior_util
+        R, D, N = max(MAPPING_S) * max(MAPPING_D), max(MAPPING_D), max(MAPPING_N)
+        rng = np.random.default_rng(41)
+        rt32, up = rng.uniform(0.35, 3.0, (D, N)).astype(np.float32), rng.random((D, N)) < 0.5
+        req = np.stack([rng.uniform(0.001, 0.999, (D, N)), rng.integers(-1, 2, (D, N))], -1).astype(np.float32)      # (p, code) requests
+        if model_name == "single_trial":
+            p32 = prior_util.single_prior(R, 43)
+            d = np.stack([np.where(up, rt32, -rt32), np.abs(rng.normal(1.0, 0.5, (D, N)))], -1).astype(np.float32)   # (choicert, z1)
+            d[:, 4::5, 0] = 0.0                                          # timeouts, censored at t_censor
+            data = {"marginal": d}
+        else:
+            basic = model_name == "basic_ddm_dc"
+            p32 = (prior_util.basic_prior if basic else prior_util.alpha_ns_prior)(R, 42)
+            plain = _trials(basic, rt32, up)
+            cens = plain.copy()
+            if basic:
+                cens[:, 4::5, 1] = 0.0                                   # censored timeouts (their gradient is not implemented: NaN)
+            data = {"log_likelihood": cens, "cdf": cens, "grad": plain, "quantile": req}
+        for x in (p32,) + tuple(data.values()):
+            x.setflags(write=False)
+        _MAPPING[model_name] = (p32, data)
+    return _MAPPING[model_name]
+
+
+@pytest.mark.parametrize("kernel,model_name", [(k, m) for k in ("log_likelihood", "cdf", "quantile", "grad") for m in ("basic_ddm_dc", "alpha_not_scaled")]
+                         + [("marginal", "single_trial")])
+def test_row_mapping_is_one_for_every_kernel_and_layout(kernel, model_name):
+    """The kernels share one mapping of workgroups to rows (csrc/nddm_wiener.h: wiener_block_rows) and one tile staging.  At
+    draws_per_dataset 1, 5 (paired layout), 16 (the staging threshold), 17 and 35 (ragged last chunks of 16 and of 4 rows), 1 and 3 data
+    sets, and 1, 65 and 1030 trials (one lane, a second pass of the lane loop, a second LDS tile): every output of the [D * S]-row
+    launch has the bits of the same rows launched with draws_per_dataset = 1 against repeated data sets, and rows 0, S - 1, S and R - 1
+    have the values of a launch of that row alone (NaN where it has NaN)."""
+    torch = _torch()
+    from bayesflow_nddms_amd import engine
+    p_all, data = _mapping_inputs(model_name)
+    model = {"basic_ddm_dc": engine.BASIC_DDM_DC, "alpha_not_scaled": engine.ALPHA_NOT_SCALED, "single_trial": engine.SINGLE_TRIAL}[model_name]
+    call = {"log_likelihood": lambda p, d, s: engine.wiener_log_likelihood(model, p, d, draws_per_dataset=s, per_trial=True),
+            "cdf": lambda p, d, s: engine.wiener_cdf(model, p, d, draws_per_dataset=s),
+            "quantile": lambda p, d, s: engine.wiener_quantile(model, p, d, draws_per_dataset=s),
+            "grad": lambda p, d, s: engine.wiener_log_likelihood_grad(model, p, d, draws_per_dataset=s),
+            "marginal": lambda p, d, s: engine.wiener_marginal_log_likelihood(model, p, d, draws_per_dataset=s, t_censor=4.0, per_trial=True)}[kernel]
+    bits = lambda x: x.contiguous().view(torch.int64 if x.dtype == torch.float64 else torch.int32)
+    p_dev, d_dev = torch.as_tensor(p_all.copy()).cuda(), torch.as_tensor(data[kernel].copy()).cuda()
+    finite = 0
+    for D in MAPPING_D:
+        for S in MAPPING_S:
+            for N in MAPPING_N:
+                R = D * S
+                p, d = p_dev[:R], d_dev[:D, :N].contiguous()
+                full = call(p, d, S)
+                paired = call(p, d.repeat_interleave(S, 0), 1)
+                assert list(full) == list(paired)
+                for key, x in full.items():
+                    assert x.shape[0] == R and torch.equal(bits(x), bits(paired[key])), (D, S, N, key)
+                    finite += int(torch.isfinite(x).sum())
+                for r in sorted({0, S - 1, S if D > 1 else 0, R - 1}):
+                    one = call(p[r:r + 1], d[r // S:r // S + 1], 1)
+                    for key, x in full.items():
+                        a, b = x[r:r + 1], one[key]
+                        nan = torch.isnan(a)
+                        assert torch.equal(nan, torch.isnan(b)) and torch.equal(bits(a)[~nan], bits(b)[~nan]), (D, S, N, r, key)
+    assert finite > 0                                                   # (the comparisons are not of NaN alone)

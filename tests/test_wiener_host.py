@@ -165,22 +165,140 @@ def test_c_abi_exports_the_entry_and_validates_before_any_hip_call():
     assert "nddm_wiener_log_likelihood" in _lib.EXPORTS and hasattr(L, "nddm_wiener_log_likelihood")
     assert L.nddm_abi_version() == _lib.ABI_VERSION == 4
     d = ctypes.c_void_p(16)
-    f = L.nddm_wiener_log_likelihood
-    # model: only the two with a closed form, named in the message
-    assert f(1, d, 4, 1, d, 10, 0, d, None, None) == _lib.NDDM_ERR_PARAM and b"model 1" in L.nddm_last_error()
-    assert f(7, d, 4, 1, d, 10, 0, d, None, None) == _lib.NDDM_ERR_PARAM and b"model 7" in L.nddm_last_error()
-    assert f(0, d, 4, 1, d, 10, 1, d, None, None) == _lib.NDDM_ERR_PARAM                 # flags reserved
-    assert f(0, None, 4, 1, d, 10, 0, d, None, None) == _lib.NDDM_ERR_NULL
-    assert f(3, d, 4, 1, None, 10, 0, d, None, None) == _lib.NDDM_ERR_NULL
-    assert f(0, d, 4, 1, d, 10, 0, None, None, None) == _lib.NDDM_ERR_NULL               # both outputs NULL
-    assert f(0, d, -1, 1, d, 10, 0, d, None, None) == _lib.NDDM_ERR_SHAPE
-    assert f(0, d, 4, 1, d, 0, 0, d, None, None) == _lib.NDDM_ERR_SHAPE
-    assert f(0, d, 4, 0, d, 10, 0, d, None, None) == _lib.NDDM_ERR_SHAPE
-    assert f(0, d, 4, 3, d, 10, 0, d, None, None) == _lib.NDDM_ERR_SHAPE                 # 3 does not divide 4
-    assert f(0, d, 0, 1, d, 10, 0, d, None, None) == _lib.NDDM_OK                        # empty batch
+    f = L.nddm_wiener_log_likelihood                                    # (the argument checks: test_argument_contract_of_the_five_entry_points)
     import torch
     if not torch.cuda.is_available():
         assert f(0, d, 4, 2, d, 10, 0, d, None, None) in (_lib.NDDM_ERR_HIP, _lib.NDDM_ERR_NO_DEVICE)
+
+
+d = "d"                                                                 # stands for a non-NULL pointer (never dereferenced: every case ends before a launch)
+# (entry point, (model, params, R, draws_per_dataset, data, n, flags, *outputs), status, nddm_last_error() in full).  The texts are the
+# library's before the five entry points shared one launch path.  Per entry point: the cases its own file used to hold, then the order
+# of the checks -- model before flags, flags before shape, shape and R / 16 before the pointers (so 2^35 rows need no memory), the
+# empty batch before the pointers, inputs before outputs.
+ARGUMENT_CASES = [
+    ("log_likelihood", (1, d, 4, 1, d, 10, 0, d, None), "PARAM", 'nddm_wiener_log_likelihood: model 1 has no closed-form likelihood here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("log_likelihood", (7, d, 4, 1, d, 10, 0, d, None), "PARAM", 'nddm_wiener_log_likelihood: model 7 has no closed-form likelihood here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("log_likelihood", (0, d, 4, 1, d, 10, 1, d, None), "PARAM", 'nddm_wiener_log_likelihood: flags must be 0 (reserved)'),
+    ("log_likelihood", (0, None, 4, 1, d, 10, 0, d, None), "NULL", 'params or data is NULL'),
+    ("log_likelihood", (3, d, 4, 1, None, 10, 0, d, None), "NULL", 'params or data is NULL'),
+    ("log_likelihood", (0, d, 4, 1, d, 10, 0, None, None), "NULL", 'no output buffer given'),
+    ("log_likelihood", (0, d, -1, 1, d, 10, 0, d, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood", (0, d, 4, 1, d, 0, 0, d, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood", (0, d, 4, 0, d, 10, 0, d, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood", (0, d, 4, 3, d, 10, 0, d, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood", (0, d, 0, 1, d, 10, 0, d, None), "OK", ''),
+    ("log_likelihood", (1, None, -1, 0, None, 0, 1, None, None), "PARAM", 'nddm_wiener_log_likelihood: model 1 has no closed-form likelihood here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("log_likelihood", (0, None, -1, 0, None, 0, 1, None, None), "PARAM", 'nddm_wiener_log_likelihood: flags must be 0 (reserved)'),
+    ("log_likelihood", (0, d, 4, 3, d, 10, 1, d, None), "PARAM", 'nddm_wiener_log_likelihood: flags must be 0 (reserved)'),
+    ("log_likelihood", (0, None, 4, 3, None, 10, 0, None, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood", (0, None, 1 << 35, 1, None, 10, 0, None, None), "SHAPE", 'R / 16 must be < 2^31 per launch'),
+    ("log_likelihood", (0, None, 0, 1, None, 10, 0, None, None), "OK", ''),
+    ("log_likelihood", (0, None, 4, 1, d, 10, 0, None, None), "NULL", 'params or data is NULL'),
+    ("log_likelihood", (0, d, 4, 1, None, 10, 0, None, None), "NULL", 'params or data is NULL'),
+    ("cdf", (1, d, 4, 1, d, 10, 0, d, None), "PARAM", 'nddm_wiener_cdf: model 1 has no closed-form distribution function here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("cdf", (7, d, 4, 1, d, 10, 0, d, None), "PARAM", 'nddm_wiener_cdf: model 7 has no closed-form distribution function here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("cdf", (0, d, 4, 1, d, 10, 1, d, None), "PARAM", 'nddm_wiener_cdf: flags must be 0 (reserved)'),
+    ("cdf", (0, None, 4, 1, d, 10, 0, d, None), "NULL", 'params or data is NULL'),
+    ("cdf", (3, d, 4, 1, None, 10, 0, d, None), "NULL", 'params or data is NULL'),
+    ("cdf", (0, d, 4, 1, d, 10, 0, None, None), "NULL", 'no output buffer given'),
+    ("cdf", (0, d, 4, 1, None, 10, 0, None, None), "NULL", 'no output buffer given'),
+    ("cdf", (0, d, -1, 1, d, 10, 0, d, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("cdf", (0, d, 4, 1, d, 0, 0, d, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("cdf", (0, d, 4, 0, d, 10, 0, d, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("cdf", (0, d, 4, 3, d, 10, 0, d, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("cdf", (0, d, 0, 1, d, 10, 0, d, None), "OK", ''),
+    ("cdf", (0, d, 0, 1, None, 10, 0, None, d), "OK", ''),
+    ("cdf", (7, None, -1, 0, None, 0, 1, None, None), "PARAM", 'nddm_wiener_cdf: model 7 has no closed-form distribution function here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("cdf", (0, None, -1, 0, None, 0, 0, None, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("cdf", (1, None, -1, 0, None, 0, 1, None, None), "PARAM", 'nddm_wiener_cdf: model 1 has no closed-form distribution function here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("cdf", (0, None, -1, 0, None, 0, 1, None, None), "PARAM", 'nddm_wiener_cdf: flags must be 0 (reserved)'),
+    ("cdf", (0, d, 4, 3, d, 10, 1, d, None), "PARAM", 'nddm_wiener_cdf: flags must be 0 (reserved)'),
+    ("cdf", (0, None, 4, 3, None, 10, 0, None, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("cdf", (0, None, 1 << 35, 1, None, 10, 0, None, None), "SHAPE", 'R / 16 must be < 2^31 per launch'),
+    ("cdf", (0, None, 0, 1, None, 10, 0, None, None), "OK", ''),
+    ("cdf", (0, None, 4, 1, d, 10, 0, None, None), "NULL", 'params or data is NULL'),
+    ("quantile", (1, d, 4, 1, d, 10, 0, d), "PARAM", 'nddm_wiener_quantile: model 1 has no closed-form distribution function here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("quantile", (0, None, 4, 1, d, 10, 0, d), "NULL", 'params or probs is NULL'),
+    ("quantile", (0, d, 4, 1, None, 10, 0, d), "NULL", 'params or probs is NULL'),
+    ("quantile", (0, d, 4, 1, d, 10, 0, None), "NULL", 'no output buffer given'),
+    ("quantile", (0, d, 4, 3, d, 10, 0, d), "SHAPE", 'R >= 0, n > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("quantile", (0, d, 0, 1, d, 10, 0, d), "OK", ''),
+    ("quantile", (0, None, 0, 1, None, 10, 1, None), "OK", ''),
+    ("quantile", (0, d, 4, 1, d, 10, 2, d), "PARAM", 'nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL'),
+    ("quantile", (0, d, 4, 1, d, 10, 3, d), "PARAM", 'nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL'),
+    ("quantile", (0, d, 4, 1, d, 10, 4, d), "PARAM", 'nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL'),
+    ("quantile", (0, d, 4, 1, d, 10, 2147483648, d), "PARAM", 'nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL'),
+    ("quantile", (0, d, 4, 1, d, 10, 4294967294, d), "PARAM", 'nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL'),
+    ("quantile", (0, d, 0, 1, d, 10, 1, d), "OK", ''),
+    ("quantile", (7, None, -1, 0, None, 0, 2, None), "PARAM", 'nddm_wiener_quantile: model 7 has no closed-form distribution function here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("quantile", (0, None, -1, 0, None, 0, 2, None), "PARAM", 'nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL'),
+    ("quantile", (0, None, -1, 0, None, 0, 1, None), "SHAPE", 'R >= 0, n > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("quantile", (0, None, 4, 1, None, 10, 1, None), "NULL", 'params or probs is NULL'),
+    ("quantile", (1, None, -1, 0, None, 0, 2, None), "PARAM", 'nddm_wiener_quantile: model 1 has no closed-form distribution function here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("quantile", (0, d, 4, 3, d, 10, 2, d), "PARAM", 'nddm_wiener_quantile: flags must be 0 or NDDM_QUANTILE_CONDITIONAL'),
+    ("quantile", (0, None, 4, 3, None, 10, 0, None), "SHAPE", 'R >= 0, n > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("quantile", (0, None, 1 << 35, 1, None, 10, 0, None), "SHAPE", 'R / 16 must be < 2^31 per launch'),
+    ("quantile", (0, None, 0, 1, None, 10, 0, None), "OK", ''),
+    ("quantile", (0, None, 4, 1, d, 10, 0, None), "NULL", 'params or probs is NULL'),
+    ("quantile", (0, d, 4, 1, None, 10, 0, None), "NULL", 'params or probs is NULL'),
+    ("log_likelihood_grad", (1, None, -1, 1, None, 0, 1, None, None), "PARAM", 'nddm_wiener_log_likelihood_grad: model 1 has no closed-form likelihood here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("log_likelihood_grad", (7, d, 4, 1, d, 10, 0, d, d), "PARAM", 'nddm_wiener_log_likelihood_grad: model 7 has no closed-form likelihood here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("log_likelihood_grad", (0, None, -1, 1, None, 0, 1, None, None), "PARAM", 'nddm_wiener_log_likelihood_grad: flags must be 0 (reserved)'),
+    ("log_likelihood_grad", (0, None, -1, 1, None, 10, 0, None, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood_grad", (0, d, 4, 1, d, 0, 0, d, d), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood_grad", (0, d, 4, 0, d, 10, 0, d, d), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood_grad", (3, d, 4, 3, d, 10, 0, d, d), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood_grad", (0, None, 0, 1, None, 10, 0, None, None), "OK", ''),
+    ("log_likelihood_grad", (0, None, 4, 1, d, 10, 0, d, d), "NULL", 'params or data is NULL'),
+    ("log_likelihood_grad", (3, d, 4, 1, None, 10, 0, d, d), "NULL", 'params or data is NULL'),
+    ("log_likelihood_grad", (0, d, 4, 1, d, 10, 0, d, None), "NULL", 'out_grad is NULL'),
+    ("log_likelihood_grad", (1, None, -1, 0, None, 0, 1, None, None), "PARAM", 'nddm_wiener_log_likelihood_grad: model 1 has no closed-form likelihood here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)'),
+    ("log_likelihood_grad", (0, None, -1, 0, None, 0, 1, None, None), "PARAM", 'nddm_wiener_log_likelihood_grad: flags must be 0 (reserved)'),
+    ("log_likelihood_grad", (0, d, 4, 3, d, 10, 1, d, d), "PARAM", 'nddm_wiener_log_likelihood_grad: flags must be 0 (reserved)'),
+    ("log_likelihood_grad", (0, None, 4, 3, None, 10, 0, None, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("log_likelihood_grad", (0, None, 1 << 35, 1, None, 10, 0, None, None), "SHAPE", 'R / 16 must be < 2^31 per launch'),
+    ("log_likelihood_grad", (0, None, 4, 1, d, 10, 0, None, None), "NULL", 'params or data is NULL'),
+    ("log_likelihood_grad", (0, d, 4, 1, None, 10, 0, None, None), "NULL", 'params or data is NULL'),
+    ("marginal_log_likelihood", (0, d, 4, 1, d, 10, 0, d, d), "PARAM", 'nddm_wiener_marginal_log_likelihood: model 0 has no marginal likelihood here (NDDM_SINGLE_TRIAL only)'),
+    ("marginal_log_likelihood", (2, d, 4, 1, d, 10, 0, d, d), "PARAM", 'nddm_wiener_marginal_log_likelihood: model 2 has no marginal likelihood here (NDDM_SINGLE_TRIAL only)'),
+    ("marginal_log_likelihood", (3, d, 4, 1, d, 10, 0, d, d), "PARAM", 'nddm_wiener_marginal_log_likelihood: model 3 has no marginal likelihood here (NDDM_SINGLE_TRIAL only)'),
+    ("marginal_log_likelihood", (4, d, 4, 1, d, 10, 0, d, d), "PARAM", 'nddm_wiener_marginal_log_likelihood: model 4 has no marginal likelihood here (NDDM_SINGLE_TRIAL only)'),
+    ("marginal_log_likelihood", (7, d, 4, 1, d, 10, 0, d, d), "PARAM", 'nddm_wiener_marginal_log_likelihood: model 7 has no marginal likelihood here (NDDM_SINGLE_TRIAL only)'),
+    ("marginal_log_likelihood", (1, None, -1, 1, None, 0, 1, None, None), "PARAM", 'nddm_wiener_marginal_log_likelihood: flags must be 0 (reserved)'),
+    ("marginal_log_likelihood", (1, None, -1, 1, None, 10, 0, None, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("marginal_log_likelihood", (1, d, 4, 1, d, 0, 0, d, d), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("marginal_log_likelihood", (1, d, 4, 0, d, 10, 0, d, d), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("marginal_log_likelihood", (1, d, 4, 3, d, 10, 0, d, d), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("marginal_log_likelihood", (1, None, 0, 1, None, 10, 0, None, None), "OK", ''),
+    ("marginal_log_likelihood", (1, None, 4, 1, d, 10, 0, d, d), "NULL", 'params or data is NULL'),
+    ("marginal_log_likelihood", (1, d, 4, 1, None, 10, 0, d, d), "NULL", 'params or data is NULL'),
+    ("marginal_log_likelihood", (1, d, 4, 1, d, 10, 0, None, None), "NULL", 'no output buffer given'),
+    ("marginal_log_likelihood", (0, None, -1, 0, None, 0, 1, None, None), "PARAM", 'nddm_wiener_marginal_log_likelihood: model 0 has no marginal likelihood here (NDDM_SINGLE_TRIAL only)'),
+    ("marginal_log_likelihood", (1, None, -1, 0, None, 0, 1, None, None), "PARAM", 'nddm_wiener_marginal_log_likelihood: flags must be 0 (reserved)'),
+    ("marginal_log_likelihood", (1, d, 4, 3, d, 10, 1, d, d), "PARAM", 'nddm_wiener_marginal_log_likelihood: flags must be 0 (reserved)'),
+    ("marginal_log_likelihood", (1, None, 4, 3, None, 10, 0, None, None), "SHAPE", 'R >= 0, n_trials > 0 and draws_per_dataset > 0 dividing R are required'),
+    ("marginal_log_likelihood", (1, None, 1 << 35, 1, None, 10, 0, None, None), "SHAPE", 'R / 16 must be < 2^31 per launch'),
+    ("marginal_log_likelihood", (1, None, 4, 1, d, 10, 0, None, None), "NULL", 'params or data is NULL'),
+    ("marginal_log_likelihood", (1, d, 4, 1, None, 10, 0, None, None), "NULL", 'params or data is NULL'),
+]
+
+
+@pytest.mark.parametrize("entry", ["log_likelihood", "cdf", "quantile", "log_likelihood_grad", "marginal_log_likelihood"])
+def test_argument_contract_of_the_five_entry_points(entry):
+    """Every status code, which check wins when two are violated, and the text of nddm_last_error(), for the shared launch path of the
+    Wiener family (csrc/nddm_kernels.hip: wiener_launch).  No case reaches a HIP call."""
+    from bayesflow_nddms_amd import _lib
+    L = _lib.lib()
+    f = getattr(L, "nddm_wiener_" + entry)
+    status = {"OK": _lib.NDDM_OK, "NULL": _lib.NDDM_ERR_NULL, "SHAPE": _lib.NDDM_ERR_SHAPE, "PARAM": _lib.NDDM_ERR_PARAM}
+    mine = [c for c in ARGUMENT_CASES if c[0] == entry]
+    assert mine
+    for _, args, want, text in mine:
+        model, params, R, S, data, n, flags, *outs = [ctypes.c_void_p(16) if a is d else a for a in args]
+        t_censor = (4.0,) if entry == "marginal_log_likelihood" else ()
+        assert f(model, params, R, S, data, n, *t_censor, flags, *outs, None) == status[want], args
+        assert L.nddm_last_error().decode() == text, args
 
 
 def test_python_adapter_checks_host_inputs():

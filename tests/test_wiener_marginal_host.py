@@ -198,19 +198,7 @@ def test_c_abi_exports_the_entry_and_validates_before_any_hip_call():
     f = L.nddm_wiener_marginal_log_likelihood
     assert f.argtypes[6] is ctypes.c_float and f.argtypes[7] is ctypes.c_uint32 and len(f.argtypes) == 11
     d = ctypes.c_void_p(16)
-    # the order of nddm_wiener_log_likelihood: model, flags, shapes, the empty batch, NULLs
-    for model in (0, 2, 3, 4, 7):
-        assert f(model, d, 4, 1, d, 10, 4.0, 0, d, d, None) == _lib.NDDM_ERR_PARAM
-        assert b"model %d" % model in L.nddm_last_error() and b"NDDM_SINGLE_TRIAL only" in L.nddm_last_error()
-    assert f(1, None, -1, 1, None, 0, 4.0, 1, None, None, None) == _lib.NDDM_ERR_PARAM and b"flags" in L.nddm_last_error()
-    assert f(1, None, -1, 1, None, 10, 4.0, 0, None, None, None) == _lib.NDDM_ERR_SHAPE
-    assert f(1, d, 4, 1, d, 0, 4.0, 0, d, d, None) == _lib.NDDM_ERR_SHAPE
-    assert f(1, d, 4, 0, d, 10, 4.0, 0, d, d, None) == _lib.NDDM_ERR_SHAPE
-    assert f(1, d, 4, 3, d, 10, 4.0, 0, d, d, None) == _lib.NDDM_ERR_SHAPE               # 3 does not divide 4
-    assert f(1, None, 0, 1, None, 10, 4.0, 0, None, None, None) == _lib.NDDM_OK          # empty batch, before the NULL checks
-    assert f(1, None, 4, 1, d, 10, 4.0, 0, d, d, None) == _lib.NDDM_ERR_NULL
-    assert f(1, d, 4, 1, None, 10, 4.0, 0, d, d, None) == _lib.NDDM_ERR_NULL
-    assert f(1, d, 4, 1, d, 10, 4.0, 0, None, None, None) == _lib.NDDM_ERR_NULL
+    # (the argument checks and their order: tests/test_wiener_host.py, test_argument_contract_of_the_five_entry_points)
     hdr = open(os.path.join(ROOT, "include", "nddm.h")).read()
     assert "int nddm_wiener_marginal_log_likelihood(" in hdr and "#define NDDM_ABI_VERSION 4" in hdr
     assert "NDDM_SINGLE_TRIAL_ALT (a latent diffusion coefficient) is OUT OF" in hdr
