@@ -6,13 +6,13 @@ Host code is Python; the arithmetic lives in hand-written HIP kernels for gfx950
 """
 from .engine import (ALPHA_NOT_SCALED, BASIC_DDM_DC, EXPLICIT_BOUNDARY, SINGLE_TRIAL, SINGLE_TRIAL_ALT, SUMMARY_COLS,
                      SUMMARY_K, GLOBAL_STREAM, StreamState, draw_prior_device, seed, simulate, wiener_cdf, wiener_log_likelihood, wiener_log_likelihood_grad,
-                     wiener_marginal_log_likelihood, wiener_quantile)
-from .likelihood import (diffusion_lpdf, dwiener_logpdf, pwiener, qwiener, single_trial_logpdf, wiener_choice_prob, wiener_loglik,
-                         wiener_rt_quantiles)
+                     wiener_marginal_log_likelihood, wiener_marginal_log_likelihood_grad, wiener_quantile)
+from .likelihood import (diffusion_lpdf, dwiener_logpdf, pwiener, qwiener, single_trial_loglik, single_trial_logpdf, wiener_choice_prob,
+                         wiener_loglik, wiener_rt_quantiles)
 
 __all__ = ["ALPHA_NOT_SCALED", "BASIC_DDM_DC", "EXPLICIT_BOUNDARY", "SINGLE_TRIAL", "SINGLE_TRIAL_ALT",
            "SUMMARY_COLS", "SUMMARY_K", "GLOBAL_STREAM", "StreamState", "draw_prior_device", "seed", "simulate",
            "wiener_log_likelihood", "dwiener_logpdf", "diffusion_lpdf", "wiener_cdf", "pwiener", "wiener_choice_prob",
            "wiener_quantile", "qwiener", "wiener_rt_quantiles", "wiener_log_likelihood_grad", "wiener_loglik",
-           "wiener_marginal_log_likelihood", "single_trial_logpdf"]
+           "wiener_marginal_log_likelihood", "single_trial_logpdf", "wiener_marginal_log_likelihood_grad", "single_trial_loglik"]
 __version__ = "0.1.0"

@@ -41,6 +41,7 @@ def _declare(L):
     L.nddm_wiener_cdf.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_uint32, fp, fp, vp]
     L.nddm_wiener_log_likelihood_grad.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_uint32, fp, fp, vp]
     L.nddm_wiener_marginal_log_likelihood.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_float, c.c_uint32, fp, fp, vp]
+    L.nddm_wiener_marginal_log_likelihood_grad.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_float, c.c_uint32, fp, fp, vp]
     L.nddm_wiener_quantile.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_uint32, fp, vp]
     L.nddm_simulate.argtypes = [c.c_int32, fp, fp] + common + [c.c_float, c.c_int32, fp, fp, fp, vp]
     L.nddm_simulate_indirect.argtypes = [c.c_int32, fp, fp] + common[:-1] + [fp, c.c_uint32, c.c_float, c.c_int32, fp, fp, fp, vp]
@@ -70,7 +71,7 @@ EXPORTS = [
     "nddm_simulate_indirect", "nddm_draw_prior_indirect", "nddm_source_hash", "nddm_simulate_codes", "nddm_decode_codes",
     "nddm_graph_arena_create", "nddm_graph_arena_bind", "nddm_graph_arena_info", "nddm_graph_arena_release", "nddm_build_info",
     "nddm_simulratcliff", "nddm_wiener_log_likelihood", "nddm_wiener_cdf", "nddm_wiener_quantile",
-    "nddm_wiener_log_likelihood_grad", "nddm_wiener_marginal_log_likelihood",
+    "nddm_wiener_log_likelihood_grad", "nddm_wiener_marginal_log_likelihood", "nddm_wiener_marginal_log_likelihood_grad",
 ]
 
 

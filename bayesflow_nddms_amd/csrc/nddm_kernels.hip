@@ -34,7 +34,7 @@
 //
 // This translation unit: nddm_rng.h (random stream) -> nddm_sim.h (sim_kernel) -> nddm_prepass.h (pre-pass, combine, prior)
 // -> nddm_ratcliff.h (the exact first-passage sampler) -> nddm_wiener.h (the Wiener first-passage log-likelihood) -> nddm_wiener_cdf.h (its distribution function) -> nddm_wiener_quantile.h (its quantile function)
-// -> nddm_wiener_grad.h (the log-likelihood's value and gradient) -> nddm_wiener_marginal.h (the single-trial model's marginal log-likelihood)
+// -> nddm_wiener_grad.h (the log-likelihood's value and gradient) -> nddm_wiener_marginal.h (the single-trial model's marginal log-likelihood) -> nddm_wiener_marginal_grad.h (its value and gradient)
 // -> below: the host side (launch slots, sizing, dispatch; the Wiener family's one launch path, wiener_launch) and the extern "C" entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -55,6 +55,7 @@
 #include "nddm_wiener_cdf.h"
 #include "nddm_wiener_grad.h"
 #include "nddm_wiener_marginal.h"
+#include "nddm_wiener_marginal_grad.h"
 #include "nddm_wiener_quantile.h"
 
 namespace nddm {
@@ -698,14 +699,14 @@ static int simulate(int model, const float *params, const float *bounds, int64_t
     return rc;
 }
 
-// ---- the Wiener family's launch path: nddm_wiener_log_likelihood, _cdf, _quantile, _log_likelihood_grad, _marginal_log_likelihood ----------
-// The five entry points differ in their kernels, their outputs and their words; the checks, the layout rule and the launch are here, once.
+// ---- the Wiener family's launch path: nddm_wiener_log_likelihood, _cdf, _quantile, _log_likelihood_grad, _marginal_log_likelihood[_grad] ---
+// The six entry points differ in their kernels, their outputs and their words; the checks, the layout rule and the launch are here, once.
 // What an entry point says about itself (every message but model_msg and launch_msg ends in fail's unused %s):
 struct WienerEntry {
     const char *model_msg;                                              // %s: the model number
     const char *flags_msg, *shape_msg, *null_in_msg, *null_out_msg;
     const char *launch_msg;                                             // %s: the HIP error
-    int rows;                                                           // rows per workgroup: WIENER_ROWS, WIENER_GRAD_ROWS or WMARG_ROWS
+    int rows;                                                           // rows per workgroup: WIENER_ROWS, WIENER_GRAD_ROWS, WMARG_ROWS or WMGRAD_ROWS
 };
 
 // the words most of the entry points share
@@ -1097,7 +1098,7 @@ int nddm_simulratcliff(const float *params, int64_t B, int32_t n_trials, uint64_
 }
 
 /* ---- the Wiener family.  Each entry point states its models, its flags, which pointers may be NULL, its outputs and extra fields, its
- * kernels and the words of its messages; nddm::wiener_launch makes the checks (one order and one set of status codes for all five),
+ * kernels and the words of its messages; nddm::wiener_launch makes the checks (one order and one set of status codes for all six),
  * chooses the layout and makes the one launch. ---- */
 
 /* the Wiener first-passage log-likelihood (JAGS dwiener / Stan wiener_lpdf of the reference's likelihood-based fits): csrc/nddm_wiener.h */
@@ -1179,6 +1180,22 @@ int nddm_wiener_marginal_log_likelihood(int32_t model, const float *params, int6
     A.out_trial = out_trial; A.out_sum = out_sum; A.t_censor = t_censor;
     return wiener_launch(E, model, model == NDDM_SINGLE_TRIAL, flags == 0u, params, data, R, draws_per_dataset, n_trials, params && data,
                          out_trial || out_sum, stream, A, K);
+}
+
+/* the value and the gradient of the single-trial model's marginal log-likelihood in one launch: csrc/nddm_wiener_marginal_grad.h.
+ * out_loglik may be NULL. */
+int nddm_wiener_marginal_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
+                                             int32_t n_trials, float t_censor, uint32_t flags, double *out_loglik, double *out_grad, void *stream)
+{
+    using namespace nddm;
+    static const WienerEntry E = {"nddm_wiener_marginal_log_likelihood_grad: model %s has no marginal likelihood here (NDDM_SINGLE_TRIAL only)",
+                                  "nddm_wiener_marginal_log_likelihood_grad: flags must be 0 (reserved)%s", WIENER_SHAPE_MSG, WIENER_NULL_IN_MSG,
+                                  "out_grad is NULL%s", "wiener marginal gradient kernel launch failed: %s", WMGRAD_ROWS};
+    static void (*const K[2])(WienerMarginalGradArgs) = {wiener_marginal_grad_kernel<false>, wiener_marginal_grad_kernel<true>};
+    WienerMarginalGradArgs A;
+    A.out_sum = out_loglik; A.out_grad = out_grad; A.t_censor = t_censor;
+    return wiener_launch(E, model, model == NDDM_SINGLE_TRIAL, flags == 0u, params, data, R, draws_per_dataset, n_trials, params && data,
+                         out_grad != nullptr, stream, A, K);
 }
 
 static int draw_prior_impl(int32_t model, int64_t B, uint64_t seed, uint64_t set_offset, const uint64_t *set_offset_dev,

@@ -390,8 +390,8 @@ def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs, r
 
 
 def _wiener_device_call(checked, params, data, device, outputs, call):
-    """The device half wiener_log_likelihood, wiener_marginal_log_likelihood, wiener_log_likelihood_grad, wiener_cdf and wiener_quantile
-    share.  `checked`: what _wiener_host_checks returned; `outputs`: (result key, wanted?, shape with None for n_trials, torch dtype's name)
+    """The device half wiener_log_likelihood, wiener_marginal_log_likelihood[_grad], wiener_log_likelihood_grad, wiener_cdf and
+    wiener_quantile share.  `checked`: what _wiener_host_checks returned; `outputs`: (result key, wanted?, shape with None for n_trials, torch dtype's name)
     in the result's order; `call(L, params pointer, data pointer, n_trials, {key: output pointer or None}, stream handle)` makes the one
     library call and checks its status -- it is not called for an empty batch.  -> {key: device tensor} of the wanted outputs."""
     S, p_rows, d_rows, p_np, d_np, R = checked
@@ -477,6 +477,37 @@ def wiener_log_likelihood_grad(model, params, data, draws_per_dataset=1, device=
 
     return _wiener_device_call(checked, params, data, device,
                                [("loglik", True, (R,), "float64"), ("grad", True, (R, NPARAMS[model]), "float64")], call)
+
+
+def wiener_marginal_log_likelihood_grad(model, params, data, draws_per_dataset=1, t_censor=None, device=None):
+    """Marginal log-likelihood of observed trials under the single-trial model AND its gradient in the eight parameter columns, one kernel
+    launch (include/nddm.h: nddm_wiener_marginal_log_likelihood_grad): what a gradient-based fit of this model consumes per step.  The
+    arguments of wiener_marginal_log_likelihood.  Returns {'loglik': float64 [R], 'grad': float64 [R, 8]} on the device, the columns in
+    params' order (drift, mu_alpha, beta, ter, std_alpha, dc, sigma1, gamma); 'loglik' has the bits of wiener_marginal_log_likelihood's.
+
+    A timeout (choicert 0) with t_censor > 0 HAS a gradient: a valid row of valid trials, timeouts included, gets a finite one.  An invalid
+    row gives NaN in both; |choicert| <= ter (-inf in the value), a timeout without t_censor, a non-finite z1 or a NaN choicert give NaN in
+    every gradient column of their row.  Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are."""
+    checked = _wiener_host_checks(model, params, data, draws_per_dataset, "marginal likelihood", {"grad": True}, marginal=True)
+    S, R = checked[0], checked[-1]
+    tc = 0.0 if t_censor is None else float(t_censor)
+    if math.isnan(tc) or tc < 0:
+        raise ValueError("t_censor must be >= 0 (or None: timeouts then give NaN)")
+
+    def call(L, p, d, N, o, st):
+        _lib.check(L.nddm_wiener_marginal_log_likelihood_grad(int(model), p, R, S, d, N, tc, 0, o["loglik"], o["grad"], st))
+        _WIENER_MARGINAL_GRAD_LAUNCHES[0] += 1
+
+    return _wiener_device_call(checked, params, data, device, [("loglik", True, (R,), "float64"), ("grad", True, (R, NPARAMS[model]), "float64")], call)
+
+
+# kernel launches wiener_marginal_log_likelihood_grad has made in this process (tests count them: one per forward plus backward)
+_WIENER_MARGINAL_GRAD_LAUNCHES = [0]
+
+
+def wiener_marginal_grad_launches():
+    """Developer aid: how many launches wiener_marginal_log_likelihood_grad has made in this process."""
+    return _WIENER_MARGINAL_GRAD_LAUNCHES[0]
 
 
 def wiener_cdf(model, params, data, draws_per_dataset=1, want_cdf=True, want_p_upper=True, device=None):

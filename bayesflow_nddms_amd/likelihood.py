@@ -10,6 +10,8 @@
     wiener_loglik(model, params, data, draws_per_dataset)       a row's log-likelihood, DIFFERENTIABLE in params (nddm_wiener_log_likelihood_grad)
     single_trial_logpdf(y, z, drift, mu_alpha, beta, ter, ...)  the single-trial model's joint log density of (choicert, z1), the latent
                                                                 boundary integrated out (nddm_wiener_marginal_log_likelihood)
+    single_trial_loglik(params, data, draws_per_dataset, ...)   a row's marginal log-likelihood under the single-trial model, DIFFERENTIABLE in
+                                                                params (nddm_wiener_marginal_log_likelihood_grad)
 
 The first two take numpy arrays, scalars or device tensors, broadcast them against each other (numpy rules), score every element in ONE kernel
 launch and return a float32 device tensor of the broadcast shape.  The sign of y / Y is the response: positive = upper boundary.
@@ -203,6 +205,48 @@ def wiener_loglik(model, params, data, draws_per_dataset=1, device=None):
     if not isinstance(params, torch.Tensor):
         params = torch.as_tensor(np.asarray(params, dtype=np.float64))
     return _wiener_loglik_function().apply(params, data, model, int(draws_per_dataset), device)
+
+
+_SingleTrialLoglik = None
+
+
+def _single_trial_loglik_function():
+    """The torch.autograd.Function behind single_trial_loglik (made on first use: importing this module does not import torch)."""
+    global _SingleTrialLoglik
+    if _SingleTrialLoglik is None:
+        torch = engine._torch()
+
+        class SingleTrialLoglik(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, params, data, draws_per_dataset, t_censor, device):
+                r = engine.wiener_marginal_log_likelihood_grad(engine.SINGLE_TRIAL, params.detach(), data.detach() if hasattr(data, "detach") else data,
+                                                               draws_per_dataset=draws_per_dataset, t_censor=t_censor, device=device)
+                ctx.save_for_backward(r["grad"])
+                ctx.params_shape, ctx.params_dtype, ctx.params_device = params.shape, params.dtype, params.device
+                return r["loglik"]
+
+            @staticmethod
+            def backward(ctx, grad_output):
+                (grad,) = ctx.saved_tensors                             # the forward's launch computed it: nothing is launched here
+                g = (grad_output.to(grad.dtype)[:, None] * grad).reshape(ctx.params_shape)
+                return g.to(device=ctx.params_device, dtype=ctx.params_dtype), None, None, None, None
+
+        _SingleTrialLoglik = SingleTrialLoglik
+    return _SingleTrialLoglik
+
+
+def single_trial_loglik(params, data, draws_per_dataset=1, t_censor=None, device=None):
+    """A row's marginal log-likelihood under the single-trial model, float64 [R] on the device, DIFFERENTIABLE with respect to `params` (a
+    torch tensor; [R, 8] = drift, mu_alpha, beta, ter, std_alpha, dc, sigma1, gamma): the arguments of
+    engine.wiener_marginal_log_likelihood_grad, whose ONE launch the forward makes; it keeps the gradient, and the backward is
+    grad_output[:, None] * grad cast to params' dtype and device -- no second launch.  `data` gets no gradient.  With nothing requiring grad
+    the values are the same.  Timeouts (choicert 0) are censored at t_censor and have a gradient.
+
+        loss = -likelihood.single_trial_loglik(theta, data, t_censor=4.0).sum(); loss.backward()"""
+    torch = engine._torch()                                             # (the engine call refuses bad host input before it asks for a device)
+    if not isinstance(params, torch.Tensor):
+        params = torch.as_tensor(np.asarray(params, dtype=np.float64))
+    return _single_trial_loglik_function().apply(params, data, int(draws_per_dataset), t_censor, device)
 
 
 def single_trial_logpdf(y, z, drift, mu_alpha, beta, ter, std_alpha, dc, sigma1, gamma=1.0, t_censor=None, device=None):

@@ -63,6 +63,23 @@ def log_likelihood(params, sim_data, dt=.01, max_steps=400., gamma=1.0, device=N
     return engine.wiener_marginal_log_likelihood(engine.SINGLE_TRIAL, _with_gamma(params, gamma), sim_data, t_censor=tc, device=device)["loglik"]
 
 
+def log_likelihood_and_grad(params, sim_data, dt=.01, max_steps=400., gamma=1.0, device=None):
+    """log_likelihood and its gradient in (drift, mu_alpha, beta, ter, std_alpha, dc, sigma1), one launch
+    (engine.wiener_marginal_log_likelihood_grad): the arguments of log_likelihood; params [R, 7] (or [R, 8]) against sim_data [D, n_trials, 2]
+    with R = D * S -- row r is scored against data set r // S.  Returns (float64 [R], float64 [R, 7]) on the device; the first has
+    log_likelihood's bits, the second drops gamma's column.  A missing response (choicert 0) is censored at max_steps * dt and has a gradient.
+    For a differentiable torch value see likelihood.single_trial_loglik."""
+    p = _with_gamma(params, gamma)
+    d = sim_data if hasattr(sim_data, "is_cuda") else np.asarray(sim_data, dtype=np.float64)
+    R = p.shape[0]
+    D = d.shape[0] if d.ndim == 3 else 1
+    if R % D:
+        raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
+    tc = float(engine.max_k_of(max_steps)) * float(dt)
+    r = engine.wiener_marginal_log_likelihood_grad(engine.SINGLE_TRIAL, p, d, draws_per_dataset=R // D, t_censor=tc, device=device)
+    return r["loglik"], r["grad"][:, :7]
+
+
 def simulate_trials_fine(params, n_trials, seed=None, set_offset=None, fast=None, state_f64=False):
     """(:1710-1722): 1 ms resolution, max_steps=4000 keeps the 4 s tolerance."""
     return simulate_trials(params, n_trials, dt=.001, max_steps=4000, seed=seed, set_offset=set_offset, fast=fast, state_f64=state_f64)

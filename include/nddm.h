@@ -72,6 +72,7 @@ extern "C" {
 /* 4 (additive): nddm_wiener_quantile. */
 /* 4 (additive): nddm_wiener_log_likelihood_grad.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_marginal_log_likelihood.  No existing entry point changes. */
+/* 4 (additive): nddm_wiener_marginal_log_likelihood_grad.  No existing entry point changes. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -313,11 +314,31 @@ int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t 
  * trial never gives NaN or +inf.
  * The bits of out_sum are a function of (the row's parameters, its data set, n_trials, t_censor) alone: the same whatever the layout, the
  * draws_per_dataset factorisation, the stream or a capture.  No scratch memory, no atomics: a call made while `stream` is capturing is one
- * kernel node.  Error checks, their order and their status codes are nddm_wiener_log_likelihood's; R = 0 is NDDM_OK.  No gradient.  The
- * math, the quadrature and its accuracy: csrc/nddm_wiener_marginal.h, DESIGN.md section 15. */
+ * kernel node.  Error checks, their order and their status codes are nddm_wiener_log_likelihood's; R = 0 is NDDM_OK.  Its gradient:
+ * nddm_wiener_marginal_log_likelihood_grad below.  The math, the quadrature and its accuracy: csrc/nddm_wiener_marginal.h, DESIGN.md section 15. */
 int nddm_wiener_marginal_log_likelihood(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
                                         int32_t n_trials, float t_censor, uint32_t flags /* 0, reserved */,
                                         float *out_trial /* [R, n_trials] or NULL */, double *out_sum /* [R] or NULL */, void *stream);
+
+/* The same marginal log-likelihood AND its gradient in the model's eight parameter columns, one fused launch: what a gradient-based fit of
+ * the single-trial model consumes per step (MAP refinement of amortized draws, Laplace / variational fits, HMC / NUTS).  (ABI 4, additive)
+ *   model, params, draws_per_dataset, data, n_trials, t_censor: exactly as nddm_wiener_marginal_log_likelihood takes them
+ *   flags              must be 0 (reserved): NDDM_ERR_PARAM otherwise
+ *   out_loglik         device f64 [R] or NULL: the row's log-likelihood, BIT FOR BIT nddm_wiener_marginal_log_likelihood's out_sum
+ *   out_grad           device f64 [R, 8] (NULL: NDDM_ERR_NULL): d out_loglik[r] / d params[r, j], in params' column order (drift, mu_alpha,
+ *                      beta, ter, std_alpha, dc, sigma1, gamma): the expectation of the integrand's partials under the normalised integrand
+ *                      on the quadrature's last 32 nodes, the chain rule once per row in float64
+ * Special values (none an error): an invalid row (nddm_wiener_marginal_log_likelihood's conditions) gives NaN in out_loglik and in every
+ * gradient column, the other rows unaffected; |choicert| <= ter (-inf in the value), a timeout with t_censor <= 0, a non-finite z1 or a NaN
+ * choicert (NaN in the value) give NaN in every gradient column of their row.  A TIMEOUT WITH t_censor > 0 HAS A GRADIENT: the partials of
+ * log P(no response before t_censor) in both of its forms; a valid row of valid trials, timeouts included, gets a finite gradient.
+ * The bits of both outputs are a function of (the row's parameters, its data set, n_trials, t_censor) alone: the same whatever the layout,
+ * the draws_per_dataset factorisation, the stream or a capture.  No scratch memory, no atomics: a call made while `stream` is capturing is
+ * one kernel node.  Error checks, their order and their status codes are nddm_wiener_marginal_log_likelihood's; R = 0 is NDDM_OK.  The
+ * math: csrc/nddm_wiener_marginal_grad.h, DESIGN.md section 16. */
+int nddm_wiener_marginal_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
+                                             int32_t n_trials, float t_censor, uint32_t flags /* 0, reserved */,
+                                             double *out_loglik /* [R] or NULL */, double *out_grad /* [R, 8] */, void *stream);
 
 /* The distribution function of the same first-passage law (RWiener / HDDM pwiener, the companion of dwiener) and the choice
  * probability: where in its distribution an observed response time falls -- posterior predictive p-values, probability-integral

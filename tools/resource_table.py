@@ -40,6 +40,9 @@ def pretty(name):
     m = re.match(r"_ZN4nddm22wiener_marginal_kernelILb(\d)E", name)
     if m:                                                     # the single-trial model's marginal likelihood, the same two layouts
         return f"wiener_marginal_kernel<{'broadcast' if m.group(1) == '1' else 'paired'}>"
+    m = re.match(r"_ZN4nddm27wiener_marginal_grad_kernelILb(\d)E", name)
+    if m:                                                     # its value-and-gradient kernel, the same two layouts
+        return f"wiener_marginal_grad_kernel<{'broadcast' if m.group(1) == '1' else 'paired'}>"
     m = re.match(r"_ZN(?:4nddm|10nddm_train|12nddm_deepset|11nddm_update)(\d+)", name)
     if m:
         n = int(m.group(1))
