@@ -132,3 +132,11 @@ def quantile(params, probs=(.1, .3, .5, .7, .9)):
     R, Q = (p.shape[0] if p.ndim == 2 else 1), pr.shape[0]
     req = np.stack([np.concatenate([pr, pr]), np.concatenate([-np.ones(Q), np.ones(Q)])], -1)[None]
     return engine.wiener_quantile(MODEL, p, req, draws_per_dataset=max(R, 1), conditional=True)["quantile"].reshape(R, 2, Q)
+
+
+def fit_hmc(data, **kw):
+    """The reference's likelihood-based fit of this model (basic_ddm_dc_pyjags.py: JAGS over dwiener) by batched Hamiltonian Monte Carlo on
+    the device: mcmc.hmc_fit's arguments and its result, the reference's JAGS-sample layout (alpha, ndt, beta, delta, varsigma, each
+    [participants, samples, chains]) that diagnostics.rhat_neff reads."""
+    from . import mcmc
+    return mcmc.hmc_fit(data, **kw)

@@ -54,6 +54,7 @@
 #include "nddm_wiener.h"
 #include "nddm_wiener_cdf.h"
 #include "nddm_wiener_grad.h"
+#include "nddm_wiener_hmc.h"
 #include "nddm_wiener_marginal.h"
 #include "nddm_wiener_marginal_grad.h"
 #include "nddm_wiener_quantile.h"
@@ -718,7 +719,7 @@ static bool wiener_closed_form(int32_t model) { return model == NDDM_BASIC_DDM_D
 // The argument checks in their one order: model, flags, shape, R / 16, the empty batch (*empty: NDDM_OK and nothing to launch, before any
 // pointer is looked at), NULL inputs, NULL outputs, the stream.  The entry point evaluates the conditions that are its own.
 static int wiener_checks(const WienerEntry &E, int32_t model, bool model_ok, bool flags_ok, int64_t R, int64_t S, int32_t n, bool in_ok,
-                         bool out_ok, hipStream_t st, bool *empty)
+                         bool out_ok, hipStream_t st, bool *empty, bool shape_ok = true)
 {
     *empty = false;
     if (!model_ok) {
@@ -727,7 +728,7 @@ static int wiener_checks(const WienerEntry &E, int32_t model, bool model_ok, boo
         return fail(NDDM_ERR_PARAM, E.model_msg, m);
     }
     if (!flags_ok) return fail(NDDM_ERR_PARAM, E.flags_msg);
-    if (R < 0 || n <= 0 || S <= 0 || R % S != 0) return fail(NDDM_ERR_SHAPE, E.shape_msg);
+    if (R < 0 || n <= 0 || S <= 0 || R % S != 0 || !shape_ok) return fail(NDDM_ERR_SHAPE, E.shape_msg);
     if (R / WIENER_ROWS >= (1ll << 31)) return fail(NDDM_ERR_SHAPE, "R / 16 must be < 2^31 per launch%s");
     if (R == 0) { *empty = true; return NDDM_OK; }
     if (!in_ok) return fail(NDDM_ERR_NULL, E.null_in_msg);
@@ -1165,6 +1166,43 @@ int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t 
     A.out_sum = out_loglik; A.out_grad = out_grad;
     return wiener_launch(E, model, wiener_closed_form(model), flags == 0u, params, data, R, draws_per_dataset, n_trials, params && data,
                          out_grad != nullptr, stream, A, K[model == NDDM_ALPHA_NOT_SCALED]);
+}
+
+/* batched Hamiltonian Monte Carlo over the basic_ddm_dc Wiener posterior, one wave per chain: csrc/nddm_wiener_hmc.h.  A chain is a row of
+ * the family's checks; the plan is its own (4 chains per workgroup, no broadcast layout: every wave stages its own data set). */
+int nddm_wiener_hmc(int32_t model, const float *data, int64_t D, int32_t n_trials, int64_t C, int64_t chains_per_dataset, double *state,
+                    const double *inv_mass, int32_t n_iter, int32_t n_adapt, int32_t n_leapfrog, int32_t thin, uint32_t free_mask,
+                    uint64_t seed, uint64_t chain_offset, uint64_t iter_offset, uint32_t flags, float *out_draws, float *out_log_post,
+                    float *out_accept, int32_t *out_divergent, int32_t *out_flagged, void *stream)
+{
+    using namespace nddm;
+    static const WienerEntry E = {"nddm_wiener_hmc: model %s has no sampler here (NDDM_BASIC_DDM_DC only)",
+                                  "nddm_wiener_hmc: flags must be 0 (reserved) and free_mask < 32%s",
+                                  "C >= 0 chains = D x chains_per_dataset > 0, 0 < n_trials <= 2048, n_iter, n_leapfrog, thin > 0, n_adapt >= 0, "
+                                  "n_iter x n_leapfrog x ceil(n_trials / 64) <= 2^19 per launch and chain / iteration indices < 2^32 are required%s",
+                                  "data or state is NULL%s", WIENER_NULL_OUT_MSG, "wiener hmc kernel launch failed: %s", 4};
+    g_err[0] = 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const bool counts_ok = n_iter > 0 && n_leapfrog > 0 && thin > 0 && n_adapt >= 0 && n_trials <= WHMC_MAX_TRIALS && D >= 0 &&
+                           chains_per_dataset > 0 && C == D * chains_per_dataset;
+    const bool shape_ok = counts_ok && (long long)n_iter * n_leapfrog * ((n_trials + 63) / 64) <= WHMC_MAX_ROUNDS &&
+                          chain_offset < (1ull << 32) && chain_offset + (uint64_t)(C > 0 ? C : 0) <= (1ull << 32) &&
+                          iter_offset < (1ull << 32) && iter_offset + (uint64_t)n_iter <= (1ull << 32);
+    bool empty;
+    if (const int rc = wiener_checks(E, model, model == NDDM_BASIC_DDM_DC, flags == 0u && free_mask < 32u, C, chains_per_dataset, n_trials,
+                                     data && state, out_draws || out_log_post || out_accept || out_divergent || out_flagged, st, &empty,
+                                     shape_ok)) return rc;
+    if (empty) return NDDM_OK;
+    WienerHmcArgs A;
+    A.data = data; A.state = state; A.inv_mass = inv_mass;
+    A.out_draws = out_draws; A.out_log_post = out_log_post; A.out_accept = out_accept; A.out_divergent = out_divergent; A.out_flagged = out_flagged;
+    A.C = C; A.S = chains_per_dataset; A.chain_offset = chain_offset; A.iter_offset = iter_offset;
+    A.K = (long long)((iter_offset + (uint64_t)n_iter) / (uint64_t)thin - iter_offset / (uint64_t)thin);
+    A.k0 = (unsigned)seed; A.k1 = (unsigned)(seed >> 32);
+    A.free_mask = free_mask; A.N = n_trials; A.n_iter = n_iter; A.n_adapt = n_adapt; A.n_leapfrog = n_leapfrog; A.thin = thin;
+    hipLaunchKernelGGL(wiener_hmc_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, A);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? NDDM_OK : fail(NDDM_ERR_HIP, E.launch_msg, hipGetErrorString(e));
 }
 
 /* the single-trial model's marginal log-likelihood (the latent per-trial boundary integrated out by quadrature): csrc/nddm_wiener_marginal.h */

@@ -99,6 +99,49 @@ def converged_fits(param_means, index=3, low=0.0, high=1.0):
     return (m[:, index] > low) & (m[:, index] < high)
 
 
+def rhat_neff(samples):
+    """Convergence diagnostics of MCMC output in the reference's JAGS-sample layout: a dict of arrays [..., iterations, chains] (keys that
+    begin with '_' are skipped), or one such array -> per key (or for the array) {'rhat', 'neff', 'mean', 'std'}, each of the leading
+    shape.  What the reference's `diagnostic` reports (pyhddmjagsutils.py:180-331), from the formulas of Gelman et al., Bayesian Data
+    Analysis, 3rd ed., section 11.4-11.5, with that function's conventions: population variances (divisor n) within a chain;
+        rhat   split chains: each chain's halves as 2m chains of n/2, sqrt(((1 - 2/n) W + (2/n) B) / W)
+        neff   m n / (1 + 2 sum rho_t) with rho_t = 1 - V_t / (2 var+), var+ of the UNSPLIT chains, V_t the variogram at lag t averaged over
+               the chains; lags 1, 2, ... are added in pairs (t, t + 1), t odd, while the last pair's sum is not negative (that pair is
+               still counted) and the pair's even lag stays below n - 2; rounded to an integer."""
+    if isinstance(samples, dict):
+        return {k: rhat_neff(v) for k, v in samples.items() if not k.startswith("_")}
+    x = np.asarray(samples, dtype=np.float64)
+    if x.ndim < 2 or x.shape[-2] < 4 or x.shape[-1] < 2:
+        raise ValueError(f"samples must be [..., iterations >= 4, chains >= 2], got {x.shape}")
+    lead, n, m = x.shape[:-2], x.shape[-2], x.shape[-1]
+    x = x.reshape((-1, n, m))
+
+    def var_plus(y):                                                    # y [V, n, m] -> (var+, W)
+        k = y.shape[1]
+        cm = y.mean(axis=1)
+        B = k * ((cm - cm.mean(axis=1, keepdims=True)) ** 2).sum(axis=1) / (y.shape[2] - 1.0)
+        W = y.var(axis=1).mean(axis=1)
+        return (1.0 - 1.0 / k) * W + B / k, W
+    h = n // 2
+    split = np.concatenate([x[:, :h, :], x[:, h:2 * h, :]] if n % 2 == 0 else [x[:, :h, :], x[:, n - h:, :]], axis=2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vs, Ws = var_plus(split)
+        rhat = np.sqrt(vs / Ws)
+        vp, _ = var_plus(x)
+        neff = np.empty(x.shape[0])
+        for v in range(x.shape[0]):
+            tot, pair, t = 0.0, 0.0, 2
+            while t < n - 2 and pair >= 0.0:
+                odd = 1.0 - np.mean((x[v, t - 1:] - x[v, :n - t + 1]) ** 2) / (2.0 * vp[v])
+                even = 1.0 - np.mean((x[v, t:] - x[v, :n - t]) ** 2) / (2.0 * vp[v])
+                pair = odd + even
+                tot += pair
+                t += 2
+            neff[v] = np.round(m * n / (1.0 + 2.0 * tot))
+    return {"rhat": rhat.reshape(lead), "neff": neff.reshape(lead), "mean": x.mean(axis=(1, 2)).reshape(lead),
+            "std": x.reshape(x.shape[0], -1).std(axis=1).reshape(lead)}
+
+
 def posterior_log_likelihood(samples, data, model):
     """Score posterior draws by the exact likelihood: samples [D, S, P] (what amortizer.sample returns for a batch of D data sets;
     [S, P] for one), data [D, n_trials, 2] in the simulator's format (model = engine.BASIC_DDM_DC or engine.ALPHA_NOT_SCALED) ->

@@ -449,6 +449,98 @@ def wiener_marginal_log_likelihood(model, params, data, draws_per_dataset=1, t_c
                                                                                    st)))
 
 
+WHMC_STATE, WHMC_MAX_TRIALS, WHMC_MAX_ROUNDS = 12, 2048, 1 << 19
+
+
+def wiener_hmc_max_iter(n_trials, n_leapfrog):
+    """The most iterations one nddm_wiener_hmc launch may run: n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19."""
+    return max(WHMC_MAX_ROUNDS // (int(n_leapfrog) * ((int(n_trials) + 63) // 64)), 0)
+
+
+def wiener_hmc(model, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1, n_adapt=0, n_leapfrog=16, thin=1, free_mask=31, seed=0,
+               chain_offset=0, iter_offset=0, want_draws=True, want_log_post=True, device=None):
+    """Batched Hamiltonian Monte Carlo over the basic_ddm_dc Wiener posterior, one wave per chain, all n_iter iterations in ONE launch
+    (include/nddm.h: nddm_wiener_hmc; the chain: csrc/nddm_wiener_hmc.h).
+
+    model: BASIC_DDM_DC only.  data: [D, n_trials, 2] = (rt, choice), n_trials <= 2048.  state: float64 [C, 12], C = D *
+    chains_per_dataset, chain c on data set c // chains_per_dataset (mcmc.make_state builds one; a device tensor is updated in place).
+    inv_mass: float64 [C, 5] or None (ones).  One launch is bounded: n_iter <= wiener_hmc_max_iter(n_trials, n_leapfrog); mcmc.hmc_fit
+    cuts a long run into such launches.  Returns a dict of device tensors: 'draws' float32 [C, K, 5] in the model's columns, 'log_post'
+    float32 [C, K], 'accept' float32 [C], 'divergent' int32 [C], 'flagged' int32 [C] and 'state' float64 [C, 12]; K = (iter_offset +
+    n_iter) // thin - iter_offset // thin.  Host inputs are shape- and range-checked (ValueError); a data set that cannot be sampled (a
+    timeout, a non-finite value, an rt <= 0) that arrives on the device flags its chains instead."""
+    if model != BASIC_DDM_DC:
+        raise ValueError(f"model {model} has no sampler here (BASIC_DDM_DC only)")
+    S, n_iter, n_adapt, n_leapfrog, thin, free_mask = (int(x) for x in (chains_per_dataset, n_iter, n_adapt, n_leapfrog, thin, free_mask))
+    if S <= 0:
+        raise ValueError("chains_per_dataset must be > 0")
+    if n_iter <= 0 or n_leapfrog <= 0 or thin <= 0 or n_adapt < 0:
+        raise ValueError("n_iter, n_leapfrog and thin must be > 0 and n_adapt >= 0")
+    if not 0 <= free_mask < 32:
+        raise ValueError("free_mask has five bits")
+    chain_offset, iter_offset = int(chain_offset), int(iter_offset)
+    if chain_offset < 0 or iter_offset < 0 or iter_offset + n_iter > 1 << 32:
+        raise ValueError("chain_offset and iter_offset must be >= 0 and the iteration index < 2^32")
+    d_rows = (3, 2, "data must have shape [D, n_trials, 2]")
+    d_np = _host_rows(data, *d_rows)
+    if d_np is not None:
+        if not np.all(np.isfinite(d_np)):
+            raise ValueError("data must be finite")
+        if not np.all(np.isin(d_np[..., 1], (-1.0, 1.0))):
+            raise ValueError("the sampler takes (rt, choice) with choice in {1, -1}: a timeout (choice 0) has no gradient here")
+        if np.any(d_np[..., 0] <= 0):
+            raise ValueError("response times must be > 0")
+    D, N = (int(d_np.shape[0]), int(d_np.shape[1])) if d_np is not None else \
+        ((1, int(data.shape[0])) if data.ndim == 2 else (int(data.shape[0]), int(data.shape[1])))
+    if N > WHMC_MAX_TRIALS:
+        raise ValueError(f"n_trials must be <= {WHMC_MAX_TRIALS}")
+    if n_iter > wiener_hmc_max_iter(N, n_leapfrog):
+        raise ValueError(f"one launch runs at most {wiener_hmc_max_iter(N, n_leapfrog)} iterations at n_trials {N} and n_leapfrog {n_leapfrog} "
+                         "(n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19): cut the run (mcmc.hmc_fit does)")
+    C = D * S
+    if chain_offset + C > 1 << 32:
+        raise ValueError("the chain index must stay < 2^32")
+
+    def rows(x, last, label):
+        if getattr(x, "is_cuda", False):
+            if tuple(x.shape) != (C, last) or str(x.dtype) != "torch.float64" or not x.is_contiguous():
+                raise ValueError(f"{label} must be a contiguous float64 [{C}, {last}]")
+            return None
+        a = np.ascontiguousarray(x, dtype=np.float64)
+        if a.shape != (C, last):
+            raise ValueError(f"{label} must have shape [{C}, {last}] (D {D} x chains_per_dataset {S}), got {a.shape}")
+        return a
+    s_np = rows(state, WHMC_STATE, "state")
+    if s_np is not None and not np.all(np.isfinite(s_np[:, :10])):
+        raise ValueError("state must be finite")
+    m_np = None if inv_mass is None else rows(inv_mass, 5, "inv_mass")
+    if m_np is not None and not (np.all(np.isfinite(m_np)) and np.all(m_np > 0)):
+        raise ValueError("inv_mass must be finite and > 0")
+    torch = require_device()
+    L = _lib.lib()
+    dev = _device(device)
+    K = (iter_offset + n_iter) // thin - iter_offset // thin
+    with torch.cuda.device(dev):
+        d_dev = _device_rows(data, d_np, dev, *d_rows)
+        s_dev = state if s_np is None else torch.as_tensor(s_np, dtype=torch.float64).to(dev)
+        m_dev = None if inv_mass is None else (inv_mass if m_np is None else torch.as_tensor(m_np, dtype=torch.float64).to(dev))
+        res = {"draws": torch.empty((C, K, 5), dtype=torch.float32, device=dev) if want_draws else None,
+               "log_post": torch.empty((C, K), dtype=torch.float32, device=dev) if want_log_post else None,
+               "accept": torch.empty((C,), dtype=torch.float32, device=dev), "divergent": torch.empty((C,), dtype=torch.int32, device=dev),
+               "flagged": torch.empty((C,), dtype=torch.int32, device=dev)}
+        if C > 0:
+            st = torch.cuda.current_stream(dev)
+            _lib.check(L.nddm_wiener_hmc(int(model), _ptr(d_dev), D, N, C, S, _ptr(s_dev), _ptr(m_dev), n_iter, n_adapt, n_leapfrog, thin,
+                                         free_mask, _u64(seed), chain_offset, iter_offset, 0, _ptr(res["draws"]), _ptr(res["log_post"]),
+                                         _ptr(res["accept"]), _ptr(res["divergent"]), _ptr(res["flagged"]), st.cuda_stream))
+            for t in (d_dev, s_dev, m_dev):
+                if t is not None:
+                    t.record_stream(st)
+    res = {k: v for k, v in res.items() if v is not None}
+    res["state"] = s_dev
+    return res
+
+
 # kernel launches wiener_log_likelihood_grad has made in this process (tests count them: one per forward plus backward)
 _WIENER_GRAD_LAUNCHES = [0]
 

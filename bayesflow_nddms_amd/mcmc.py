@@ -1,0 +1,204 @@
+"""The reference's likelihood-based fit of basic_ddm_dc (basic_ddm_dc_pyjags.py: JAGS over dwiener, 6 chains per participant) as batched
+Hamiltonian Monte Carlo on the device: engine.wiener_hmc runs every chain of every participant in one launch per block of iterations
+(csrc/nddm_wiener_hmc.h); this module holds the host side -- the coordinates, the initial values, the warm-up schedule and the
+reference's sample layout.  DESIGN.md section 17.
+
+Columns (drift, boundary, beta, tau, dc); the posterior, its supports and its documented deviations from the JAGS model (the dc floor, tau
+below the smallest response time) are the header's."""
+import numpy as np
+
+from . import engine
+
+PARAM_NAMES = ("drift", "boundary", "beta", "tau", "dc")
+JAGS_NAMES = {"drift": "delta", "boundary": "alpha", "beta": "beta", "tau": "ndt", "dc": "varsigma"}     # basic_ddm_dc_pyjags.py:170
+DC_MIN = 0.05
+ALL_FREE = 31
+
+
+def free_mask(free=PARAM_NAMES):
+    """Column names (or a mask) -> the five-bit mask of the sampled columns."""
+    if isinstance(free, (int, np.integer)):
+        if not 0 <= int(free) < 32:
+            raise ValueError("free_mask has five bits")
+        return int(free)
+    unknown = [f for f in free if f not in PARAM_NAMES]
+    if unknown:
+        raise ValueError(f"unknown columns {unknown}: the columns are {PARAM_NAMES}")
+    return sum(1 << PARAM_NAMES.index(f) for f in set(free))
+
+
+def _support(data):
+    """data [C, N, 2] (one data set per row of theta / q) -> (lo [C, 5], width [C, 5]) of the bounded columns (column 0 unused)."""
+    d = np.asarray(data, dtype=np.float32)
+    if d.ndim == 2:
+        d = d[None]
+    if d.ndim != 3 or d.shape[-1] != 2 or d.shape[1] == 0:
+        raise ValueError(f"data must have shape [C, n_trials, 2], got {d.shape}")
+    T = np.minimum(1.5, d[..., 0].min(axis=1).astype(np.float64))
+    if not np.all(T > 0):
+        raise ValueError("response times must be > 0")
+    C = d.shape[0]
+    lo = np.zeros((C, 5))
+    lo[:, 4] = DC_MIN
+    wd = np.stack([np.ones(C), np.full(C, 10.0), np.ones(C), T, np.full(C, 10.0 - DC_MIN)], 1)
+    return lo, wd
+
+
+def theta_to_q(theta, data, free=ALL_FREE):
+    """theta [C, 5] (or [5]) in the model's columns -> the sampler's coordinates q, float64: drift unchanged, a bounded column
+    logit((theta - lo) / (hi - lo)) with tau's upper limit T = min(1.5, the smallest rt of the row's data set) -- hence `data` [C, N, 2]
+    (or [N, 2]).  A column that is not `free` keeps theta, as the sampler's state does."""
+    t = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+    lo, wd = _support(data)
+    if t.shape != lo.shape:
+        raise ValueError(f"theta must have shape [{lo.shape[0]}, 5] (one row per data set), got {t.shape}")
+    mask = free_mask(free)
+    x = (t - lo) / wd
+    if any((mask >> j & 1) and np.any(~((x[:, j] > 0) & (x[:, j] < 1))) for j in range(1, 5)):
+        raise ValueError("theta lies outside the sampler's support: boundary (0, 10), beta (0, 1), tau (0, min(1.5, min rt)), dc (0.05, 10)")
+    q = t.copy()
+    for j in range(1, 5):
+        if mask >> j & 1:
+            q[:, j] = np.log(x[:, j]) - np.log1p(-x[:, j])
+    return q if np.ndim(theta) == 2 else q[0]
+
+
+def q_to_theta(q, data, free=ALL_FREE):
+    """The inverse of theta_to_q."""
+    x = np.atleast_2d(np.asarray(q, dtype=np.float64))
+    lo, wd = _support(data)
+    if x.shape != lo.shape:
+        raise ValueError(f"q must have shape [{lo.shape[0]}, 5] (one row per data set), got {x.shape}")
+    mask = free_mask(free)
+    t = x.copy()
+    for j in range(1, 5):
+        if mask >> j & 1:
+            e = np.exp(-np.abs(x[:, j]))
+            t[:, j] = lo[:, j] + wd[:, j] * np.where(x[:, j] >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    return t if np.ndim(q) == 2 else t[0]
+
+
+def make_state(theta, data, eps0=0.05, free=ALL_FREE):
+    """The state [C, 12] a chain starts from at theta [C, 5] (data [C, N, 2]: each chain's data set): q, log eps = log eps0, log eps-bar =
+    0, H-bar = 0, mu = log(10 eps0), no adapting iteration done (Hoffman & Gelman 2014, algorithm 5's initial values)."""
+    q = np.atleast_2d(theta_to_q(theta, data, free))
+    st = np.zeros((q.shape[0], engine.WHMC_STATE))
+    st[:, :5] = q
+    st[:, 5] = np.log(eps0)
+    st[:, 8] = np.log(10.0 * eps0)
+    return st
+
+
+def restart_adaptation(state, eps0=None):
+    """A state whose step-size adaptation begins again: at the step size it has (or eps0), H-bar = 0, no adapting iteration done."""
+    st = np.array(state, dtype=np.float64)
+    if eps0 is not None:
+        st[:, 5] = np.log(eps0)
+    st[:, 6] = 0.0
+    st[:, 7] = 0.0
+    st[:, 8] = np.log(10.0) + st[:, 5]
+    st[:, 9] = 0.0
+    return st
+
+
+def hmc_init(data, chains, seed):
+    """The reference's initial values (basic_ddm_dc_pyjags.py:188-196) for `chains` chains per data set: uniform on (.5, 2) for boundary and
+    dc, (.2, .8) for beta, (-4, 4) for drift, (0, min rt / 2) for the non-decision time -> float64 [D, chains, 5] in this project's
+    columns."""
+    d = np.asarray(data, dtype=np.float64)
+    if d.ndim == 2:
+        d = d[None]
+    rng = np.random.default_rng(seed)
+    D = d.shape[0]
+    th = np.empty((D, int(chains), 5))
+    th[..., 0] = rng.uniform(-4.0, 4.0, (D, chains))
+    th[..., 1] = rng.uniform(0.5, 2.0, (D, chains))
+    th[..., 2] = rng.uniform(0.2, 0.8, (D, chains))
+    th[..., 3] = rng.uniform(0.0, 1.0, (D, chains)) * (np.minimum(d[..., 0].min(axis=1), 1.5)[:, None] / 2.0)
+    th[..., 4] = rng.uniform(0.5, 2.0, (D, chains))
+    return th
+
+
+def _run(call, data, state, inv_mass, n_iter, n_adapt, iter_offset, max_iter, thin, **kw):
+    """n_iter iterations from iter_offset as bounded launches -> (the launches' results, the state)."""
+    out, done = [], 0
+    while done < n_iter:
+        n = min(max_iter, n_iter - done)
+        r = call(engine.BASIC_DDM_DC, data, state, inv_mass=inv_mass, n_iter=n, n_adapt=n_adapt, thin=thin, iter_offset=iter_offset + done, **kw)
+        state = r["state"]
+        out.append(r)
+        done += n
+    return out, state
+
+
+def hmc_fit(data, chains=6, warmup=2000, samples=10000, thin=10, n_leapfrog=16, free=PARAM_NAMES, fixed=None, seed=0, eps0=0.05,
+            device=None, _call=None):
+    """Fit basic_ddm_dc to every data set of data [D, n_trials, 2] = (rt, choice in {1, -1}) by `chains` HMC chains each, all D * chains
+    chains side by side on the device (engine.wiener_hmc), the defaults the reference's: 6 chains, 2000 + 10 000 iterations, thin 10.
+
+    free: the sampled columns; fixed: {column: value}, columns held at a value and taken out of `free` (fixed={"dc": 1.0} is the standard DDM
+    fit: the likelihood identifies only boundary / dc and drift / dc, so with dc free the priors alone hold that direction); a column
+    neither free nor fixed keeps its initial value.  Warm-up has two stages: the first half adapts
+    the step size under unit mass, and its second half's q give inv_mass, their per-chain variance floored at 1e-3; the second half adapts
+    the step size again under that mass.  Sampling follows, cut into the bounded launches the entry point accepts.
+
+    Returns the reference's JAGS-sample layout: 'alpha', 'ndt', 'beta', 'delta', 'varsigma', each float64 [D, samples // thin, chains], plus
+    'log_post' of the same shape, 'accept_rate' [D, chains] (the sampling iterations' mean acceptance probability), 'n_divergent'
+    [D, chains] and 'flagged' [D, chains]."""
+    call = _call or (lambda *a, **k: engine.wiener_hmc(*a, device=device, **k))
+    d = np.asarray(data.detach().cpu().numpy() if hasattr(data, "detach") else data, dtype=np.float32)
+    if d.ndim == 2:
+        d = d[None]
+    if d.ndim != 3 or d.shape[-1] != 2:
+        raise ValueError(f"data must have shape [D, n_trials, 2], got {d.shape}")
+    chains, warmup, samples, thin = int(chains), int(warmup), int(samples), int(thin)
+    if chains < 1 or warmup < 4 or samples < 1 or thin < 1 or samples % thin:
+        raise ValueError("chains >= 1, warmup >= 4, samples >= 1 and thin dividing samples are required")
+    mask = free_mask(free)
+    fixed = {} if fixed is None else dict(fixed)
+    for k in fixed:
+        if k not in PARAM_NAMES:
+            raise ValueError(f"unknown fixed column {k!r}: the columns are {PARAM_NAMES}")
+        mask &= ~(1 << PARAM_NAMES.index(k))                             # (a fixed column is not sampled, whatever `free` says)
+    D, N = d.shape[0], d.shape[1]
+    theta = hmc_init(d, chains, seed)
+    for k, v in fixed.items():
+        theta[..., PARAM_NAMES.index(k)] = float(v)
+    per_chain = np.repeat(d, chains, 0)
+    state = make_state(theta.reshape(-1, 5), per_chain, eps0=eps0, free=mask)
+    max_iter = engine.wiener_hmc_max_iter(N, n_leapfrog)
+    if max_iter < 1:
+        raise ValueError("n_leapfrog is too large for one bounded launch")
+    kw = dict(chains_per_dataset=chains, n_leapfrog=n_leapfrog, free_mask=mask, seed=seed)
+    # stage 1: unit mass; its second half kept (every iteration) for the mass
+    w1 = warmup // 2
+    h1 = w1 // 2
+    _, state = _run(call, d, state, None, h1, w1, 0, max_iter, 1, want_draws=False, want_log_post=False, **kw)
+    res, state = _run(call, d, state, None, w1 - h1, w1, h1, max_iter, 1, want_log_post=False, **kw)
+    th = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)                   # [C, w1 - h1, 5], float32 theta
+    lo, wd = _support(per_chain)
+    x = np.clip((th - lo[:, None, :]) / wd[:, None, :], 1e-7, 1.0 - 1e-7)
+    qs = np.where(np.array([False] + [bool(mask >> j & 1) for j in range(1, 5)]), np.log(x) - np.log1p(-x), th)
+    var = np.var(qs, axis=1) if qs.shape[1] > 1 else np.ones((D * chains, 5))
+    inv_mass = np.where(np.isfinite(var), np.maximum(var, 1e-3), 1.0)
+    # stage 2: that mass, the step size adapted again
+    state = restart_adaptation(_host(state))
+    w2 = warmup - w1
+    _, state = _run(call, d, state, inv_mass, w2, w2, w1, max_iter, 1, want_draws=False, want_log_post=False, **kw)
+    res, state = _run(call, d, state, inv_mass, samples, w2, warmup, max_iter, thin, **kw)
+    # (iteration g is kept when (g + 1) % thin == 0: with warmup a multiple of thin every launch's draws line up)
+    draws = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)
+    lp = np.concatenate([_host(r["log_post"]) for r in res], 1).astype(np.float64)
+    K = draws.shape[1]
+    n_samp = np.array([min(max_iter, samples - i * max_iter) for i in range(len(res))], dtype=np.float64)
+    acc = sum(_host(r["accept"]).astype(np.float64) * n for r, n in zip(res, n_samp)) / n_samp.sum()
+    out = {JAGS_NAMES[name]: draws[:, :, j].reshape(D, chains, K).transpose(0, 2, 1) for j, name in enumerate(PARAM_NAMES)}
+    out["log_post"] = lp.reshape(D, chains, K).transpose(0, 2, 1)
+    out["accept_rate"] = acc.reshape(D, chains)
+    out["n_divergent"] = sum(_host(r["divergent"]).astype(np.int64) for r in res).reshape(D, chains)
+    out["flagged"] = _host(res[0]["flagged"]).astype(np.int64).reshape(D, chains)
+    return out
+
+
+def _host(t):
+    return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)

@@ -73,6 +73,7 @@ extern "C" {
 /* 4 (additive): nddm_wiener_log_likelihood_grad.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_marginal_log_likelihood.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_marginal_log_likelihood_grad.  No existing entry point changes. */
+/* 4 (additive): nddm_wiener_hmc.  No existing entry point changes. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -293,6 +294,39 @@ int nddm_wiener_log_likelihood(int32_t model, const float *params, int64_t R, in
 int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
                                     int32_t n_trials, uint32_t flags /* 0, reserved */, double *out_loglik /* [R] or NULL */,
                                     double *out_grad /* [R, P] */, void *stream);
+
+/* Batched Hamiltonian Monte Carlo over the basic_ddm_dc posterior of the reference's JAGS fit (basic_ddm_dc_pyjags.py:103-137), one wave per
+ * chain, all the iterations of the call in one launch.  (ABI 4, additive)
+ *   model              NDDM_BASIC_DDM_DC only (NDDM_ERR_PARAM otherwise); columns (drift, boundary, beta, tau, dc)
+ *   data               device f32 [D, n_trials, 2] = (rt, choice), n_trials <= 2048; chain c samples data set c / chains_per_dataset,
+ *                      C = D * chains_per_dataset
+ *   state              device f64 [C, 12], in and out: q[5] (unconstrained: drift = q0, a bounded column theta = lo + (hi - lo) sigmoid(q);
+ *                      a FIXED column's slot holds theta itself), log eps, log eps-bar, H-bar, mu, adapting iterations done, then two
+ *                      words the chain only reports in: the last iteration's energy error H1 - H0 and the largest finite |H1 - H0| so far
+ *   inv_mass           device f64 [C, 5] or NULL (ones): momentum p_j ~ N(0, 1 / inv_mass_j)
+ *   n_iter, n_leapfrog, thin > 0, n_adapt >= 0: a chain adapts log eps by dual averaging (target .8) while its state counts fewer than
+ *                      n_adapt adapting iterations.  One launch is bounded: n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19 (about 1.2 s)
+ *   free_mask          bit j set: column j is sampled; clear: it keeps its value (no momentum, prior or Jacobian term).  < 32
+ *   seed, chain_offset, iter_offset: Philox key and the global indices (both < 2^32) of chain 0 and of this call's first iteration.  A
+ *                      chain's output is a pure function of (seed, global chain index, its data set, its incoming state, inv_mass,
+ *                      free_mask, n_leapfrog, thin, n_adapt, the iteration range): a run continued from a returned state with iter_offset
+ *                      advanced gives the bits of the uncut run, whatever else is in the launch
+ *   flags              must be 0 (reserved)
+ *   outputs, each may be NULL, not all: out_draws f32 [C, K, 5] in theta and out_log_post f32 [C, K] (the log posterior in q, Jacobian
+ *                      included, up to an additive constant), K = (iter_offset + n_iter) / thin - iter_offset / thin, global iteration g
+ *                      kept when (g + 1) % thin == 0; out_accept f32 [C]: the mean acceptance probability of this call's non-adapting
+ *                      iterations (NaN: none); out_divergent i32 [C]: rejections with a non-finite or > 1000 energy error;
+ *                      out_flagged i32 [C]
+ * Priors: drift N(0, 2^2); boundary N(1, .5^2) on (0, 10); beta Beta(2, 2); tau N(.5, .25^2) on (0, min(1.5, smallest rt)); dc N(1, .5^2)
+ * on (0.05, 10) -- the floor is a deviation from JAGS's (0, 10).  A chain whose data set holds a choice-0 trial, a non-finite value or an
+ * rt <= 0, or whose incoming state (or inverse mass) is not finite, is FLAGGED: no iteration, NaN draws, out_flagged = 1, state unchanged,
+ * the other chains unaffected.  Error checks, their order and their status codes are nddm_wiener_log_likelihood's (a chain is a row); C = 0
+ * is NDDM_OK.  No scratch memory, no atomics.  The chain: csrc/nddm_wiener_hmc.h, DESIGN.md section 17. */
+int nddm_wiener_hmc(int32_t model, const float *data /* [D, n_trials, 2] */, int64_t D, int32_t n_trials, int64_t C,
+                    int64_t chains_per_dataset, double *state /* [C, 12] */, const double *inv_mass /* [C, 5] or NULL */, int32_t n_iter,
+                    int32_t n_adapt, int32_t n_leapfrog, int32_t thin, uint32_t free_mask, uint64_t seed, uint64_t chain_offset,
+                    uint64_t iter_offset, uint32_t flags /* 0, reserved */, float *out_draws, float *out_log_post, float *out_accept,
+                    int32_t *out_divergent, int32_t *out_flagged, void *stream);
 
 /* The single-trial model's MARGINAL log-likelihood: the per-trial boundary a ~ N(mu_alpha, std_alpha^2) | a > 0 is latent, z1 ~ N(gamma a,
  * sigma1^2) observes it, and the response is the first passage of the Wiener process with boundary a; the latent is integrated out, one

@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""Rate of the batched HMC sampler (nddm_wiener_hmc; csrc/nddm_wiener_hmc.h) at the shape of the reference's fit -- 100 participants x 6
+chains = 600 chains x 100 trials, 16 leapfrog steps (basic_ddm_dc_pyjags.py) -- beside the route the library offered before it: the SAME
+algorithm (the same coordinates, priors, jittered step, leapfrog and accept rule) as a PyTorch loop over likelihood.wiener_loglik with all
+600 chains batched, one gradient launch per leapfrog step plus PyTorch's elementwise ops around it.  Both run in this process, alternating,
+after a warm-up of each; the figure of each is the MEDIAN of three timed runs (a host clock around work that ends in a device synchronise).
+
+Prints one JSON line: seconds per iteration of both, their ratio, the device loop's time per leapfrog step and per trial round (64 trials of
+one chain), leapfrog x trials per second, the time of one full bounded launch (WHMC_MAX_ROUNDS rounds), and the projected wall time of the
+reference's 2000 + 10 000 iterations cut into bounded launches.
+
+Usage: python tools/wiener_hmc_rate.py [--json OUT] [--iters 8000] [--baseline-iters 60]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.dirname(os.path.abspath(__file__))]
+
+D, CHAINS, N, LEAPFROG = 100, 6, 100, 16
+EPS = 0.05
+
+
+def torch_hmc(torch, engine, likelihood, data, q, T, n_iter, eps, gen):
+    """n_iter iterations of the kernel's algorithm for all chains at once in PyTorch float64: unit mass, all five columns free, one
+    likelihood.wiener_loglik launch (value and gradient) per leapfrog step -> (q, the mean acceptance probability)."""
+    C = q.shape[0]
+    lo = torch.tensor([0.0, 0.0, 0.0, 0.0, 0.05], dtype=torch.float64, device=q.device)
+    wd = torch.stack([torch.ones_like(T), torch.full_like(T, 10.0), torch.ones_like(T), T, torch.full_like(T, 9.95)], 1)
+
+    def log_post(x):
+        sg = torch.sigmoid(x)
+        th = torch.cat([x[:, :1], lo[1:] + wd[:, 1:] * sg[:, 1:]], 1).detach().requires_grad_(True)
+        ll = likelihood.wiener_loglik(engine.BASIC_DDM_DC, th, data, draws_per_dataset=CHAINS)
+        (gl,) = torch.autograd.grad(ll.sum(), th)
+        v, a, b, ta, s = th.detach().unbind(1)
+        lp = ll.detach() - 0.125 * v * v - 2.0 * (a - 1.0) ** 2 + torch.log(b) + torch.log1p(-b) - 8.0 * (ta - 0.5) ** 2 - 2.0 * (s - 1.0) ** 2
+        gl = gl + torch.stack([-0.25 * v, -4.0 * (a - 1.0), 1.0 / b - 1.0 / (1.0 - b), -16.0 * (ta - 0.5), -4.0 * (s - 1.0)], 1)
+        jac = wd[:, 1:] * sg[:, 1:] * (1.0 - sg[:, 1:])
+        lp = lp + (torch.log(wd[:, 1:]) + torch.nn.functional.logsigmoid(x[:, 1:]) + torch.nn.functional.logsigmoid(-x[:, 1:])).sum(1)
+        return lp, torch.cat([gl[:, :1], gl[:, 1:] * jac + (1.0 - 2.0 * sg[:, 1:])], 1)
+    lp, g = log_post(q)
+    acc = torch.zeros((), dtype=torch.float64, device=q.device)
+    for _ in range(n_iter):
+        p = torch.randn(C, 5, dtype=torch.float64, device=q.device, generator=gen)
+        u = torch.rand(C, 2, dtype=torch.float64, device=q.device, generator=gen)
+        e = (eps * (0.8 + 0.2 * u[:, 0]))[:, None]
+        H0 = -lp + 0.5 * (p * p).sum(1)
+        qn, gn = q, g
+        for _ in range(LEAPFROG):
+            p = p + 0.5 * e * gn
+            qn = qn + e * p
+            lpn, gn = log_post(qn)
+            p = p + 0.5 * e * gn
+        d = H0 - (-lpn + 0.5 * (p * p).sum(1))
+        ok = torch.isfinite(d) & (d > -1000.0)
+        take = ok & (torch.log(u[:, 1]) < d)
+        acc = acc + torch.where(ok, torch.exp(d.clamp(max=0.0)), torch.zeros_like(d)).mean()
+        q = torch.where(take[:, None], qn, q)
+        g = torch.where(take[:, None], gn, g)
+        lp = torch.where(take, lpn, lp)
+    return q, acc / n_iter
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json")
+    ap.add_argument("--iters", type=int, default=8000)
+    ap.add_argument("--baseline-iters", type=int, default=60)
+    a = ap.parse_args()
+    import torch
+    import wiener_hmc_host as H
+    from bayesflow_nddms_amd import engine, likelihood, mcmc
+    engine.require_device()
+    data_np = H.example_data(D, N, 41)
+    theta = mcmc.hmc_init(data_np, CHAINS, 1).reshape(-1, 5)
+    per = np.repeat(data_np, CHAINS, 0)
+    dev = torch.device("cuda")
+    data = torch.as_tensor(data_np).to(dev)
+    kw = dict(chains_per_dataset=CHAINS, n_leapfrog=LEAPFROG, seed=3)
+    # both routes start from chains that have found the posterior: 300 adapting iterations of the device loop (not timed)
+    st = torch.as_tensor(mcmc.make_state(theta, per, eps0=EPS)).to(dev)
+    engine.wiener_hmc(engine.BASIC_DDM_DC, data, st, n_iter=300, n_adapt=300, want_draws=False, want_log_post=False, **kw)
+    torch.cuda.synchronize()
+    eps = float(torch.exp(st[:, 5]).median())
+    T = torch.as_tensor(np.minimum(1.5, per[..., 0].min(1).astype(np.float64))).to(dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(5)
+
+    def device_loop():
+        s = st.clone()
+        r = engine.wiener_hmc(engine.BASIC_DDM_DC, data, s, n_iter=a.iters, n_adapt=0, iter_offset=300, thin=10, **kw)
+        return r["accept"].mean()
+
+    def baseline():
+        return torch_hmc(torch, engine, likelihood, data, st[:, :5].clone(), T, a.baseline_iters, eps, gen)[1]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        acc = float(fn())                                               # (reading the value back is the synchronise)
+        return time.perf_counter() - t0, acc
+    timed(device_loop)
+    timed(baseline)                                                     # warm-up of every shape the timed windows use
+    dev_t, base_t, dev_acc, base_acc = [], [], [], []
+    for _ in range(3):                                                  # alternating
+        t, x = timed(device_loop)
+        dev_t.append(t / a.iters)
+        dev_acc.append(x)
+        t, x = timed(baseline)
+        base_t.append(t / a.baseline_iters)
+        base_acc.append(x)
+    dev_it, base_it = float(np.median(dev_t)), float(np.median(base_t))
+    rounds = (N + 63) // 64
+    per_launch = engine.wiener_hmc_max_iter(N, LEAPFROG)
+    total = 12_000
+    out = {"tool": "tools/wiener_hmc_rate.py", "device": torch.cuda.get_device_name(0), "chains": D * CHAINS, "n_trials": N, "n_leapfrog": LEAPFROG,
+           "step_size": eps, "timed_iterations": {"device_loop": a.iters, "torch_loop": a.baseline_iters}, "runs": 3,
+           "device_loop": {"seconds_per_iteration_runs": dev_t, "seconds_per_iteration": dev_it, "mean_accept": float(np.mean(dev_acc)),
+                           "seconds_per_leapfrog_step": dev_it / LEAPFROG, "seconds_per_trial_round": dev_it / (LEAPFROG * rounds),
+                           "leapfrog_trials_per_second": D * CHAINS * LEAPFROG * N / dev_it},
+           "torch_loop": {"seconds_per_iteration_runs": base_t, "seconds_per_iteration": base_it, "mean_accept": float(np.mean(base_acc)),
+                          "launches_per_iteration": LEAPFROG, "leapfrog_trials_per_second": D * CHAINS * LEAPFROG * N / base_it},
+           "speedup_device_loop_over_torch_loop": base_it / dev_it,
+           "bounded_launch": {"max_rounds": engine.WHMC_MAX_ROUNDS, "max_iterations_at_this_shape": per_launch,
+                              "seconds_of_a_full_launch": per_launch * dev_it},
+           "projected_fit_2000_plus_10000": {"launches": math.ceil(total / per_launch) + 2, "device_loop_seconds": total * dev_it,
+                                             "torch_loop_seconds": total * base_it}}
+    line = json.dumps(out)
+    print(line)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
