@@ -6,9 +6,9 @@ Host code is Python; the arithmetic lives in hand-written HIP kernels for gfx950
 """
 from .engine import (ALPHA_NOT_SCALED, BASIC_DDM_DC, EXPLICIT_BOUNDARY, SINGLE_TRIAL, SINGLE_TRIAL_ALT, SUMMARY_COLS,
                      SUMMARY_K, GLOBAL_STREAM, StreamState, draw_prior_device, seed, simulate, wiener_cdf, wiener_log_likelihood, wiener_log_likelihood_grad,
-                     wiener_hmc, wiener_marginal_log_likelihood, wiener_marginal_log_likelihood_grad, wiener_quantile)
+                     wiener_hmc, wiener_hmc_joint, wiener_marginal_log_likelihood, wiener_marginal_log_likelihood_grad, wiener_quantile)
 from .diagnostics import rhat_neff
-from .mcmc import hmc_fit, hmc_init, q_to_theta, theta_to_q
+from .mcmc import hmc_fit, hmc_fit_joint, hmc_init, hmc_init_joint, q_to_theta, theta_to_q
 from .likelihood import (diffusion_lpdf, dwiener_logpdf, pwiener, qwiener, single_trial_loglik, single_trial_logpdf, wiener_choice_prob,
                          wiener_loglik, wiener_rt_quantiles)
 
@@ -17,5 +17,6 @@ __all__ = ["ALPHA_NOT_SCALED", "BASIC_DDM_DC", "EXPLICIT_BOUNDARY", "SINGLE_TRIA
            "wiener_log_likelihood", "dwiener_logpdf", "diffusion_lpdf", "wiener_cdf", "pwiener", "wiener_choice_prob",
            "wiener_quantile", "qwiener", "wiener_rt_quantiles", "wiener_log_likelihood_grad", "wiener_loglik",
            "wiener_marginal_log_likelihood", "single_trial_logpdf", "wiener_marginal_log_likelihood_grad", "single_trial_loglik",
-           "wiener_hmc", "hmc_fit", "hmc_init", "theta_to_q", "q_to_theta", "rhat_neff"]
+           "wiener_hmc", "hmc_fit", "hmc_init", "theta_to_q", "q_to_theta", "rhat_neff", "wiener_hmc_joint", "hmc_fit_joint",
+           "hmc_init_joint"]
 __version__ = "0.1.0"

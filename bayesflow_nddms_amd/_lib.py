@@ -8,6 +8,7 @@ from .build import SO_PATH
 NDDM_OK, NDDM_ERR_NULL, NDDM_ERR_SHAPE, NDDM_ERR_PARAM, NDDM_ERR_HIP, NDDM_ERR_NO_DEVICE = range(6)
 GAUSS_EXACT, GAUSS_FAST, BRIDGE, GAUSS_PACKED, STATE_F64 = 0, 1, 2, 4, 8
 QUANTILE_CONDITIONAL = 1             # nddm_wiener_quantile's flag (a namespace of its own)
+HMC_SIGMA_FIXED = 1                  # nddm_wiener_hmc_joint's flag (a namespace of its own)
 ABI_VERSION = 4
 
 _lib = None
@@ -44,6 +45,8 @@ def _declare(L):
     L.nddm_wiener_marginal_log_likelihood_grad.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_float, c.c_uint32, fp, fp, vp]
     L.nddm_wiener_hmc.argtypes = [c.c_int32, fp, c.c_int64, c.c_int32, c.c_int64, c.c_int64, fp, fp, c.c_int32, c.c_int32, c.c_int32, c.c_int32,
                                   c.c_uint32, c.c_uint64, c.c_uint64, c.c_uint64, c.c_uint32, fp, fp, fp, fp, fp, vp]
+    L.nddm_wiener_hmc_joint.argtypes = [c.c_int32, fp, c.c_int64, c.c_int32, c.c_int64, c.c_int64, fp, fp, fp, fp, fp, c.c_int32, c.c_int32, c.c_int32,
+                                        c.c_int32, c.c_uint32, c.c_uint64, c.c_uint64, c.c_uint64, c.c_uint32, fp, fp, fp, fp, fp, fp, fp, vp]
     L.nddm_wiener_quantile.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_uint32, fp, vp]
     L.nddm_simulate.argtypes = [c.c_int32, fp, fp] + common + [c.c_float, c.c_int32, fp, fp, fp, vp]
     L.nddm_simulate_indirect.argtypes = [c.c_int32, fp, fp] + common[:-1] + [fp, c.c_uint32, c.c_float, c.c_int32, fp, fp, fp, vp]
@@ -74,7 +77,7 @@ EXPORTS = [
     "nddm_graph_arena_create", "nddm_graph_arena_bind", "nddm_graph_arena_info", "nddm_graph_arena_release", "nddm_build_info",
     "nddm_simulratcliff", "nddm_wiener_log_likelihood", "nddm_wiener_cdf", "nddm_wiener_quantile",
     "nddm_wiener_log_likelihood_grad", "nddm_wiener_marginal_log_likelihood", "nddm_wiener_marginal_log_likelihood_grad",
-    "nddm_wiener_hmc",
+    "nddm_wiener_hmc", "nddm_wiener_hmc_joint",
 ]
 
 

@@ -92,6 +92,25 @@ def generate_data(test_num=2, nparts=100, ntrials=100, seed=2021, dt=.001, max_s
     return genparam
 
 
+def fit_hmc(genparam_or_y, extdata=None, **kw):
+    """The reference's JAGS fit of this model (alpha_not_scaled.py:138-259: per participant delta, alpha, beta, ndt, varsigma; extdata[p] ~
+    N(alpha[p], sigma); one shared sigma ~ N(3, 1) T(0, 10)) on the device: mcmc.hmc_fit_joint's arguments and its result, the reference's
+    sample layout plus 'sigma' [1, samples // thin, chains].  Takes generate_data's `genparam` dictionary, or the signed response times y
+    [P, n_trials] (y = +-rt, positive = upper boundary) with extdata [P]."""
+    from . import mcmc
+    if isinstance(genparam_or_y, dict):
+        g = genparam_or_y
+        y = np.asarray(g["y"], dtype=np.float64).reshape(int(g["nparts"]), int(g["ntrials"]))
+        extdata = g["extdata"] if extdata is None else extdata
+    else:
+        y = np.atleast_2d(np.asarray(genparam_or_y.detach().cpu().numpy() if hasattr(genparam_or_y, "detach") else genparam_or_y, dtype=np.float64))
+    if extdata is None:
+        raise ValueError("extdata [P] is required with signed response times")
+    if y.ndim != 2:
+        raise ValueError(f"y must have shape [P, n_trials], got {y.shape}")
+    return mcmc.hmc_fit_joint(np.stack([np.abs(y), np.sign(y)], -1).astype(np.float32), extdata, **kw)
+
+
 def log_likelihood(params, y, per_trial=False):
     """log p(y | params) of the generator's model (drift ~ N(Nu, Eta) integrated out, Nu clipped to +-5 as the generator does), one
     launch: params [R, 6] (or [6]) = Nu, Alpha, Beta, Tau, Eta, Varsigma; y [D, n_trials] (or [n_trials]) the signed RTs

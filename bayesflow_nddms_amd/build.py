@@ -19,6 +19,7 @@ HEADERS = [os.path.join(_HERE, "csrc", "nddm_rng.h"), os.path.join(_HERE, "csrc"
            os.path.join(_HERE, "csrc", "nddm_wiener_quantile.h"), os.path.join(_HERE, "csrc", "nddm_wiener_grad.h"),
            os.path.join(_HERE, "csrc", "nddm_wiener_marginal.h"), os.path.join(_HERE, "csrc", "nddm_wiener_marginal_grad.h"),
            os.path.join(_HERE, "csrc", "nddm_wiener_hmc.h"),
+           os.path.join(_HERE, "csrc", "nddm_wiener_hmc_joint.h"),
            os.path.join(os.path.dirname(_HERE), "include", "nddm.h")]
 # -ffp-contract=off: the exact Gaussian transform spells out every fma; contraction would change roundings
 HIPCC_FLAGS = ["-O3", "-ffp-contract=off", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17"]

@@ -55,6 +55,7 @@
 #include "nddm_wiener_cdf.h"
 #include "nddm_wiener_grad.h"
 #include "nddm_wiener_hmc.h"
+#include "nddm_wiener_hmc_joint.h"
 #include "nddm_wiener_marginal.h"
 #include "nddm_wiener_marginal_grad.h"
 #include "nddm_wiener_quantile.h"
@@ -1202,6 +1203,55 @@ int nddm_wiener_hmc(int32_t model, const float *data, int64_t D, int32_t n_trial
     A.free_mask = free_mask; A.N = n_trials; A.n_iter = n_iter; A.n_adapt = n_adapt; A.n_leapfrog = n_leapfrog; A.thin = thin;
     hipLaunchKernelGGL(wiener_hmc_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, A);
     const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? NDDM_OK : fail(NDDM_ERR_HIP, E.launch_msg, hipGetErrorString(e));
+}
+
+/* the alpha_not_scaled JAGS fit: nddm_wiener_hmc's chains coupled by a shared sigma, Metropolis within Gibbs: csrc/nddm_wiener_hmc_joint.h.
+ * The coupling is by launch order: one pre-pass, then per iteration the participant kernel and the sigma kernel, all on the caller's stream. */
+int nddm_wiener_hmc_joint(int32_t model, const float *data, int64_t P, int32_t n_trials, int64_t C, int64_t chains, const double *extdata,
+                          double *state, const double *inv_mass, double *sigma, double *workspace, int32_t n_iter, int32_t n_adapt,
+                          int32_t n_leapfrog, int32_t thin, uint32_t free_mask, uint64_t seed, uint64_t chain_offset, uint64_t iter_offset,
+                          uint32_t flags, float *out_draws, float *out_log_post, float *out_accept, int32_t *out_divergent,
+                          int32_t *out_flagged, float *out_sigma, float *out_sigma_accept, void *stream)
+{
+    using namespace nddm;
+    static const WienerEntry E = {"nddm_wiener_hmc_joint: model %s has no sampler here (NDDM_BASIC_DDM_DC only)",
+                                  "nddm_wiener_hmc_joint: flags must be 0 or NDDM_HMC_SIGMA_FIXED and free_mask < 32%s",
+                                  "C >= 0 chains = P x chains > 0 (P >= 2 when sigma is sampled), 0 < n_trials <= 2048, 0 < n_iter <= 4096, n_leapfrog, "
+                                  "thin > 0, n_adapt >= 0, n_iter x n_leapfrog x ceil(n_trials / 64) <= 2^19 per call and chain / iteration indices "
+                                  "< 2^32 are required%s",
+                                  "data, extdata, state, sigma or workspace is NULL%s", WIENER_NULL_OUT_MSG, "wiener hmc joint kernel launch failed: %s", 4};
+    g_err[0] = 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const bool fixed = (flags & NDDM_HMC_SIGMA_FIXED) != 0u;
+    const bool counts_ok = n_iter > 0 && n_iter <= WHMCJ_MAX_ITER && n_leapfrog > 0 && thin > 0 && n_adapt >= 0 && n_trials <= WHMC_MAX_TRIALS &&
+                           P >= 0 && chains > 0 && C == P * chains && (fixed || P >= 2 || C == 0);
+    const bool shape_ok = counts_ok && (long long)n_iter * n_leapfrog * ((n_trials + 63) / 64) <= WHMC_MAX_ROUNDS &&
+                          chain_offset < (1ull << 32) && chain_offset + (uint64_t)(C > 0 ? C : 0) <= (1ull << 32) &&
+                          iter_offset < (1ull << 32) && iter_offset + (uint64_t)n_iter <= (1ull << 32);
+    bool empty;
+    if (const int rc = wiener_checks(E, model, model == NDDM_BASIC_DDM_DC, (flags & ~NDDM_HMC_SIGMA_FIXED) == 0u && free_mask < 32u, C, chains,
+                                     n_trials, data && extdata && state && sigma && workspace,
+                                     out_draws || out_log_post || out_accept || out_divergent || out_flagged || out_sigma || out_sigma_accept, st,
+                                     &empty, shape_ok)) return rc;
+    if (empty) return NDDM_OK;
+    WienerHmcJointArgs A;
+    A.data = data; A.ext = extdata; A.state = state; A.inv_mass = inv_mass; A.sigma = sigma; A.ws = workspace;
+    A.out_draws = out_draws; A.out_log_post = out_log_post; A.out_accept = out_accept; A.out_divergent = out_divergent; A.out_flagged = out_flagged;
+    A.out_sigma = out_sigma; A.out_sigma_accept = out_sigma_accept;
+    A.P = P; A.S = chains; A.chain_offset = chain_offset; A.iter_offset = iter_offset;
+    A.K = (long long)((iter_offset + (uint64_t)n_iter) / (uint64_t)thin - iter_offset / (uint64_t)thin);
+    A.k0 = (unsigned)seed; A.k1 = (unsigned)(seed >> 32);
+    A.free_mask = free_mask; A.N = n_trials; A.n_iter = n_iter; A.n_adapt = n_adapt; A.n_leapfrog = n_leapfrog; A.thin = thin;
+    A.sigma_fixed = fixed ? 1 : 0; A.it = 0;
+    hipLaunchKernelGGL(wiener_hmc_joint_prepass_kernel, dim3(1), dim3(256), 0, st, A);
+    hipError_t e = hipGetLastError();
+    for (int it = 0; it < n_iter && e == hipSuccess; ++it) {
+        A.it = it;
+        hipLaunchKernelGGL(wiener_hmc_joint_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, A);
+        if (!fixed) hipLaunchKernelGGL(wiener_hmc_joint_sigma_kernel, dim3((unsigned)((chains + 3) / 4)), dim3(256), 0, st, A);
+        e = hipGetLastError();
+    }
     return e == hipSuccess ? NDDM_OK : fail(NDDM_ERR_HIP, E.launch_msg, hipGetErrorString(e));
 }
 

@@ -181,9 +181,19 @@ inline WhmcData whmc_stage(float2 *tile, const float *src, int N, int)
 }
 #endif
 
+// What a posterior may add to the chain's own: nothing (nddm_wiener_hmc), or nddm_wiener_hmc_joint.h's external measurement of the boundary,
+// ext ~ N(boundary, sigma): -(ext - boundary)^2 / (2 sigma^2) on the float64 theta.  `on` is a compile-time switch: the instantiation
+// without the term holds none of its arithmetic.
+struct WhmcNoExt { static constexpr bool on = false; };
+struct WhmcExt {
+    static constexpr bool on = true;
+    double ext, inv_var;        // the measurement and 1 / sigma^2
+};
+
 // log posterior (up to a constant) and its gradient at q, in the unconstrained coordinates; theta: the point in the model's columns
+template <class Ext = WhmcNoExt>
 __device__ __forceinline__ double whmc_log_post(const double (&q)[5], unsigned mask, double T, const float2 *tile, int N, int lane,
-                                                double (&dq)[5], double (&theta)[5])
+                                                double (&dq)[5], double (&theta)[5], const Ext &ext = Ext())
 {
     double sg[5], jac[5], lj = 0.0;
     theta[0] = q[0]; sg[0] = 0.0; jac[0] = 1.0;
@@ -214,9 +224,16 @@ __device__ __forceinline__ double whmc_log_post(const double (&q)[5], unsigned m
     if (mask & 4u) { lp += log(b) + log(1.0 - b); gl[2] += 1.0 / b - 1.0 / (1.0 - b); }
     if (mask & 8u) { lp += -8.0 * (ta - 0.5) * (ta - 0.5); gl[3] += -16.0 * (ta - 0.5); }
     if (mask & 16u) { lp += -2.0 * (sc - 1.0) * (sc - 1.0); gl[4] += -4.0 * (sc - 1.0); }
+    double le = 0.0;
+    if constexpr (Ext::on) {                                            // in theta, before the Jacobian; the value joins the finished sum
+        const double d = ext.ext - a;
+        le = -0.5 * (d * d) * ext.inv_var;
+        gl[1] += d * ext.inv_var;
+    }
     dq[0] = (mask & 1u) ? gl[0] : 0.0;
 #pragma unroll
     for (int j = 1; j < 5; ++j) dq[j] = (mask >> j & 1u) ? gl[j] * jac[j] + (1.0 - 2.0 * sg[j]) : 0.0;
+    if constexpr (Ext::on) return (ll + lp) + le;
     return ll + lp;
 }
 
@@ -241,10 +258,12 @@ struct WhmcTally {
 };
 
 // One chain through iterations [iter_offset, iter_offset + n_iter): st is its state (updated), im its inverse mass; kept draws go to
-// draws / log_post (either may be NULL) through `keep` (lane 0 on the device).  The data set is staged in `tile`.
+// draws / log_post (either may be NULL) through `keep` (lane 0 on the device).  The data set is staged in `tile`.  `ext`: see WhmcNoExt.
+template <class Ext = WhmcNoExt>
 __device__ __forceinline__ WhmcTally whmc_chain(double *st, const double (&im)[5], const float2 *tile, int N, double T, unsigned mask,
                                                 unsigned k0, unsigned k1, unsigned chain, unsigned long long iter_offset, int n_iter,
-                                                int n_adapt, int n_leapfrog, int thin, float *draws, float *log_post, int lane, bool keep)
+                                                int n_adapt, int n_leapfrog, int thin, float *draws, float *log_post, int lane, bool keep,
+                                                const Ext &ext = Ext())
 {
     double q[5], g[5], th[5], sim[5];
 #pragma unroll
@@ -252,7 +271,7 @@ __device__ __forceinline__ WhmcTally whmc_chain(double *st, const double (&im)[5
     double leps = st[5], lbar = st[6], hbar = st[7];
     const double mu = st[8];
     double adapted = st[9], elast = st[10], emax = st[11];
-    double lp = whmc_log_post(q, mask, T, tile, N, lane, g, th);
+    double lp = whmc_log_post(q, mask, T, tile, N, lane, g, th, ext);
     WhmcTally tally = {0.0, 0, 0};
     long long kept = 0;
     for (int it = 0; it < n_iter; ++it) {
@@ -275,7 +294,7 @@ __device__ __forceinline__ WhmcTally whmc_chain(double *st, const double (&im)[5
                 p[j] += 0.5 * eps * gn[j];
                 qn[j] += eps * im[j] * p[j];
             }
-            lpn = whmc_log_post(qn, mask, T, tile, N, lane, gn, thn);
+            lpn = whmc_log_post(qn, mask, T, tile, N, lane, gn, thn, ext);
 #pragma unroll
             for (int j = 0; j < 5; ++j) p[j] += 0.5 * eps * gn[j];
         }

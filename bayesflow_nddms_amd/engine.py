@@ -541,6 +541,114 @@ def wiener_hmc(model, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1
     return res
 
 
+WHMCJ_MAX_ITER = 4096
+
+
+def wiener_hmc_joint_max_iter(n_trials, n_leapfrog):
+    """The most joint iterations one nddm_wiener_hmc_joint call may run: wiener_hmc_max_iter's bound and 4096 (two launches an iteration)."""
+    return min(wiener_hmc_max_iter(n_trials, n_leapfrog), WHMCJ_MAX_ITER)
+
+
+def wiener_hmc_joint(model, data, extdata, state, sigma, inv_mass=None, n_iter=1, n_adapt=0, n_leapfrog=16, thin=1, free_mask=31, seed=0,
+                     chain_offset=0, iter_offset=0, sigma_fixed=False, want_draws=True, want_log_post=True, device=None):
+    """The alpha_not_scaled JAGS fit's sampler: wiener_hmc's chains coupled by one shared sigma, Metropolis within Gibbs (include/nddm.h:
+    nddm_wiener_hmc_joint; csrc/nddm_wiener_hmc_joint.h).  Per joint iteration one participant launch and one sigma launch are enqueued on
+    the current stream; nothing waits on the host.
+
+    model: BASIC_DDM_DC only.  data: [P, n_trials, 2] = (rt, choice), one data set per participant.  extdata: float64 [P], ext_p ~
+    N(boundary_p, sigma).  sigma: float64 [S], one per joint chain, in (0, 10) (any value > 0 with sigma_fixed).  state: float64 [P * S, 12],
+    participant chain c = p * S + k; inv_mass: float64 [P * S, 5] or None.  Device tensors for state and sigma are updated in place.
+    n_iter <= wiener_hmc_joint_max_iter(n_trials, n_leapfrog).  Returns wiener_hmc's dict -- 'log_post' is the participant's conditional
+    log posterior given sigma, the ext term included -- plus 'sigma_draws' float32 [S, K], 'sigma_accept' float32 [S] (the share of the
+    call's sigma proposals accepted; NaN with sigma_fixed) and 'sigma' float64 [S].  Host inputs are shape- and range-checked (ValueError);
+    on the device a data set that cannot be sampled flags every chain, a bad state or sigma its joint chain."""
+    if model != BASIC_DDM_DC:
+        raise ValueError(f"model {model} has no sampler here (BASIC_DDM_DC only)")
+    n_iter, n_adapt, n_leapfrog, thin, free_mask = (int(x) for x in (n_iter, n_adapt, n_leapfrog, thin, free_mask))
+    if n_iter <= 0 or n_leapfrog <= 0 or thin <= 0 or n_adapt < 0:
+        raise ValueError("n_iter, n_leapfrog and thin must be > 0 and n_adapt >= 0")
+    if not 0 <= free_mask < 32:
+        raise ValueError("free_mask has five bits")
+    chain_offset, iter_offset = int(chain_offset), int(iter_offset)
+    if chain_offset < 0 or iter_offset < 0 or iter_offset + n_iter > 1 << 32:
+        raise ValueError("chain_offset and iter_offset must be >= 0 and the iteration index < 2^32")
+    d_rows = (3, 2, "data must have shape [P, n_trials, 2]")
+    d_np = _host_rows(data, *d_rows)
+    if d_np is not None:
+        if not np.all(np.isfinite(d_np)):
+            raise ValueError("data must be finite")
+        if not np.all(np.isin(d_np[..., 1], (-1.0, 1.0))):
+            raise ValueError("the sampler takes (rt, choice) with choice in {1, -1}: a timeout (choice 0) has no gradient here")
+        if np.any(d_np[..., 0] <= 0):
+            raise ValueError("response times must be > 0")
+    P, N = (int(d_np.shape[0]), int(d_np.shape[1])) if d_np is not None else \
+        ((1, int(data.shape[0])) if data.ndim == 2 else (int(data.shape[0]), int(data.shape[1])))
+    if N > WHMC_MAX_TRIALS:
+        raise ValueError(f"n_trials must be <= {WHMC_MAX_TRIALS}")
+    if n_iter > wiener_hmc_joint_max_iter(N, n_leapfrog):
+        raise ValueError(f"one call runs at most {wiener_hmc_joint_max_iter(N, n_leapfrog)} joint iterations at n_trials {N} and n_leapfrog "
+                         f"{n_leapfrog} (n_iter <= 4096 and n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19): cut the run (mcmc.hmc_fit_joint does)")
+    if not sigma_fixed and P < 2:
+        raise ValueError("sampling sigma needs at least 2 participants")
+
+    def arr(x, shape, label):
+        if getattr(x, "is_cuda", False):
+            if tuple(x.shape) != shape or str(x.dtype) != "torch.float64" or not x.is_contiguous():
+                raise ValueError(f"{label} must be a contiguous float64 {list(shape)}")
+            return None
+        a = np.ascontiguousarray(x, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"{label} must have shape {list(shape)}, got {a.shape}")
+        return a
+    g_shape = tuple(sigma.shape) if hasattr(sigma, "shape") else np.shape(sigma)
+    if len(g_shape) != 1 or g_shape[0] < 1:
+        raise ValueError(f"sigma must have shape [S] with S >= 1 joint chains, got {g_shape}")
+    S = int(g_shape[0])
+    C = P * S
+    if chain_offset + C > 1 << 32:
+        raise ValueError("the chain index must stay < 2^32")
+    g_np = arr(sigma, (S,), "sigma")
+    if g_np is not None and not (np.all(np.isfinite(g_np)) and np.all(g_np > 0) and (sigma_fixed or np.all(g_np < 10))):
+        raise ValueError("sigma must be finite and > 0, and < 10 when it is sampled")
+    e_np = arr(extdata, (P,), "extdata")
+    if e_np is not None and not np.all(np.isfinite(e_np)):
+        raise ValueError("extdata must be finite")
+    s_np = arr(state, (C, WHMC_STATE), "state")
+    if s_np is not None and not np.all(np.isfinite(s_np[:, :10])):
+        raise ValueError("state must be finite")
+    m_np = None if inv_mass is None else arr(inv_mass, (C, 5), "inv_mass")
+    if m_np is not None and not (np.all(np.isfinite(m_np)) and np.all(m_np > 0)):
+        raise ValueError("inv_mass must be finite and > 0")
+    torch = require_device()
+    L = _lib.lib()
+    dev = _device(device)
+    K = (iter_offset + n_iter) // thin - iter_offset // thin
+    up = lambda x, a: x if a is None else torch.as_tensor(a, dtype=torch.float64).to(dev)
+    with torch.cuda.device(dev):
+        d_dev = _device_rows(data, d_np, dev, *d_rows)
+        e_dev, s_dev, g_dev = up(extdata, e_np), up(state, s_np), up(sigma, g_np)
+        m_dev = None if inv_mass is None else up(inv_mass, m_np)
+        ws = torch.empty((C + S, 4), dtype=torch.float64, device=dev)
+        res = {"draws": torch.empty((C, K, 5), dtype=torch.float32, device=dev) if want_draws else None,
+               "log_post": torch.empty((C, K), dtype=torch.float32, device=dev) if want_log_post else None,
+               "accept": torch.empty((C,), dtype=torch.float32, device=dev), "divergent": torch.empty((C,), dtype=torch.int32, device=dev),
+               "flagged": torch.empty((C,), dtype=torch.int32, device=dev), "sigma_draws": torch.empty((S, K), dtype=torch.float32, device=dev),
+               "sigma_accept": torch.empty((S,), dtype=torch.float32, device=dev)}
+        st = torch.cuda.current_stream(dev)
+        _lib.check(L.nddm_wiener_hmc_joint(int(model), _ptr(d_dev), P, N, C, S, _ptr(e_dev), _ptr(s_dev), _ptr(m_dev), _ptr(g_dev), _ptr(ws),
+                                           n_iter, n_adapt, n_leapfrog, thin, free_mask, _u64(seed), chain_offset, iter_offset,
+                                           _lib.HMC_SIGMA_FIXED if sigma_fixed else 0, _ptr(res["draws"]), _ptr(res["log_post"]),
+                                           _ptr(res["accept"]), _ptr(res["divergent"]), _ptr(res["flagged"]), _ptr(res["sigma_draws"]),
+                                           _ptr(res["sigma_accept"]), st.cuda_stream))
+        for t in (d_dev, e_dev, s_dev, g_dev, m_dev, ws):
+            if t is not None:
+                t.record_stream(st)
+    res = {k: v for k, v in res.items() if v is not None}
+    res["state"] = s_dev
+    res["sigma"] = g_dev
+    return res
+
+
 # kernel launches wiener_log_likelihood_grad has made in this process (tests count them: one per forward plus backward)
 _WIENER_GRAD_LAUNCHES = [0]
 

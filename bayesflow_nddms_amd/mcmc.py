@@ -200,5 +200,105 @@ def hmc_fit(data, chains=6, warmup=2000, samples=10000, thin=10, n_leapfrog=16, 
     return out
 
 
+def hmc_init_joint(data, chains, seed):
+    """The reference's initial values of the alpha_not_scaled fit (alpha_not_scaled.py:233-244): hmc_init's for the participants (alpha and
+    varsigma U(.5, 2), beta U(.2, .8), delta U(-4, 4), ndt U(0, min rt / 2)) and sigma U(.01, 5) per joint chain -> (theta float64 [P, chains,
+    5], sigma float64 [chains])."""
+    theta = hmc_init(data, chains, seed)
+    sigma = np.random.default_rng([int(seed), 0x516]).uniform(0.01, 5.0, int(chains))
+    return theta, sigma
+
+
+def _run_joint(call, data, ext, state, sigma, inv_mass, n_iter, n_adapt, iter_offset, max_iter, thin, **kw):
+    """_run for the joint sampler -> (the calls' results, the state, sigma)."""
+    out, done = [], 0
+    while done < n_iter:
+        n = min(max_iter, n_iter - done)
+        r = call(engine.BASIC_DDM_DC, data, ext, state, sigma, inv_mass=inv_mass, n_iter=n, n_adapt=n_adapt, thin=thin, iter_offset=iter_offset + done,
+                 **kw)
+        state, sigma = r["state"], r["sigma"]
+        out.append(r)
+        done += n
+    return out, state, sigma
+
+
+def hmc_fit_joint(data, extdata, chains=6, warmup=2000, samples=10000, thin=10, n_leapfrog=16, free=PARAM_NAMES, fixed=None, seed=0,
+                  eps0=0.05, device=None, _call=None):
+    """Fit the alpha_not_scaled JAGS model (alpha_not_scaled.py:138-259): every participant of data [P, n_trials, 2] = (rt, choice in {1,
+    -1}) has basic_ddm_dc's five parameters, extdata [P] ~ N(alpha_p, sigma) measures the boundary, and one sigma ~ N(3, 1) T(0, 10) is
+    shared -- `chains` JOINT chains of P participant chains and a sigma each, side by side on the device (engine.wiener_hmc_joint), the
+    defaults the reference's: 6 chains, 2000 + 10 000 iterations, thin 10.
+
+    free / fixed: hmc_fit's; `fixed` may also name "sigma" (held at that value, never sampled).  The warm-up is hmc_fit's two stages.
+    Returns hmc_fit's dictionary (each variable float64 [P, samples // thin, chains]; 'log_post' is the participant's conditional log
+    posterior given sigma) plus 'sigma' float64 [1, samples // thin, chains] -- the shape pyjags gives a scalar node, so
+    diagnostics.rhat_neff(fit) takes it as it stands -- and 'sigma_accept' [chains], the share of the sampling iterations' sigma proposals
+    accepted (NaN when sigma is fixed)."""
+    call = _call or (lambda *a, **k: engine.wiener_hmc_joint(*a, device=device, **k))
+    d = np.asarray(data.detach().cpu().numpy() if hasattr(data, "detach") else data, dtype=np.float32)
+    if d.ndim == 2:
+        d = d[None]
+    if d.ndim != 3 or d.shape[-1] != 2:
+        raise ValueError(f"data must have shape [P, n_trials, 2], got {d.shape}")
+    P, N = d.shape[0], d.shape[1]
+    ext = np.asarray(extdata.detach().cpu().numpy() if hasattr(extdata, "detach") else extdata, dtype=np.float64).reshape(-1)
+    if ext.shape != (P,) or not np.all(np.isfinite(ext)):
+        raise ValueError(f"extdata must hold one finite value per participant ({P}), got shape {ext.shape}")
+    chains, warmup, samples, thin = int(chains), int(warmup), int(samples), int(thin)
+    if chains < 1 or warmup < 4 or samples < 1 or thin < 1 or samples % thin:
+        raise ValueError("chains >= 1, warmup >= 4, samples >= 1 and thin dividing samples are required")
+    mask = free_mask(free)
+    fixed = {} if fixed is None else dict(fixed)
+    sigma_fixed = "sigma" in fixed
+    sigma_value = float(fixed.pop("sigma")) if sigma_fixed else None
+    if sigma_fixed and not (np.isfinite(sigma_value) and sigma_value > 0):
+        raise ValueError("a fixed sigma must be finite and > 0")
+    if not sigma_fixed and P < 2:
+        raise ValueError("sampling sigma needs at least 2 participants: fix it (fixed={'sigma': value}) or bring more")
+    for k in fixed:
+        if k not in PARAM_NAMES:
+            raise ValueError(f"unknown fixed column {k!r}: the columns are {PARAM_NAMES} and 'sigma'")
+        mask &= ~(1 << PARAM_NAMES.index(k))
+    theta, sigma = hmc_init_joint(d, chains, seed)
+    if sigma_fixed:
+        sigma = np.full(chains, sigma_value)
+    for k, v in fixed.items():
+        theta[..., PARAM_NAMES.index(k)] = float(v)
+    per_chain = np.repeat(d, chains, 0)
+    state = make_state(theta.reshape(-1, 5), per_chain, eps0=eps0, free=mask)
+    max_iter = engine.wiener_hmc_joint_max_iter(N, n_leapfrog)
+    if max_iter < 1:
+        raise ValueError("n_leapfrog is too large for one bounded call")
+    kw = dict(n_leapfrog=n_leapfrog, free_mask=mask, seed=seed, sigma_fixed=sigma_fixed)
+    w1 = warmup // 2
+    h1 = w1 // 2
+    _, state, sigma = _run_joint(call, d, ext, state, sigma, None, h1, w1, 0, max_iter, 1, want_draws=False, want_log_post=False, **kw)
+    res, state, sigma = _run_joint(call, d, ext, state, sigma, None, w1 - h1, w1, h1, max_iter, 1, want_log_post=False, **kw)
+    th = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)
+    lo, wd = _support(per_chain)
+    x = np.clip((th - lo[:, None, :]) / wd[:, None, :], 1e-7, 1.0 - 1e-7)
+    qs = np.where(np.array([False] + [bool(mask >> j & 1) for j in range(1, 5)]), np.log(x) - np.log1p(-x), th)
+    var = np.var(qs, axis=1) if qs.shape[1] > 1 else np.ones((P * chains, 5))
+    inv_mass = np.where(np.isfinite(var), np.maximum(var, 1e-3), 1.0)
+    state = restart_adaptation(_host(state))
+    w2 = warmup - w1
+    _, state, sigma = _run_joint(call, d, ext, state, sigma, inv_mass, w2, w2, w1, max_iter, 1, want_draws=False, want_log_post=False, **kw)
+    res, state, sigma = _run_joint(call, d, ext, state, sigma, inv_mass, samples, w2, warmup, max_iter, thin, **kw)
+    draws = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)
+    lp = np.concatenate([_host(r["log_post"]) for r in res], 1).astype(np.float64)
+    sg = np.concatenate([_host(r["sigma_draws"]) for r in res], 1).astype(np.float64)                # [chains, K]
+    K = draws.shape[1]
+    n_samp = np.array([min(max_iter, samples - i * max_iter) for i in range(len(res))], dtype=np.float64)
+    acc = sum(_host(r["accept"]).astype(np.float64) * n for r, n in zip(res, n_samp)) / n_samp.sum()
+    out = {JAGS_NAMES[name]: draws[:, :, j].reshape(P, chains, K).transpose(0, 2, 1) for j, name in enumerate(PARAM_NAMES)}
+    out["log_post"] = lp.reshape(P, chains, K).transpose(0, 2, 1)
+    out["accept_rate"] = acc.reshape(P, chains)
+    out["n_divergent"] = sum(_host(r["divergent"]).astype(np.int64) for r in res).reshape(P, chains)
+    out["flagged"] = _host(res[0]["flagged"]).astype(np.int64).reshape(P, chains)
+    out["sigma"] = sg.T[None]
+    out["sigma_accept"] = sum(_host(r["sigma_accept"]).astype(np.float64) * n for r, n in zip(res, n_samp)) / n_samp.sum()
+    return out
+
+
 def _host(t):
     return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)

@@ -74,6 +74,7 @@ extern "C" {
 /* 4 (additive): nddm_wiener_marginal_log_likelihood.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_marginal_log_likelihood_grad.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_hmc.  No existing entry point changes. */
+/* 4 (additive): nddm_wiener_hmc_joint.  No existing entry point changes. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -327,6 +328,37 @@ int nddm_wiener_hmc(int32_t model, const float *data /* [D, n_trials, 2] */, int
                     int32_t n_adapt, int32_t n_leapfrog, int32_t thin, uint32_t free_mask, uint64_t seed, uint64_t chain_offset,
                     uint64_t iter_offset, uint32_t flags /* 0, reserved */, float *out_draws, float *out_log_post, float *out_accept,
                     int32_t *out_divergent, int32_t *out_flagged, void *stream);
+
+/* The alpha_not_scaled JAGS fit (alpha_not_scaled.py:138-259): nddm_wiener_hmc's chains coupled by one shared sigma.  Participant p has
+ * nddm_wiener_hmc's posterior plus an external measurement extdata[p] ~ N(boundary_p, sigma); sigma ~ N(3, 1) on (0, 10) is shared by all P
+ * participants of a joint chain.  Metropolis within Gibbs, n_iter joint iterations per call: per iteration one participant kernel (one
+ * iteration of nddm_wiener_hmc's chain for every (p, k), the log posterior gaining -(ext_p - boundary_p)^2 / (2 sigma_k^2)) and then one
+ * sigma kernel (an independence Metropolis step on sigma_k's conditional) are enqueued on `stream`, after one pre-pass kernel: 2 n_iter + 1
+ * launches, no host synchronisation, no cooperative launch, no atomics.  (ABI 4, additive)
+ *   arguments as nddm_wiener_hmc's, D = P participants, chains_per_dataset = S joint chains, C = P * S, participant chain c = p * S + k, and
+ *   extdata            device f64 [P]
+ *   sigma              device f64 [S], in and out
+ *   workspace          device f64 [P * S + S, 4], the caller's: the call's accept and divergence accumulators.  The entry allocates nothing
+ *   flags              0 or NDDM_HMC_SIGMA_FIXED: sigma is held and no sigma kernel is launched
+ *   n_iter             <= 4096 per call (and nddm_wiener_hmc's n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19); P >= 2 when sigma is
+ *                      sampled (NDDM_ERR_SHAPE); a run cut into calls gives the bits of the uncut run
+ *   outputs, each may be NULL, not all: nddm_wiener_hmc's five, out_sigma f32 [S, K] (sigma after both parts of a kept iteration) and
+ *                      out_sigma_accept f32 [S] (the share of the call's sigma proposals accepted; NaN with NDDM_HMC_SIGMA_FIXED).
+ *                      out_log_post [C, K] is the participant's CONDITIONAL log posterior in q given sigma: it includes the ext term and
+ *                      excludes -log sigma and sigma's prior.  The joint log density of joint chain k at a kept draw, up to a constant, is
+ *                      sum_p out_log_post[p * S + k] - P log sigma_k - (sigma_k - 3)^2 / 2.
+ * A data set that cannot be sampled flags EVERY chain of the call; joint chain k alone is flagged when the incoming state or inverse mass of
+ * any (p, k) is not finite, or sigma_k is not finite and > 0 (or not < 10 when sampled).  A flagged joint chain runs no iteration: sigma and
+ * states unchanged, draws and out_sigma NaN, out_flagged = 1 for its P chains, the others' bits unaffected.  The order and the status codes of
+ * the checks are nddm_wiener_hmc's.  csrc/nddm_wiener_hmc_joint.h, DESIGN.md section 18. */
+#define NDDM_HMC_SIGMA_FIXED 1u
+int nddm_wiener_hmc_joint(int32_t model, const float *data /* [P, n_trials, 2] */, int64_t P, int32_t n_trials, int64_t C,
+                          int64_t chains /* S */, const double *extdata /* [P] */, double *state /* [C, 12] */,
+                          const double *inv_mass /* [C, 5] or NULL */, double *sigma /* [S] */, double *workspace /* [C + S, 4] */,
+                          int32_t n_iter, int32_t n_adapt, int32_t n_leapfrog, int32_t thin, uint32_t free_mask, uint64_t seed,
+                          uint64_t chain_offset, uint64_t iter_offset, uint32_t flags, float *out_draws, float *out_log_post,
+                          float *out_accept, int32_t *out_divergent, int32_t *out_flagged, float *out_sigma, float *out_sigma_accept,
+                          void *stream);
 
 /* The single-trial model's MARGINAL log-likelihood: the per-trial boundary a ~ N(mu_alpha, std_alpha^2) | a > 0 is latent, z1 ~ N(gamma a,
  * sigma1^2) observes it, and the response is the first passage of the Wiener process with boundary a; the latent is integrated out, one
