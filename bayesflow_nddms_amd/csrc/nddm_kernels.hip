@@ -751,6 +751,12 @@ static int wiener_plan(int64_t S, int64_t R, int rows, bool *staged, long long *
     return fail(NDDM_ERR_SHAPE, "too many workgroups for one launch (R / %s must be < 2^31)", r);
 }
 
+// The status of the last launch (e: hipGetLastError()'s, which clears it), in the entry point's words
+static int launch_status(hipError_t e, const char *launch_msg)
+{
+    return e == hipSuccess ? NDDM_OK : fail(NDDM_ERR_HIP, launch_msg, hipGetErrorString(e));
+}
+
 // Checks, plan and the one kernel launch (no scratch memory, nothing to synchronise: capturable like a plain kernel).  A: the entry point's
 // outputs and extra fields; kernels: its model's {paired, staged} instantiations.
 template <class Args>
@@ -766,8 +772,33 @@ static int wiener_launch(const WienerEntry &E, int32_t model, bool model_ok, boo
     long long blocks;
     if (const int rc = wiener_plan(S, R, E.rows, &staged, &A.chunks, &blocks)) return rc;
     hipLaunchKernelGGL(kernels[staged], dim3((unsigned)blocks), dim3(256), 0, st, A);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? NDDM_OK : fail(NDDM_ERR_HIP, E.launch_msg, hipGetErrorString(e));
+    return launch_status(hipGetLastError(), E.launch_msg);
+}
+
+// ---- what nddm_wiener_hmc and nddm_wiener_hmc_joint share on the host ---------------------------------------------------------------------
+// The counts and bounds both require (C chains = sets x per_set); each entry point adds the terms that are its own.
+static bool whmc_shape_ok(int64_t sets, int64_t per_set, int64_t C, int32_t n_trials, int32_t n_iter, int32_t n_adapt, int32_t n_leapfrog,
+                          int32_t thin, uint64_t chain_offset, uint64_t iter_offset)
+{
+    const bool counts_ok = n_iter > 0 && n_leapfrog > 0 && thin > 0 && n_adapt >= 0 && n_trials <= WHMC_MAX_TRIALS && sets >= 0 && per_set > 0 &&
+                           C == sets * per_set;
+    return counts_ok && (long long)n_iter * n_leapfrog * ((n_trials + 63) / 64) <= WHMC_MAX_ROUNDS &&
+           chain_offset < (1ull << 32) && chain_offset + (uint64_t)(C > 0 ? C : 0) <= (1ull << 32) &&
+           iter_offset < (1ull << 32) && iter_offset + (uint64_t)n_iter <= (1ull << 32);
+}
+
+// The fields WienerHmcArgs and WienerHmcJointArgs have in common
+template <class Args>
+static void whmc_fill(Args &A, const float *data, double *state, const double *inv_mass, int64_t per_set, int32_t n_trials, int32_t n_iter,
+                      int32_t n_adapt, int32_t n_leapfrog, int32_t thin, uint32_t free_mask, uint64_t seed, uint64_t chain_offset,
+                      uint64_t iter_offset, float *out_draws, float *out_log_post, float *out_accept, int32_t *out_divergent, int32_t *out_flagged)
+{
+    A.data = data; A.state = state; A.inv_mass = inv_mass;
+    A.out_draws = out_draws; A.out_log_post = out_log_post; A.out_accept = out_accept; A.out_divergent = out_divergent; A.out_flagged = out_flagged;
+    A.S = per_set; A.chain_offset = chain_offset; A.iter_offset = iter_offset;
+    A.K = (long long)((iter_offset + (uint64_t)n_iter) / (uint64_t)thin - iter_offset / (uint64_t)thin);
+    A.k0 = (unsigned)seed; A.k1 = (unsigned)(seed >> 32);
+    A.free_mask = free_mask; A.N = n_trials; A.n_iter = n_iter; A.n_adapt = n_adapt; A.n_leapfrog = n_leapfrog; A.thin = thin;
 }
 
 }  // namespace nddm
@@ -1184,26 +1215,18 @@ int nddm_wiener_hmc(int32_t model, const float *data, int64_t D, int32_t n_trial
                                   "data or state is NULL%s", WIENER_NULL_OUT_MSG, "wiener hmc kernel launch failed: %s", 4};
     g_err[0] = 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool counts_ok = n_iter > 0 && n_leapfrog > 0 && thin > 0 && n_adapt >= 0 && n_trials <= WHMC_MAX_TRIALS && D >= 0 &&
-                           chains_per_dataset > 0 && C == D * chains_per_dataset;
-    const bool shape_ok = counts_ok && (long long)n_iter * n_leapfrog * ((n_trials + 63) / 64) <= WHMC_MAX_ROUNDS &&
-                          chain_offset < (1ull << 32) && chain_offset + (uint64_t)(C > 0 ? C : 0) <= (1ull << 32) &&
-                          iter_offset < (1ull << 32) && iter_offset + (uint64_t)n_iter <= (1ull << 32);
+    const bool shape_ok = whmc_shape_ok(D, chains_per_dataset, C, n_trials, n_iter, n_adapt, n_leapfrog, thin, chain_offset, iter_offset);
     bool empty;
     if (const int rc = wiener_checks(E, model, model == NDDM_BASIC_DDM_DC, flags == 0u && free_mask < 32u, C, chains_per_dataset, n_trials,
                                      data && state, out_draws || out_log_post || out_accept || out_divergent || out_flagged, st, &empty,
                                      shape_ok)) return rc;
     if (empty) return NDDM_OK;
     WienerHmcArgs A;
-    A.data = data; A.state = state; A.inv_mass = inv_mass;
-    A.out_draws = out_draws; A.out_log_post = out_log_post; A.out_accept = out_accept; A.out_divergent = out_divergent; A.out_flagged = out_flagged;
-    A.C = C; A.S = chains_per_dataset; A.chain_offset = chain_offset; A.iter_offset = iter_offset;
-    A.K = (long long)((iter_offset + (uint64_t)n_iter) / (uint64_t)thin - iter_offset / (uint64_t)thin);
-    A.k0 = (unsigned)seed; A.k1 = (unsigned)(seed >> 32);
-    A.free_mask = free_mask; A.N = n_trials; A.n_iter = n_iter; A.n_adapt = n_adapt; A.n_leapfrog = n_leapfrog; A.thin = thin;
+    whmc_fill(A, data, state, inv_mass, chains_per_dataset, n_trials, n_iter, n_adapt, n_leapfrog, thin, free_mask, seed, chain_offset, iter_offset,
+              out_draws, out_log_post, out_accept, out_divergent, out_flagged);
+    A.C = C;
     hipLaunchKernelGGL(wiener_hmc_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, A);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? NDDM_OK : fail(NDDM_ERR_HIP, E.launch_msg, hipGetErrorString(e));
+    return launch_status(hipGetLastError(), E.launch_msg);
 }
 
 /* the alpha_not_scaled JAGS fit: nddm_wiener_hmc's chains coupled by a shared sigma, Metropolis within Gibbs: csrc/nddm_wiener_hmc_joint.h.
@@ -1224,11 +1247,8 @@ int nddm_wiener_hmc_joint(int32_t model, const float *data, int64_t P, int32_t n
     g_err[0] = 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool fixed = (flags & NDDM_HMC_SIGMA_FIXED) != 0u;
-    const bool counts_ok = n_iter > 0 && n_iter <= WHMCJ_MAX_ITER && n_leapfrog > 0 && thin > 0 && n_adapt >= 0 && n_trials <= WHMC_MAX_TRIALS &&
-                           P >= 0 && chains > 0 && C == P * chains && (fixed || P >= 2 || C == 0);
-    const bool shape_ok = counts_ok && (long long)n_iter * n_leapfrog * ((n_trials + 63) / 64) <= WHMC_MAX_ROUNDS &&
-                          chain_offset < (1ull << 32) && chain_offset + (uint64_t)(C > 0 ? C : 0) <= (1ull << 32) &&
-                          iter_offset < (1ull << 32) && iter_offset + (uint64_t)n_iter <= (1ull << 32);
+    const bool shape_ok = whmc_shape_ok(P, chains, C, n_trials, n_iter, n_adapt, n_leapfrog, thin, chain_offset, iter_offset) &&
+                          n_iter <= WHMCJ_MAX_ITER && (fixed || P >= 2 || C == 0);
     bool empty;
     if (const int rc = wiener_checks(E, model, model == NDDM_BASIC_DDM_DC, (flags & ~NDDM_HMC_SIGMA_FIXED) == 0u && free_mask < 32u, C, chains,
                                      n_trials, data && extdata && state && sigma && workspace,
@@ -1236,14 +1256,10 @@ int nddm_wiener_hmc_joint(int32_t model, const float *data, int64_t P, int32_t n
                                      &empty, shape_ok)) return rc;
     if (empty) return NDDM_OK;
     WienerHmcJointArgs A;
-    A.data = data; A.ext = extdata; A.state = state; A.inv_mass = inv_mass; A.sigma = sigma; A.ws = workspace;
-    A.out_draws = out_draws; A.out_log_post = out_log_post; A.out_accept = out_accept; A.out_divergent = out_divergent; A.out_flagged = out_flagged;
-    A.out_sigma = out_sigma; A.out_sigma_accept = out_sigma_accept;
-    A.P = P; A.S = chains; A.chain_offset = chain_offset; A.iter_offset = iter_offset;
-    A.K = (long long)((iter_offset + (uint64_t)n_iter) / (uint64_t)thin - iter_offset / (uint64_t)thin);
-    A.k0 = (unsigned)seed; A.k1 = (unsigned)(seed >> 32);
-    A.free_mask = free_mask; A.N = n_trials; A.n_iter = n_iter; A.n_adapt = n_adapt; A.n_leapfrog = n_leapfrog; A.thin = thin;
-    A.sigma_fixed = fixed ? 1 : 0; A.it = 0;
+    whmc_fill(A, data, state, inv_mass, chains, n_trials, n_iter, n_adapt, n_leapfrog, thin, free_mask, seed, chain_offset, iter_offset, out_draws,
+              out_log_post, out_accept, out_divergent, out_flagged);
+    A.ext = extdata; A.sigma = sigma; A.ws = workspace; A.out_sigma = out_sigma; A.out_sigma_accept = out_sigma_accept;
+    A.P = P; A.sigma_fixed = fixed ? 1 : 0; A.it = 0;
     hipLaunchKernelGGL(wiener_hmc_joint_prepass_kernel, dim3(1), dim3(256), 0, st, A);
     hipError_t e = hipGetLastError();
     for (int it = 0; it < n_iter && e == hipSuccess; ++it) {
@@ -1252,7 +1268,7 @@ int nddm_wiener_hmc_joint(int32_t model, const float *data, int64_t P, int32_t n
         if (!fixed) hipLaunchKernelGGL(wiener_hmc_joint_sigma_kernel, dim3((unsigned)((chains + 3) / 4)), dim3(256), 0, st, A);
         e = hipGetLastError();
     }
-    return e == hipSuccess ? NDDM_OK : fail(NDDM_ERR_HIP, E.launch_msg, hipGetErrorString(e));
+    return launch_status(e, E.launch_msg);
 }
 
 /* the single-trial model's marginal log-likelihood (the latent per-trial boundary integrated out by quadrature): csrc/nddm_wiener_marginal.h */

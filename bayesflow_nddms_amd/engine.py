@@ -457,23 +457,17 @@ def wiener_hmc_max_iter(n_trials, n_leapfrog):
     return max(WHMC_MAX_ROUNDS // (int(n_leapfrog) * ((int(n_trials) + 63) // 64)), 0)
 
 
-def wiener_hmc(model, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1, n_adapt=0, n_leapfrog=16, thin=1, free_mask=31, seed=0,
-               chain_offset=0, iter_offset=0, want_draws=True, want_log_post=True, device=None):
-    """Batched Hamiltonian Monte Carlo over the basic_ddm_dc Wiener posterior, one wave per chain, all n_iter iterations in ONE launch
-    (include/nddm.h: nddm_wiener_hmc; the chain: csrc/nddm_wiener_hmc.h).
-
-    model: BASIC_DDM_DC only.  data: [D, n_trials, 2] = (rt, choice), n_trials <= 2048.  state: float64 [C, 12], C = D *
-    chains_per_dataset, chain c on data set c // chains_per_dataset (mcmc.make_state builds one; a device tensor is updated in place).
-    inv_mass: float64 [C, 5] or None (ones).  One launch is bounded: n_iter <= wiener_hmc_max_iter(n_trials, n_leapfrog); mcmc.hmc_fit
-    cuts a long run into such launches.  Returns a dict of device tensors: 'draws' float32 [C, K, 5] in the model's columns, 'log_post'
-    float32 [C, K], 'accept' float32 [C], 'divergent' int32 [C], 'flagged' int32 [C] and 'state' float64 [C, 12]; K = (iter_offset +
-    n_iter) // thin - iter_offset // thin.  Host inputs are shape- and range-checked (ValueError); a data set that cannot be sampled (a
-    timeout, a non-finite value, an rt <= 0) that arrives on the device flags its chains instead."""
+def _hmc_host_checks(model, data, sets, n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset, max_iter_of, bound,
+                     chains_per_dataset=None):
+    """The front end wiener_hmc and wiener_hmc_joint share, up to the launch bound: host inputs are refused here (ValueError), before any
+    device work.  sets: the letter of data's first axis; max_iter_of / bound: the sampler's launch bound and its sentence ({m}: the bound,
+    {N}, {L}); chains_per_dataset: wiener_hmc's.  -> (the counts, mask and offsets as ints, data's row description, its host array or None,
+    the number of data sets, n_trials)."""
     if model != BASIC_DDM_DC:
         raise ValueError(f"model {model} has no sampler here (BASIC_DDM_DC only)")
-    S, n_iter, n_adapt, n_leapfrog, thin, free_mask = (int(x) for x in (chains_per_dataset, n_iter, n_adapt, n_leapfrog, thin, free_mask))
-    if S <= 0:
+    if chains_per_dataset is not None and int(chains_per_dataset) <= 0:
         raise ValueError("chains_per_dataset must be > 0")
+    n_iter, n_adapt, n_leapfrog, thin, free_mask = (int(x) for x in (n_iter, n_adapt, n_leapfrog, thin, free_mask))
     if n_iter <= 0 or n_leapfrog <= 0 or thin <= 0 or n_adapt < 0:
         raise ValueError("n_iter, n_leapfrog and thin must be > 0 and n_adapt >= 0")
     if not 0 <= free_mask < 32:
@@ -481,7 +475,7 @@ def wiener_hmc(model, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1
     chain_offset, iter_offset = int(chain_offset), int(iter_offset)
     if chain_offset < 0 or iter_offset < 0 or iter_offset + n_iter > 1 << 32:
         raise ValueError("chain_offset and iter_offset must be >= 0 and the iteration index < 2^32")
-    d_rows = (3, 2, "data must have shape [D, n_trials, 2]")
+    d_rows = (3, 2, f"data must have shape [{sets}, n_trials, 2]")
     d_np = _host_rows(data, *d_rows)
     if d_np is not None:
         if not np.all(np.isfinite(d_np)):
@@ -494,50 +488,87 @@ def wiener_hmc(model, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1
         ((1, int(data.shape[0])) if data.ndim == 2 else (int(data.shape[0]), int(data.shape[1])))
     if N > WHMC_MAX_TRIALS:
         raise ValueError(f"n_trials must be <= {WHMC_MAX_TRIALS}")
-    if n_iter > wiener_hmc_max_iter(N, n_leapfrog):
-        raise ValueError(f"one launch runs at most {wiener_hmc_max_iter(N, n_leapfrog)} iterations at n_trials {N} and n_leapfrog {n_leapfrog} "
-                         "(n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19): cut the run (mcmc.hmc_fit does)")
-    C = D * S
+    if n_iter > max_iter_of(N, n_leapfrog):
+        raise ValueError(bound.format(m=max_iter_of(N, n_leapfrog), N=N, L=n_leapfrog))
+    return (n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset), d_rows, d_np, D, N
+
+
+def _hmc_f64(x, shape, label, note=""):
+    """A sampler's float64 input of a given shape: a device tensor is checked and left where it is (-> None), anything else -> its host
+    array."""
+    if getattr(x, "is_cuda", False):
+        if tuple(x.shape) != shape or str(x.dtype) != "torch.float64" or not x.is_contiguous():
+            raise ValueError(f"{label} must be a contiguous float64 {list(shape)}")
+        return None
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError(f"{label} must have shape {list(shape)}{note}, got {a.shape}")
+    return a
+
+
+def _hmc_chain_checks(C, chain_offset, state, inv_mass, note="", own=lambda: {}):
+    """The chain index, then the sampler's `own` inputs (-> {name: (value, host array or None)}), state [C, 12] and inv_mass [C, 5] or None
+    -> the float64 inputs {name: (value, host array or None)}, the sampler's own first."""
     if chain_offset + C > 1 << 32:
         raise ValueError("the chain index must stay < 2^32")
-
-    def rows(x, last, label):
-        if getattr(x, "is_cuda", False):
-            if tuple(x.shape) != (C, last) or str(x.dtype) != "torch.float64" or not x.is_contiguous():
-                raise ValueError(f"{label} must be a contiguous float64 [{C}, {last}]")
-            return None
-        a = np.ascontiguousarray(x, dtype=np.float64)
-        if a.shape != (C, last):
-            raise ValueError(f"{label} must have shape [{C}, {last}] (D {D} x chains_per_dataset {S}), got {a.shape}")
-        return a
-    s_np = rows(state, WHMC_STATE, "state")
+    f64 = own()
+    s_np = _hmc_f64(state, (C, WHMC_STATE), "state", note)
     if s_np is not None and not np.all(np.isfinite(s_np[:, :10])):
         raise ValueError("state must be finite")
-    m_np = None if inv_mass is None else rows(inv_mass, 5, "inv_mass")
+    m_np = None if inv_mass is None else _hmc_f64(inv_mass, (C, 5), "inv_mass", note)
     if m_np is not None and not (np.all(np.isfinite(m_np)) and np.all(m_np > 0)):
         raise ValueError("inv_mass must be finite and > 0")
+    return dict(f64, state=(state, s_np), inv_mass=(inv_mass, m_np))
+
+
+def _hmc_device_call(data, d_rows, d_np, f64, C, K, want_draws, want_log_post, own, device, call, always=False):
+    """The device half the two samplers share.  f64: _hmc_chain_checks' inputs; own: (key, shape, torch dtype's name) of the sampler's
+    further buffers; call(L, data pointer, {name: input pointer}, {key: output pointer or None}, stream handle) makes the one library call and
+    checks its status -- for no chain only if `always`.  -> ({key: device tensor} of the wanted outputs and `own`, {name: device tensor}
+    of the inputs)."""
     torch = require_device()
     L = _lib.lib()
     dev = _device(device)
-    K = (iter_offset + n_iter) // thin - iter_offset // thin
     with torch.cuda.device(dev):
         d_dev = _device_rows(data, d_np, dev, *d_rows)
-        s_dev = state if s_np is None else torch.as_tensor(s_np, dtype=torch.float64).to(dev)
-        m_dev = None if inv_mass is None else (inv_mass if m_np is None else torch.as_tensor(m_np, dtype=torch.float64).to(dev))
-        res = {"draws": torch.empty((C, K, 5), dtype=torch.float32, device=dev) if want_draws else None,
-               "log_post": torch.empty((C, K), dtype=torch.float32, device=dev) if want_log_post else None,
-               "accept": torch.empty((C,), dtype=torch.float32, device=dev), "divergent": torch.empty((C,), dtype=torch.int32, device=dev),
-               "flagged": torch.empty((C,), dtype=torch.int32, device=dev)}
-        if C > 0:
+        ins = {k: x if a is None else torch.as_tensor(a, dtype=torch.float64).to(dev) for k, (x, a) in f64.items()}
+        res = {key: torch.empty(shape, dtype=getattr(torch, dtype), device=dev) if wanted else None for key, wanted, shape, dtype in
+               [("draws", want_draws, (C, K, 5), "float32"), ("log_post", want_log_post, (C, K), "float32"), ("accept", True, (C,), "float32"),
+                ("divergent", True, (C,), "int32"), ("flagged", True, (C,), "int32")] + [(key, True, shape, dtype) for key, shape, dtype in own]}
+        if C > 0 or always:
             st = torch.cuda.current_stream(dev)
-            _lib.check(L.nddm_wiener_hmc(int(model), _ptr(d_dev), D, N, C, S, _ptr(s_dev), _ptr(m_dev), n_iter, n_adapt, n_leapfrog, thin,
-                                         free_mask, _u64(seed), chain_offset, iter_offset, 0, _ptr(res["draws"]), _ptr(res["log_post"]),
-                                         _ptr(res["accept"]), _ptr(res["divergent"]), _ptr(res["flagged"]), st.cuda_stream))
-            for t in (d_dev, s_dev, m_dev):
+            call(L, _ptr(d_dev), {k: _ptr(v) for k, v in ins.items()}, {k: _ptr(v) for k, v in res.items()}, st.cuda_stream)
+            for t in (d_dev, *ins.values(), *(res[key] for key, _, _ in own)):
                 if t is not None:
                     t.record_stream(st)
-    res = {k: v for k, v in res.items() if v is not None}
-    res["state"] = s_dev
+    return {k: v for k, v in res.items() if v is not None}, ins
+
+
+def wiener_hmc(model, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1, n_adapt=0, n_leapfrog=16, thin=1, free_mask=31, seed=0,
+               chain_offset=0, iter_offset=0, want_draws=True, want_log_post=True, device=None):
+    """Batched Hamiltonian Monte Carlo over the basic_ddm_dc Wiener posterior, one wave per chain, all n_iter iterations in ONE launch
+    (include/nddm.h: nddm_wiener_hmc; the chain: csrc/nddm_wiener_hmc.h).
+
+    model: BASIC_DDM_DC only.  data: [D, n_trials, 2] = (rt, choice), n_trials <= 2048.  state: float64 [C, 12], C = D *
+    chains_per_dataset, chain c on data set c // chains_per_dataset (mcmc.make_state builds one; a device tensor is updated in place).
+    inv_mass: float64 [C, 5] or None (ones).  One launch is bounded: n_iter <= wiener_hmc_max_iter(n_trials, n_leapfrog); mcmc.hmc_fit
+    cuts a long run into such launches.  Returns a dict of device tensors: 'draws' float32 [C, K, 5] in the model's columns, 'log_post'
+    float32 [C, K], 'accept' float32 [C], 'divergent' int32 [C], 'flagged' int32 [C] and 'state' float64 [C, 12]; K = (iter_offset +
+    n_iter) // thin - iter_offset // thin.  Host inputs are shape- and range-checked (ValueError); a data set that cannot be sampled (a
+    timeout, a non-finite value, an rt <= 0) that arrives on the device flags its chains instead."""
+    (n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset), d_rows, d_np, D, N = _hmc_host_checks(
+        model, data, "D", n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset, wiener_hmc_max_iter,
+        "one launch runs at most {m} iterations at n_trials {N} and n_leapfrog {L} (n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19): cut the "
+        "run (mcmc.hmc_fit does)", chains_per_dataset=chains_per_dataset)
+    S, K = int(chains_per_dataset), (iter_offset + n_iter) // thin - iter_offset // thin
+    C = D * S
+    f64 = _hmc_chain_checks(C, chain_offset, state, inv_mass, f" (D {D} x chains_per_dataset {S})")
+    res, ins = _hmc_device_call(
+        data, d_rows, d_np, f64, C, K, want_draws, want_log_post, [], device,
+        lambda L, d, i, o, st: _lib.check(L.nddm_wiener_hmc(int(model), d, D, N, C, S, i["state"], i["inv_mass"], n_iter, n_adapt, n_leapfrog, thin,
+                                                            free_mask, _u64(seed), chain_offset, iter_offset, 0, o["draws"], o["log_post"],
+                                                            o["accept"], o["divergent"], o["flagged"], st)))
+    res["state"] = ins["state"]
     return res
 
 
@@ -562,90 +593,36 @@ def wiener_hmc_joint(model, data, extdata, state, sigma, inv_mass=None, n_iter=1
     log posterior given sigma, the ext term included -- plus 'sigma_draws' float32 [S, K], 'sigma_accept' float32 [S] (the share of the
     call's sigma proposals accepted; NaN with sigma_fixed) and 'sigma' float64 [S].  Host inputs are shape- and range-checked (ValueError);
     on the device a data set that cannot be sampled flags every chain, a bad state or sigma its joint chain."""
-    if model != BASIC_DDM_DC:
-        raise ValueError(f"model {model} has no sampler here (BASIC_DDM_DC only)")
-    n_iter, n_adapt, n_leapfrog, thin, free_mask = (int(x) for x in (n_iter, n_adapt, n_leapfrog, thin, free_mask))
-    if n_iter <= 0 or n_leapfrog <= 0 or thin <= 0 or n_adapt < 0:
-        raise ValueError("n_iter, n_leapfrog and thin must be > 0 and n_adapt >= 0")
-    if not 0 <= free_mask < 32:
-        raise ValueError("free_mask has five bits")
-    chain_offset, iter_offset = int(chain_offset), int(iter_offset)
-    if chain_offset < 0 or iter_offset < 0 or iter_offset + n_iter > 1 << 32:
-        raise ValueError("chain_offset and iter_offset must be >= 0 and the iteration index < 2^32")
-    d_rows = (3, 2, "data must have shape [P, n_trials, 2]")
-    d_np = _host_rows(data, *d_rows)
-    if d_np is not None:
-        if not np.all(np.isfinite(d_np)):
-            raise ValueError("data must be finite")
-        if not np.all(np.isin(d_np[..., 1], (-1.0, 1.0))):
-            raise ValueError("the sampler takes (rt, choice) with choice in {1, -1}: a timeout (choice 0) has no gradient here")
-        if np.any(d_np[..., 0] <= 0):
-            raise ValueError("response times must be > 0")
-    P, N = (int(d_np.shape[0]), int(d_np.shape[1])) if d_np is not None else \
-        ((1, int(data.shape[0])) if data.ndim == 2 else (int(data.shape[0]), int(data.shape[1])))
-    if N > WHMC_MAX_TRIALS:
-        raise ValueError(f"n_trials must be <= {WHMC_MAX_TRIALS}")
-    if n_iter > wiener_hmc_joint_max_iter(N, n_leapfrog):
-        raise ValueError(f"one call runs at most {wiener_hmc_joint_max_iter(N, n_leapfrog)} joint iterations at n_trials {N} and n_leapfrog "
-                         f"{n_leapfrog} (n_iter <= 4096 and n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19): cut the run (mcmc.hmc_fit_joint does)")
+    (n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset), d_rows, d_np, P, N = _hmc_host_checks(
+        model, data, "P", n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset, wiener_hmc_joint_max_iter,
+        "one call runs at most {m} joint iterations at n_trials {N} and n_leapfrog {L} (n_iter <= 4096 and n_iter * n_leapfrog * ceil(n_trials / "
+        "64) <= 2^19): cut the run (mcmc.hmc_fit_joint does)")
     if not sigma_fixed and P < 2:
         raise ValueError("sampling sigma needs at least 2 participants")
-
-    def arr(x, shape, label):
-        if getattr(x, "is_cuda", False):
-            if tuple(x.shape) != shape or str(x.dtype) != "torch.float64" or not x.is_contiguous():
-                raise ValueError(f"{label} must be a contiguous float64 {list(shape)}")
-            return None
-        a = np.ascontiguousarray(x, dtype=np.float64)
-        if a.shape != shape:
-            raise ValueError(f"{label} must have shape {list(shape)}, got {a.shape}")
-        return a
     g_shape = tuple(sigma.shape) if hasattr(sigma, "shape") else np.shape(sigma)
     if len(g_shape) != 1 or g_shape[0] < 1:
         raise ValueError(f"sigma must have shape [S] with S >= 1 joint chains, got {g_shape}")
-    S = int(g_shape[0])
+    S, K = int(g_shape[0]), (iter_offset + n_iter) // thin - iter_offset // thin
     C = P * S
-    if chain_offset + C > 1 << 32:
-        raise ValueError("the chain index must stay < 2^32")
-    g_np = arr(sigma, (S,), "sigma")
-    if g_np is not None and not (np.all(np.isfinite(g_np)) and np.all(g_np > 0) and (sigma_fixed or np.all(g_np < 10))):
-        raise ValueError("sigma must be finite and > 0, and < 10 when it is sampled")
-    e_np = arr(extdata, (P,), "extdata")
-    if e_np is not None and not np.all(np.isfinite(e_np)):
-        raise ValueError("extdata must be finite")
-    s_np = arr(state, (C, WHMC_STATE), "state")
-    if s_np is not None and not np.all(np.isfinite(s_np[:, :10])):
-        raise ValueError("state must be finite")
-    m_np = None if inv_mass is None else arr(inv_mass, (C, 5), "inv_mass")
-    if m_np is not None and not (np.all(np.isfinite(m_np)) and np.all(m_np > 0)):
-        raise ValueError("inv_mass must be finite and > 0")
-    torch = require_device()
-    L = _lib.lib()
-    dev = _device(device)
-    K = (iter_offset + n_iter) // thin - iter_offset // thin
-    up = lambda x, a: x if a is None else torch.as_tensor(a, dtype=torch.float64).to(dev)
-    with torch.cuda.device(dev):
-        d_dev = _device_rows(data, d_np, dev, *d_rows)
-        e_dev, s_dev, g_dev = up(extdata, e_np), up(state, s_np), up(sigma, g_np)
-        m_dev = None if inv_mass is None else up(inv_mass, m_np)
-        ws = torch.empty((C + S, 4), dtype=torch.float64, device=dev)
-        res = {"draws": torch.empty((C, K, 5), dtype=torch.float32, device=dev) if want_draws else None,
-               "log_post": torch.empty((C, K), dtype=torch.float32, device=dev) if want_log_post else None,
-               "accept": torch.empty((C,), dtype=torch.float32, device=dev), "divergent": torch.empty((C,), dtype=torch.int32, device=dev),
-               "flagged": torch.empty((C,), dtype=torch.int32, device=dev), "sigma_draws": torch.empty((S, K), dtype=torch.float32, device=dev),
-               "sigma_accept": torch.empty((S,), dtype=torch.float32, device=dev)}
-        st = torch.cuda.current_stream(dev)
-        _lib.check(L.nddm_wiener_hmc_joint(int(model), _ptr(d_dev), P, N, C, S, _ptr(e_dev), _ptr(s_dev), _ptr(m_dev), _ptr(g_dev), _ptr(ws),
-                                           n_iter, n_adapt, n_leapfrog, thin, free_mask, _u64(seed), chain_offset, iter_offset,
-                                           _lib.HMC_SIGMA_FIXED if sigma_fixed else 0, _ptr(res["draws"]), _ptr(res["log_post"]),
-                                           _ptr(res["accept"]), _ptr(res["divergent"]), _ptr(res["flagged"]), _ptr(res["sigma_draws"]),
-                                           _ptr(res["sigma_accept"]), st.cuda_stream))
-        for t in (d_dev, e_dev, s_dev, g_dev, m_dev, ws):
-            if t is not None:
-                t.record_stream(st)
-    res = {k: v for k, v in res.items() if v is not None}
-    res["state"] = s_dev
-    res["sigma"] = g_dev
+
+    def own():
+        g_np = _hmc_f64(sigma, (S,), "sigma")
+        if g_np is not None and not (np.all(np.isfinite(g_np)) and np.all(g_np > 0) and (sigma_fixed or np.all(g_np < 10))):
+            raise ValueError("sigma must be finite and > 0, and < 10 when it is sampled")
+        e_np = _hmc_f64(extdata, (P,), "extdata")
+        if e_np is not None and not np.all(np.isfinite(e_np)):
+            raise ValueError("extdata must be finite")
+        return {"extdata": (extdata, e_np), "sigma": (sigma, g_np)}
+    f64 = _hmc_chain_checks(C, chain_offset, state, inv_mass, own=own)
+    res, ins = _hmc_device_call(
+        data, d_rows, d_np, f64, C, K, want_draws, want_log_post,
+        [("sigma_draws", (S, K), "float32"), ("sigma_accept", (S,), "float32"), ("workspace", (C + S, 4), "float64")], device,
+        lambda L, d, i, o, st: _lib.check(L.nddm_wiener_hmc_joint(
+            int(model), d, P, N, C, S, i["extdata"], i["state"], i["inv_mass"], i["sigma"], o["workspace"], n_iter, n_adapt, n_leapfrog, thin,
+            free_mask, _u64(seed), chain_offset, iter_offset, _lib.HMC_SIGMA_FIXED if sigma_fixed else 0, o["draws"], o["log_post"], o["accept"],
+            o["divergent"], o["flagged"], o["sigma_draws"], o["sigma_accept"], st)), always=True)
+    del res["workspace"]
+    res["state"], res["sigma"] = ins["state"], ins["sigma"]
     return res
 
 

@@ -119,16 +119,93 @@ def hmc_init(data, chains, seed):
     return th
 
 
-def _run(call, data, state, inv_mass, n_iter, n_adapt, iter_offset, max_iter, thin, **kw):
-    """n_iter iterations from iter_offset as bounded launches -> (the launches' results, the state)."""
+def _host(t):
+    return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+
+def _trials(data, sets):
+    """The data of a fit as float32 [sets, n_trials, 2] on the host (`sets`: the first axis' letter in the refusal)."""
+    d = np.asarray(_host(data), dtype=np.float32)
+    if d.ndim == 2:
+        d = d[None]
+    if d.ndim != 3 or d.shape[-1] != 2:
+        raise ValueError(f"data must have shape [{sets}, n_trials, 2], got {d.shape}")
+    return d
+
+
+def _run(call, lead, carried, inv_mass, n_iter, n_adapt, iter_offset, max_iter, thin, **kw):
+    """n_iter iterations from iter_offset as bounded launches -> (the launches' results, what the sampler carries from launch to launch).
+    lead: the sampler's inputs before the carried ones; carried: {result key: value} in the call's order -- the state, and sigma when the
+    sampler has one -- each taken from the launch's result for the next."""
     out, done = [], 0
     while done < n_iter:
         n = min(max_iter, n_iter - done)
-        r = call(engine.BASIC_DDM_DC, data, state, inv_mass=inv_mass, n_iter=n, n_adapt=n_adapt, thin=thin, iter_offset=iter_offset + done, **kw)
-        state = r["state"]
+        r = call(engine.BASIC_DDM_DC, *lead, *carried.values(), inv_mass=inv_mass, n_iter=n, n_adapt=n_adapt, thin=thin,
+                 iter_offset=iter_offset + done, **kw)
+        carried = {k: r[k] for k in carried}
         out.append(r)
         done += n
-    return out, state
+    return out, carried
+
+
+def _fit(call, d, lead, own_fixed, init, max_iter_of, unit, chains, warmup, samples, thin, n_leapfrog, free, fixed, seed, eps0, **kw):
+    """What hmc_fit and hmc_fit_joint share: the checks, the mask and `fixed`, the initial state, the warm-up's two stages with the mass
+    estimate between them, the sampling phase cut into bounded launches, and the JAGS layout.  d: _trials' data; lead: the sampler's inputs
+    before the state; own_fixed(fixed) takes the sampler's own entries out of `fixed` -> (what else `fixed` may name, in the refusal's
+    words, the sampler's own keywords); init(d, chains, seed) -> (theta [D, chains, 5], what the sampler carries besides the state);
+    max_iter_of: the sampler's launch bound, `unit` its name for a launch.
+    -> (the layout, the sampling launches' results, mean(key): their n_iter-weighted mean of a per-launch output)."""
+    chains, warmup, samples, thin = int(chains), int(warmup), int(samples), int(thin)
+    if chains < 1 or warmup < 4 or samples < 1 or thin < 1 or samples % thin:
+        raise ValueError("chains >= 1, warmup >= 4, samples >= 1 and thin dividing samples are required")
+    mask = free_mask(free)
+    fixed = {} if fixed is None else dict(fixed)
+    also, own_kw = own_fixed(fixed)
+    for k in fixed:
+        if k not in PARAM_NAMES:
+            raise ValueError(f"unknown fixed column {k!r}: the columns are {PARAM_NAMES}{also}")
+        mask &= ~(1 << PARAM_NAMES.index(k))                             # (a fixed column is not sampled, whatever `free` says)
+    D, N = d.shape[0], d.shape[1]
+    theta, carried = init(d, chains, seed)
+    for k, v in fixed.items():
+        theta[..., PARAM_NAMES.index(k)] = float(v)
+    per_chain = np.repeat(d, chains, 0)
+    carried = {"state": make_state(theta.reshape(-1, 5), per_chain, eps0=eps0, free=mask), **carried}
+    max_iter = max_iter_of(N, n_leapfrog)
+    if max_iter < 1:
+        raise ValueError(f"n_leapfrog is too large for one bounded {unit}")
+    kw = dict(kw, n_leapfrog=n_leapfrog, free_mask=mask, seed=seed, **own_kw)
+    quiet = dict(kw, want_draws=False, want_log_post=False)
+    # stage 1: unit mass; its second half kept (every iteration) for the mass
+    w1 = warmup // 2
+    h1 = w1 // 2
+    _, carried = _run(call, lead, carried, None, h1, w1, 0, max_iter, 1, **quiet)
+    res, carried = _run(call, lead, carried, None, w1 - h1, w1, h1, max_iter, 1, want_log_post=False, **kw)
+    th = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)                   # [C, w1 - h1, 5], float32 theta
+    lo, wd = _support(per_chain)
+    x = np.clip((th - lo[:, None, :]) / wd[:, None, :], 1e-7, 1.0 - 1e-7)
+    qs = np.where(np.array([False] + [bool(mask >> j & 1) for j in range(1, 5)]), np.log(x) - np.log1p(-x), th)
+    var = np.var(qs, axis=1) if qs.shape[1] > 1 else np.ones((D * chains, 5))
+    inv_mass = np.where(np.isfinite(var), np.maximum(var, 1e-3), 1.0)
+    # stage 2: that mass, the step size adapted again
+    carried["state"] = restart_adaptation(_host(carried["state"]))
+    w2 = warmup - w1
+    _, carried = _run(call, lead, carried, inv_mass, w2, w2, w1, max_iter, 1, **quiet)
+    res, carried = _run(call, lead, carried, inv_mass, samples, w2, warmup, max_iter, thin, **kw)
+    # (iteration g is kept when (g + 1) % thin == 0: with warmup a multiple of thin every launch's draws line up)
+    draws = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)
+    lp = np.concatenate([_host(r["log_post"]) for r in res], 1).astype(np.float64)
+    K = draws.shape[1]
+    n_samp = np.array([min(max_iter, samples - i * max_iter) for i in range(len(res))], dtype=np.float64)
+
+    def mean(key):
+        return sum(_host(r[key]).astype(np.float64) * n for r, n in zip(res, n_samp)) / n_samp.sum()
+    out = {JAGS_NAMES[name]: draws[:, :, j].reshape(D, chains, K).transpose(0, 2, 1) for j, name in enumerate(PARAM_NAMES)}
+    out["log_post"] = lp.reshape(D, chains, K).transpose(0, 2, 1)
+    out["accept_rate"] = mean("accept").reshape(D, chains)
+    out["n_divergent"] = sum(_host(r["divergent"]).astype(np.int64) for r in res).reshape(D, chains)
+    out["flagged"] = _host(res[0]["flagged"]).astype(np.int64).reshape(D, chains)
+    return out, res, mean
 
 
 def hmc_fit(data, chains=6, warmup=2000, samples=10000, thin=10, n_leapfrog=16, free=PARAM_NAMES, fixed=None, seed=0, eps0=0.05,
@@ -146,58 +223,9 @@ def hmc_fit(data, chains=6, warmup=2000, samples=10000, thin=10, n_leapfrog=16, 
     'log_post' of the same shape, 'accept_rate' [D, chains] (the sampling iterations' mean acceptance probability), 'n_divergent'
     [D, chains] and 'flagged' [D, chains]."""
     call = _call or (lambda *a, **k: engine.wiener_hmc(*a, device=device, **k))
-    d = np.asarray(data.detach().cpu().numpy() if hasattr(data, "detach") else data, dtype=np.float32)
-    if d.ndim == 2:
-        d = d[None]
-    if d.ndim != 3 or d.shape[-1] != 2:
-        raise ValueError(f"data must have shape [D, n_trials, 2], got {d.shape}")
-    chains, warmup, samples, thin = int(chains), int(warmup), int(samples), int(thin)
-    if chains < 1 or warmup < 4 or samples < 1 or thin < 1 or samples % thin:
-        raise ValueError("chains >= 1, warmup >= 4, samples >= 1 and thin dividing samples are required")
-    mask = free_mask(free)
-    fixed = {} if fixed is None else dict(fixed)
-    for k in fixed:
-        if k not in PARAM_NAMES:
-            raise ValueError(f"unknown fixed column {k!r}: the columns are {PARAM_NAMES}")
-        mask &= ~(1 << PARAM_NAMES.index(k))                             # (a fixed column is not sampled, whatever `free` says)
-    D, N = d.shape[0], d.shape[1]
-    theta = hmc_init(d, chains, seed)
-    for k, v in fixed.items():
-        theta[..., PARAM_NAMES.index(k)] = float(v)
-    per_chain = np.repeat(d, chains, 0)
-    state = make_state(theta.reshape(-1, 5), per_chain, eps0=eps0, free=mask)
-    max_iter = engine.wiener_hmc_max_iter(N, n_leapfrog)
-    if max_iter < 1:
-        raise ValueError("n_leapfrog is too large for one bounded launch")
-    kw = dict(chains_per_dataset=chains, n_leapfrog=n_leapfrog, free_mask=mask, seed=seed)
-    # stage 1: unit mass; its second half kept (every iteration) for the mass
-    w1 = warmup // 2
-    h1 = w1 // 2
-    _, state = _run(call, d, state, None, h1, w1, 0, max_iter, 1, want_draws=False, want_log_post=False, **kw)
-    res, state = _run(call, d, state, None, w1 - h1, w1, h1, max_iter, 1, want_log_post=False, **kw)
-    th = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)                   # [C, w1 - h1, 5], float32 theta
-    lo, wd = _support(per_chain)
-    x = np.clip((th - lo[:, None, :]) / wd[:, None, :], 1e-7, 1.0 - 1e-7)
-    qs = np.where(np.array([False] + [bool(mask >> j & 1) for j in range(1, 5)]), np.log(x) - np.log1p(-x), th)
-    var = np.var(qs, axis=1) if qs.shape[1] > 1 else np.ones((D * chains, 5))
-    inv_mass = np.where(np.isfinite(var), np.maximum(var, 1e-3), 1.0)
-    # stage 2: that mass, the step size adapted again
-    state = restart_adaptation(_host(state))
-    w2 = warmup - w1
-    _, state = _run(call, d, state, inv_mass, w2, w2, w1, max_iter, 1, want_draws=False, want_log_post=False, **kw)
-    res, state = _run(call, d, state, inv_mass, samples, w2, warmup, max_iter, thin, **kw)
-    # (iteration g is kept when (g + 1) % thin == 0: with warmup a multiple of thin every launch's draws line up)
-    draws = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)
-    lp = np.concatenate([_host(r["log_post"]) for r in res], 1).astype(np.float64)
-    K = draws.shape[1]
-    n_samp = np.array([min(max_iter, samples - i * max_iter) for i in range(len(res))], dtype=np.float64)
-    acc = sum(_host(r["accept"]).astype(np.float64) * n for r, n in zip(res, n_samp)) / n_samp.sum()
-    out = {JAGS_NAMES[name]: draws[:, :, j].reshape(D, chains, K).transpose(0, 2, 1) for j, name in enumerate(PARAM_NAMES)}
-    out["log_post"] = lp.reshape(D, chains, K).transpose(0, 2, 1)
-    out["accept_rate"] = acc.reshape(D, chains)
-    out["n_divergent"] = sum(_host(r["divergent"]).astype(np.int64) for r in res).reshape(D, chains)
-    out["flagged"] = _host(res[0]["flagged"]).astype(np.int64).reshape(D, chains)
-    return out
+    d = _trials(data, "D")
+    return _fit(call, d, (d,), lambda fixed: ("", {}), lambda *a: (hmc_init(*a), {}), engine.wiener_hmc_max_iter, "launch", chains, warmup,
+                samples, thin, n_leapfrog, free, fixed, seed, eps0, chains_per_dataset=int(chains))[0]
 
 
 def hmc_init_joint(data, chains, seed):
@@ -207,19 +235,6 @@ def hmc_init_joint(data, chains, seed):
     theta = hmc_init(data, chains, seed)
     sigma = np.random.default_rng([int(seed), 0x516]).uniform(0.01, 5.0, int(chains))
     return theta, sigma
-
-
-def _run_joint(call, data, ext, state, sigma, inv_mass, n_iter, n_adapt, iter_offset, max_iter, thin, **kw):
-    """_run for the joint sampler -> (the calls' results, the state, sigma)."""
-    out, done = [], 0
-    while done < n_iter:
-        n = min(max_iter, n_iter - done)
-        r = call(engine.BASIC_DDM_DC, data, ext, state, sigma, inv_mass=inv_mass, n_iter=n, n_adapt=n_adapt, thin=thin, iter_offset=iter_offset + done,
-                 **kw)
-        state, sigma = r["state"], r["sigma"]
-        out.append(r)
-        done += n
-    return out, state, sigma
 
 
 def hmc_fit_joint(data, extdata, chains=6, warmup=2000, samples=10000, thin=10, n_leapfrog=16, free=PARAM_NAMES, fixed=None, seed=0,
@@ -235,70 +250,27 @@ def hmc_fit_joint(data, extdata, chains=6, warmup=2000, samples=10000, thin=10, 
     diagnostics.rhat_neff(fit) takes it as it stands -- and 'sigma_accept' [chains], the share of the sampling iterations' sigma proposals
     accepted (NaN when sigma is fixed)."""
     call = _call or (lambda *a, **k: engine.wiener_hmc_joint(*a, device=device, **k))
-    d = np.asarray(data.detach().cpu().numpy() if hasattr(data, "detach") else data, dtype=np.float32)
-    if d.ndim == 2:
-        d = d[None]
-    if d.ndim != 3 or d.shape[-1] != 2:
-        raise ValueError(f"data must have shape [P, n_trials, 2], got {d.shape}")
-    P, N = d.shape[0], d.shape[1]
-    ext = np.asarray(extdata.detach().cpu().numpy() if hasattr(extdata, "detach") else extdata, dtype=np.float64).reshape(-1)
+    d = _trials(data, "P")
+    P = d.shape[0]
+    ext = np.asarray(_host(extdata), dtype=np.float64).reshape(-1)
     if ext.shape != (P,) or not np.all(np.isfinite(ext)):
         raise ValueError(f"extdata must hold one finite value per participant ({P}), got shape {ext.shape}")
-    chains, warmup, samples, thin = int(chains), int(warmup), int(samples), int(thin)
-    if chains < 1 or warmup < 4 or samples < 1 or thin < 1 or samples % thin:
-        raise ValueError("chains >= 1, warmup >= 4, samples >= 1 and thin dividing samples are required")
-    mask = free_mask(free)
-    fixed = {} if fixed is None else dict(fixed)
-    sigma_fixed = "sigma" in fixed
-    sigma_value = float(fixed.pop("sigma")) if sigma_fixed else None
-    if sigma_fixed and not (np.isfinite(sigma_value) and sigma_value > 0):
-        raise ValueError("a fixed sigma must be finite and > 0")
-    if not sigma_fixed and P < 2:
-        raise ValueError("sampling sigma needs at least 2 participants: fix it (fixed={'sigma': value}) or bring more")
-    for k in fixed:
-        if k not in PARAM_NAMES:
-            raise ValueError(f"unknown fixed column {k!r}: the columns are {PARAM_NAMES} and 'sigma'")
-        mask &= ~(1 << PARAM_NAMES.index(k))
-    theta, sigma = hmc_init_joint(d, chains, seed)
-    if sigma_fixed:
-        sigma = np.full(chains, sigma_value)
-    for k, v in fixed.items():
-        theta[..., PARAM_NAMES.index(k)] = float(v)
-    per_chain = np.repeat(d, chains, 0)
-    state = make_state(theta.reshape(-1, 5), per_chain, eps0=eps0, free=mask)
-    max_iter = engine.wiener_hmc_joint_max_iter(N, n_leapfrog)
-    if max_iter < 1:
-        raise ValueError("n_leapfrog is too large for one bounded call")
-    kw = dict(n_leapfrog=n_leapfrog, free_mask=mask, seed=seed, sigma_fixed=sigma_fixed)
-    w1 = warmup // 2
-    h1 = w1 // 2
-    _, state, sigma = _run_joint(call, d, ext, state, sigma, None, h1, w1, 0, max_iter, 1, want_draws=False, want_log_post=False, **kw)
-    res, state, sigma = _run_joint(call, d, ext, state, sigma, None, w1 - h1, w1, h1, max_iter, 1, want_log_post=False, **kw)
-    th = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)
-    lo, wd = _support(per_chain)
-    x = np.clip((th - lo[:, None, :]) / wd[:, None, :], 1e-7, 1.0 - 1e-7)
-    qs = np.where(np.array([False] + [bool(mask >> j & 1) for j in range(1, 5)]), np.log(x) - np.log1p(-x), th)
-    var = np.var(qs, axis=1) if qs.shape[1] > 1 else np.ones((P * chains, 5))
-    inv_mass = np.where(np.isfinite(var), np.maximum(var, 1e-3), 1.0)
-    state = restart_adaptation(_host(state))
-    w2 = warmup - w1
-    _, state, sigma = _run_joint(call, d, ext, state, sigma, inv_mass, w2, w2, w1, max_iter, 1, want_draws=False, want_log_post=False, **kw)
-    res, state, sigma = _run_joint(call, d, ext, state, sigma, inv_mass, samples, w2, warmup, max_iter, thin, **kw)
-    draws = np.concatenate([_host(r["draws"]) for r in res], 1).astype(np.float64)
-    lp = np.concatenate([_host(r["log_post"]) for r in res], 1).astype(np.float64)
-    sg = np.concatenate([_host(r["sigma_draws"]) for r in res], 1).astype(np.float64)                # [chains, K]
-    K = draws.shape[1]
-    n_samp = np.array([min(max_iter, samples - i * max_iter) for i in range(len(res))], dtype=np.float64)
-    acc = sum(_host(r["accept"]).astype(np.float64) * n for r, n in zip(res, n_samp)) / n_samp.sum()
-    out = {JAGS_NAMES[name]: draws[:, :, j].reshape(P, chains, K).transpose(0, 2, 1) for j, name in enumerate(PARAM_NAMES)}
-    out["log_post"] = lp.reshape(P, chains, K).transpose(0, 2, 1)
-    out["accept_rate"] = acc.reshape(P, chains)
-    out["n_divergent"] = sum(_host(r["divergent"]).astype(np.int64) for r in res).reshape(P, chains)
-    out["flagged"] = _host(res[0]["flagged"]).astype(np.int64).reshape(P, chains)
-    out["sigma"] = sg.T[None]
-    out["sigma_accept"] = sum(_host(r["sigma_accept"]).astype(np.float64) * n for r, n in zip(res, n_samp)) / n_samp.sum()
+    held = []                                                            # the fixed sigma, if there is one
+
+    def own_fixed(fixed):
+        if "sigma" in fixed:
+            held.append(float(fixed.pop("sigma")))
+            if not (np.isfinite(held[0]) and held[0] > 0):
+                raise ValueError("a fixed sigma must be finite and > 0")
+        elif P < 2:
+            raise ValueError("sampling sigma needs at least 2 participants: fix it (fixed={'sigma': value}) or bring more")
+        return " and 'sigma'", dict(sigma_fixed=bool(held))
+
+    def init(d, chains, seed):
+        theta, sigma = hmc_init_joint(d, chains, seed)
+        return theta, {"sigma": np.full(chains, held[0]) if held else sigma}
+    out, res, mean = _fit(call, d, (d, ext), own_fixed, init, engine.wiener_hmc_joint_max_iter, "call", chains, warmup, samples, thin, n_leapfrog,
+                          free, fixed, seed, eps0)
+    out["sigma"] = np.concatenate([_host(r["sigma_draws"]) for r in res], 1).astype(np.float64).T[None]      # [chains, K] -> [1, K, chains]
+    out["sigma_accept"] = mean("sigma_accept")
     return out
-
-
-def _host(t):
-    return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)

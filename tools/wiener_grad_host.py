@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The per-trial code and the chain rule of csrc/nddm_wiener_grad.h run on the HOST, without a GPU: the header's own wiener_grad_row,
 wiener_grad_trial and wiener_grad_finish (over nddm_wiener.h's wiener_row and wiener_trial) compiled by the host compiler as a stand-alone
-program against the stand-in for <hip/hip_runtime.h> of tools/wiener_quantile_host.py (the hardware's rcp / exp / log become the C
+program against the stand-in for <hip/hip_runtime.h> of tools/host_build.py (the hardware's rcp / exp / log become the C
 library's), optionally under AddressSanitizer and UndefinedBehaviorSanitizer.  A row's trials are summed in one sequence here (one lane), not
 in the kernel's 64 interleaved ones: the float64 sums differ in their last bits, nothing more.
 
@@ -11,8 +11,6 @@ Usage: python tools/wiener_grad_host.py [--sanitize] [--json OUT]      prints on
 |gradient - yardstick| / scale_j over tests/wiener_cdf_ref.prior_rows (20 000 rows each, one trial per row; tests/wiener_grad_ref.py is the
 float64 yardstick and defines scale_j), and the bar B = 4 x the largest of them, rounded up to one significant digit.
 """
-import argparse
-import json
 import math
 import os
 import subprocess
@@ -24,7 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import wiener_host as H  # noqa: E402  (trial_data)
-import wiener_quantile_host as Q  # noqa: E402  (the stand-in header and the compiler call)
+import host_build as B  # noqa: E402  (the stand-in header, the compiler call, the command line)
 
 MAIN = r"""// usage: wiener_grad_host MODEL(0|3) in.bin out.bin ; in: int32 n, int32 N, then n * (P + 2N) floats (params, N trials); out: n * (1 + P) doubles
 #include <cstdio>
@@ -62,7 +60,7 @@ int main(int argc, char **argv) {
 
 
 def build(td, sanitize=False):
-    return Q.build(td, sanitize, main=MAIN, name="wiener_grad_host")
+    return B.build(td, MAIN, "wiener_grad_host", sanitize)
 
 
 def evaluate(exe, td, model, params, data):
@@ -109,17 +107,5 @@ def survey(sanitize=False, n=20_000):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sanitize", action="store_true")
-    ap.add_argument("--json")
-    a = ap.parse_args()
-    line = json.dumps(survey(a.sanitize))
-    print(line)
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    B.cli(survey)

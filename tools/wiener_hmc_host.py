@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The chain of csrc/nddm_wiener_hmc.h run on the HOST, without a GPU: the header's own whmc_stage, whmc_log_post, whmc_randoms and
 whmc_chain (over nddm_wiener_grad.h's likelihood and nddm_rng.h's Philox and exact Box-Muller) compiled by the host compiler as a
-stand-alone program against the stand-in for <hip/hip_runtime.h> of tools/wiener_quantile_host.py, optionally under AddressSanitizer and
+stand-alone program against the stand-in for <hip/hip_runtime.h> of tools/host_build.py, optionally under AddressSanitizer and
 UndefinedBehaviorSanitizer.  The 64 lanes are a loop and the butterfly is summed in the kernel's order, so a host chain differs from the
 device's only where the hardware's rcp / exp / log differ from the C library's in their last bits.  Two builds: float32 (the kernel's
 arithmetic) and `f64=True`, in which the likelihood's headers are compiled with every float a double -- the same expressions and the
@@ -13,11 +13,8 @@ Usage: python tools/wiener_hmc_host.py [--sanitize] [--json OUT]      prints one
 eps = 1e-3 (the bar of the energy tests = 4 x the largest), and float32 against float64 over 3 iterations of 4 leapfrog steps (the
 tolerance of the device-against-host test = 4 x the largest difference, and the share of chains whose accept decision is within it).
 """
-import argparse
-import json
 import math
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -25,7 +22,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import wiener_quantile_host as Q  # noqa: E402  (the stand-in header and the compiler call)
+import host_build as B  # noqa: E402  (the stand-in header, the compiler call, the command line)
 
 STATE = 12
 DC_MIN = 0.05
@@ -126,7 +123,7 @@ def build(td, sanitize=False, f64=False):
     """Compile the stand-alone program into a directory of its own under td -> its path."""
     sub = os.path.join(td, "f64" if f64 else "f32")
     os.makedirs(sub)
-    return Q.build(sub, sanitize, main=MAIN % (RNG_SHIM + (F64_ON if f64 else "")), name="wiener_hmc_host")
+    return B.build(sub, MAIN % (RNG_SHIM + (F64_ON if f64 else "")), "wiener_hmc_host", sanitize)
 
 
 def kept(iter_offset, n_iter, thin):
@@ -143,24 +140,11 @@ def run(exe, td, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1, n_a
     C = state.shape[0]
     assert state.shape == (C, STATE) and C == D * chains_per_dataset
     K = kept(iter_offset, n_iter, thin)
-    fin, fout = os.path.join(os.path.dirname(exe), "in.bin"), os.path.join(os.path.dirname(exe), "out.bin")
-    with open(fin, "wb") as f:
-        f.write(np.array([D, N, C, chains_per_dataset, n_iter, n_adapt, n_leapfrog, thin, free_mask, seed, chain_offset, iter_offset,
-                          inv_mass is not None], np.int64).tobytes())
-        f.write(data.tobytes())
-        f.write(state.tobytes())
-        if inv_mass is not None:
-            f.write(np.ascontiguousarray(inv_mass, np.float64).reshape(C, 5).tobytes())
-    subprocess.check_call([exe, fin, fout])
-    raw = open(fout, "rb").read()
-    o, out = 0, {}
-    for key, dt, shape in (("draws", np.float32, (C, K, 5)), ("log_post", np.float32, (C, K)), ("accept", np.float32, (C,)),
-                           ("divergent", np.int32, (C,)), ("flagged", np.int32, (C,)), ("state", np.float64, (C, STATE))):
-        n = int(np.prod(shape)) * np.dtype(dt).itemsize
-        out[key] = np.frombuffer(raw[o:o + n], dt).reshape(shape).copy()
-        o += n
-    assert o == len(raw)
-    return out
+    return B.exchange(exe, [D, N, C, chains_per_dataset, n_iter, n_adapt, n_leapfrog, thin, free_mask, seed, chain_offset, iter_offset,
+                            inv_mass is not None],
+                      [data, state] + ([] if inv_mass is None else [np.ascontiguousarray(inv_mass, np.float64).reshape(C, 5)]),
+                      (("draws", np.float32, (C, K, 5)), ("log_post", np.float32, (C, K)), ("accept", np.float32, (C,)),
+                       ("divergent", np.int32, (C,)), ("flagged", np.int32, (C,)), ("state", np.float64, (C, STATE))))
 
 
 def init_state(theta, data, chains_per_dataset=1, eps0=0.05, free=31):
@@ -263,17 +247,5 @@ def survey(sanitize=False):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sanitize", action="store_true")
-    ap.add_argument("--json")
-    a = ap.parse_args()
-    line = json.dumps(survey(a.sanitize))
-    print(line)
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    B.cli(survey)

@@ -13,10 +13,7 @@ with the ext term on (sigma = 0.2) at eps = 1e-3 (the bar of the energy tests = 
 over 3 iterations of 4 leapfrog steps for every case of the device-against-host test (its tolerance = 4 x that case's difference).
 --sanitize runs one small case through a build under AddressSanitizer and UndefinedBehaviorSanitizer first (a stand-alone program).
 """
-import argparse
-import json
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -25,7 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import wiener_hmc_host as H  # noqa: E402  (the shims, the cases, the comparison)
-import wiener_quantile_host as Q  # noqa: E402
+import host_build as B  # noqa: E402  (the stand-in header, the compiler call, the command line)
 
 STATE = H.STATE
 SIGMA_FIXED = 1
@@ -128,7 +125,7 @@ def build(td, sanitize=False, f64=False):
     """Compile the stand-alone program into a directory of its own under td -> its path."""
     sub = os.path.join(td, ("j64" if f64 else "j32") + ("s" if sanitize else ""))
     os.makedirs(sub)
-    return Q.build(sub, sanitize, main=MAIN % (H.RNG_SHIM + (H.F64_ON if f64 else "")), name="wiener_hmc_joint_host")
+    return B.build(sub, MAIN % (H.RNG_SHIM + (H.F64_ON if f64 else "")), "wiener_hmc_joint_host", sanitize)
 
 
 kept = H.kept
@@ -147,27 +144,12 @@ def run(exe, td, data, extdata, state, sigma, inv_mass=None, n_iter=1, n_adapt=0
     C = P * S
     assert state.shape == (C, STATE) and extdata.shape == (P,)
     K = kept(iter_offset, n_iter, thin)
-    fin, fout = os.path.join(os.path.dirname(exe), "in.bin"), os.path.join(os.path.dirname(exe), "out.bin")
-    with open(fin, "wb") as f:
-        f.write(np.array([P, N, S, n_iter, n_adapt, n_leapfrog, thin, free_mask, seed, chain_offset, iter_offset, inv_mass is not None,
-                          SIGMA_FIXED if sigma_fixed else 0], np.int64).tobytes())
-        f.write(data.tobytes())
-        f.write(extdata.tobytes())
-        f.write(state.tobytes())
-        f.write(sigma.tobytes())
-        if inv_mass is not None:
-            f.write(np.ascontiguousarray(inv_mass, np.float64).reshape(C, 5).tobytes())
-    subprocess.check_call([exe, fin, fout])
-    raw = open(fout, "rb").read()
-    o, out = 0, {}
-    for key, dt, shape in (("draws", np.float32, (C, K, 5)), ("log_post", np.float32, (C, K)), ("accept", np.float32, (C,)),
-                           ("divergent", np.int32, (C,)), ("flagged", np.int32, (C,)), ("sigma_draws", np.float32, (S, K)),
-                           ("sigma_accept", np.float32, (S,)), ("state", np.float64, (C, STATE)), ("sigma", np.float64, (S,))):
-        n = int(np.prod(shape)) * np.dtype(dt).itemsize
-        out[key] = np.frombuffer(raw[o:o + n], dt).reshape(shape).copy()
-        o += n
-    assert o == len(raw)
-    return out
+    return B.exchange(exe, [P, N, S, n_iter, n_adapt, n_leapfrog, thin, free_mask, seed, chain_offset, iter_offset, inv_mass is not None,
+                            SIGMA_FIXED if sigma_fixed else 0],
+                      [data, extdata, state, sigma] + ([] if inv_mass is None else [np.ascontiguousarray(inv_mass, np.float64).reshape(C, 5)]),
+                      (("draws", np.float32, (C, K, 5)), ("log_post", np.float32, (C, K)), ("accept", np.float32, (C,)),
+                       ("divergent", np.int32, (C,)), ("flagged", np.int32, (C,)), ("sigma_draws", np.float32, (S, K)),
+                       ("sigma_accept", np.float32, (S,)), ("state", np.float64, (C, STATE)), ("sigma", np.float64, (S,))))
 
 
 PROFILE = os.path.join(ROOT, "profiles", "r18_wiener_hmc_joint_host.json")
@@ -246,17 +228,5 @@ def survey(sanitize=False):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sanitize", action="store_true")
-    ap.add_argument("--json")
-    a = ap.parse_args()
-    line = json.dumps(survey(a.sanitize))
-    print(line)
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    B.cli(survey)

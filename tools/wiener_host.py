@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The per-trial code of csrc/nddm_wiener.h and csrc/nddm_wiener_cdf.h run on the HOST, without a GPU: the headers' own wiener_row,
 wiener_trial (a censored choice 0 included), wiener_cdf_side and wiener_cdf_trial compiled by the host compiler as a stand-alone program
-against the stand-in for <hip/hip_runtime.h> of tools/wiener_quantile_host.py (the hardware's rcp / rsq / exp / log become the C
+against the stand-in for <hip/hip_runtime.h> of tools/host_build.py (the hardware's rcp / rsq / exp / log become the C
 library's), optionally under AddressSanitizer and UndefinedBehaviorSanitizer.  The device's numbers differ by the hardware
 transcendentals' last ulp; what float32 cannot hold on the host it cannot hold on the device either.
 
@@ -10,8 +10,6 @@ evaluate(exe, td, model, params [n, P], data [n, 2]) -> (log f or log S [n], F [
 Usage: python tools/wiener_host.py [--sanitize] [--json OUT]      prints one JSON line: the largest errors against the float64 yardsticks
 (tests/wiener_ref.py, tests/wiener_cdf_ref.py) over the rows of tests/test_wiener_host.py.
 """
-import argparse
-import json
 import os
 import subprocess
 import sys
@@ -21,7 +19,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import wiener_quantile_host as Q  # noqa: E402  (the stand-in header and the compiler call)
+import host_build as B  # noqa: E402  (the stand-in header, the compiler call, the command line)
 
 MAIN = r"""// usage: wiener_host MODEL(0|3) in.bin out.bin ; in: int32 n, then n*(P+2) floats (params, x0, x1); out: n * (log f | log S, F, P(upper))
 #include <cstdio>
@@ -57,7 +55,7 @@ int main(int argc, char **argv) {
 
 
 def build(td, sanitize=False):
-    return Q.build(td, sanitize, main=MAIN, name="wiener_host")
+    return B.build(td, MAIN, "wiener_host", sanitize)
 
 
 def evaluate(exe, td, model, params, data):
@@ -118,17 +116,5 @@ def survey(sanitize=False, n=20_000):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sanitize", action="store_true")
-    ap.add_argument("--json")
-    a = ap.parse_args()
-    line = json.dumps(survey(a.sanitize))
-    print(line)
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    B.cli(survey)

@@ -2,7 +2,7 @@
 """The per-trial code and the chain rule of csrc/nddm_wiener_marginal_grad.h run on the HOST, without a GPU: the header's own
 wiener_marginal_grad_trial and wiener_marginal_grad_finish (over nddm_wiener_marginal.h's row constants and node, nddm_wiener_grad.h's row
 constants and the header's own partials of log S) compiled by the host compiler as a stand-alone program with its own main against the
-stand-in for <hip/hip_runtime.h> of tools/wiener_quantile_host.py (the hardware's rcp / exp / log become the C library's), optionally under
+stand-in for <hip/hip_runtime.h> of tools/host_build.py (the hardware's rcp / exp / log become the C library's), optionally under
 AddressSanitizer and UndefinedBehaviorSanitizer.  Nothing is loaded into Python.  A pass's node values live in a local array here, in LDS in the
 kernel, and a row's trials are summed in one sequence (one lane), not in the kernel's 64 interleaved ones; nothing else differs.
 
@@ -14,8 +14,6 @@ tests/wiener_marginal_ref.py (prior_rows, box; one trial per row) and parameter 
 |gradient - yardstick| / scale_j (tests/wiener_marginal_grad_ref.py is the float64 yardstick; with one trial per row scale_j is
 |yardstick_j|), and the set's device bar, 4 x the largest of them rounded up to one significant digit.
 """
-import argparse
-import json
 import math
 import os
 import subprocess
@@ -26,7 +24,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import wiener_quantile_host as Q  # noqa: E402  (the stand-in header and the compiler call)
+import host_build as B  # noqa: E402  (the stand-in header, the compiler call, the command line)
 
 MAIN = r"""// usage: wiener_marginal_grad_host grad T_CENSOR in.bin out.bin ; in: int32 n, int32 N, then n * (8 + 2N) floats (params, N trials); out: n * 9 doubles
 //        wiener_marginal_grad_host surv 0 in.bin out.bin        ; in: int32 n, int32 0, then n * 4 floats (a', w, v', t); out: n * 4 floats
@@ -85,7 +83,7 @@ int main(int argc, char **argv) {
 
 
 def build(td, sanitize=False):
-    return Q.build(td, sanitize, main=MAIN, name="wiener_marginal_grad_host")
+    return B.build(td, MAIN, "wiener_marginal_grad_host", sanitize)
 
 
 def evaluate(exe, td, params, data, t_censor):
@@ -147,18 +145,5 @@ def survey(sanitize=False, n=1500):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sanitize", action="store_true")
-    ap.add_argument("--rows", type=int, default=1500)
-    ap.add_argument("--json")
-    a = ap.parse_args()
-    line = json.dumps(survey(a.sanitize, a.rows))
-    print(line)
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    B.cli(survey, rows=1500)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The per-trial code of csrc/nddm_wiener_marginal.h run on the HOST, without a GPU: the header's own wiener_marginal_base,
 wiener_marginal_row and wiener_marginal_trial (over nddm_wiener.h's wiener_row, wiener_logpdf and wiener_log_survival) compiled by the host
-compiler as a stand-alone program against the stand-in for <hip/hip_runtime.h> of tools/wiener_quantile_host.py (the hardware's rcp / exp /
+compiler as a stand-alone program against the stand-in for <hip/hip_runtime.h> of tools/host_build.py (the hardware's rcp / exp /
 log become the C library's), optionally under AddressSanitizer and UndefinedBehaviorSanitizer.  A pass's node values live in a local array
 here, in LDS in the kernel; nothing else differs.
 
@@ -11,8 +11,6 @@ Usage: python tools/wiener_marginal_host.py [--sanitize] [--rows N] [--json OUT]
 tests/wiener_marginal_ref.py (prior_rows, box; one trial per row) the largest |log L - yardstick| of the header's float32 and of the
 scheme restated in float64 (the quadrature's own share), and the device bar 4 x the float32 figure rounded up to one significant digit.
 """
-import argparse
-import json
 import math
 import os
 import subprocess
@@ -23,7 +21,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import wiener_quantile_host as Q  # noqa: E402  (the stand-in header and the compiler call)
+import host_build as B  # noqa: E402  (the stand-in header, the compiler call, the command line)
 
 MAIN = r"""// usage: wiener_marginal_host T_CENSOR in.bin out.bin ; in: int32 n, int32 N, then n * (8 + 2N) floats (params, N trials); out: n * N floats
 #include <cstdio>
@@ -54,7 +52,7 @@ int main(int argc, char **argv) {
 
 
 def build(td, sanitize=False):
-    return Q.build(td, sanitize, main=MAIN, name="wiener_marginal_host")
+    return B.build(td, MAIN, "wiener_marginal_host", sanitize)
 
 
 def evaluate(exe, td, params, data, t_censor):
@@ -97,18 +95,5 @@ def survey(sanitize=False, n=1500):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sanitize", action="store_true")
-    ap.add_argument("--rows", type=int, default=1500)
-    ap.add_argument("--json")
-    a = ap.parse_args()
-    line = json.dumps(survey(a.sanitize, a.rows))
-    print(line)
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    B.cli(survey, rows=1500)

@@ -12,10 +12,7 @@ function's tests, and the reference sampler's tables (tests/golden/ratcliff.npz)
 
 Usage: python tools/wiener_quantile_host.py [--sanitize] [--json OUT]      (--sanitize: -fsanitize=address,undefined)
 """
-import argparse
-import json
 import os
-import shutil
 import subprocess
 import sys
 import tempfile
@@ -23,45 +20,8 @@ import tempfile
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "bayesflow_nddms_amd", "csrc")
-
-SHIM = r"""#pragma once
-#include <cmath>
-#include <cstring>
-#include <cstdint>
-#include <math.h>
-#define __device__
-#define __host__
-#define __global__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(x)
-struct float2 { float x, y; };
-inline float2 make_float2(float a, float b) { return {a, b}; }
-struct dim3s { unsigned x, y, z; };
-static dim3s threadIdx, blockIdx;
-inline void __syncthreads() {}
-#define __builtin_amdgcn_rcpf(x) (1.0f / (x))
-#define __builtin_amdgcn_rsqf(x) (1.0f / sqrtf(x))
-#define __builtin_amdgcn_exp2f(x) exp2f(x)
-#define __builtin_amdgcn_logf(x) log2f(x)
-#define __builtin_amdgcn_readlane(x, k) (x)
-inline float __expf(float x) { return expf(x); }
-inline float __logf(float x) { return logf(x); }
-inline float erfcxf(float xf) {
-    double x = xf;
-    if (x < 25.0) return (float)(exp(x * x) * erfc(x));
-    double i2 = 1.0 / (x * x);
-    return (float)(0.5641895835477563 / x * (1.0 - 0.5 * i2 + 0.75 * i2 * i2));
-}
-inline float sinpif(float x) { return (float)sin(M_PI * (double)x); }
-inline float cospif(float x) { return (float)cos(M_PI * (double)x); }
-inline unsigned __float_as_uint(float f) { unsigned u; memcpy(&u, &f, 4); return u; }
-inline float __uint_as_float(unsigned u) { float f; memcpy(&f, &u, 4); return f; }
-inline int __float_as_int(float f) { int u; memcpy(&u, &f, 4); return u; }
-inline float __int_as_float(int u) { float f; memcpy(&f, &u, 4); return f; }
-template <class T> inline T __shfl_xor(T s, int, int) { return s; }
-"""
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_build as B  # noqa: E402  (the stand-in header, the compiler call, the command line)
 
 MAIN = r"""// usage: wiener_quantile_host MODEL(0|3) FLAGS in.bin out.bin ; in: int32 n, then n*(P+2) floats (params, p, code); out: n * (rt, evaluations, F(rt), P(boundary))
 #include <cstdio>
@@ -100,19 +60,8 @@ int main(int argc, char **argv) {
 
 
 def build(td, sanitize=False, main=None, name="wiener_quantile_host"):
-    """Compile `main` (this tool's own program by default) against the stand-in header; tools/wiener_host.py builds its program here too."""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if not cxx:
-        raise RuntimeError("no host C++ compiler found")
-    os.makedirs(os.path.join(td, "hip"))
-    with open(os.path.join(td, "hip", "hip_runtime.h"), "w") as f:
-        f.write(SHIM)
-    with open(os.path.join(td, "main.cpp"), "w") as f:
-        f.write(MAIN if main is None else main)
-    exe = os.path.join(td, name)
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-    subprocess.check_call([cxx, "-std=c++17", "-w"] + flags + ["-I", td, "-I", CSRC, "-o", exe, os.path.join(td, "main.cpp")])
-    return exe
+    """Compile `main` (this tool's own program by default) against the stand-in header."""
+    return B.build(td, MAIN if main is None else main, name, sanitize)
 
 
 def solve(exe, td, model, flags, params, probs):
@@ -210,17 +159,5 @@ def _golden_tables(exe, td):
             "control_min": min(other)}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sanitize", action="store_true")
-    ap.add_argument("--json")
-    a = ap.parse_args()
-    line = json.dumps(survey(a.sanitize))
-    print(line)
-    if a.json:
-        with open(a.json, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    B.cli(survey)
