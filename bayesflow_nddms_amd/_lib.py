@@ -30,6 +30,7 @@ def _declare(L):
     L.nddm_set_tuning.argtypes = [c.c_int] * 6
     L.nddm_set_debug_trace.argtypes = [c.c_void_p, c.c_int, c.c_int]
     L.nddm_set_ordering.argtypes = [c.c_int]
+    L.nddm_set_queue_split.argtypes = [c.c_int]
     L.nddm_debug_set_slot_limit.argtypes = [c.c_int]
     L.nddm_debug_last_launch.argtypes = [c.POINTER(c.c_int32)]
     common = [c.c_int64, c.c_int32, c.c_float, c.c_int32, c.c_uint64, c.c_uint64, c.c_uint32]
@@ -77,7 +78,7 @@ EXPORTS = [
     "nddm_graph_arena_create", "nddm_graph_arena_bind", "nddm_graph_arena_info", "nddm_graph_arena_release", "nddm_build_info",
     "nddm_simulratcliff", "nddm_wiener_log_likelihood", "nddm_wiener_cdf", "nddm_wiener_quantile",
     "nddm_wiener_log_likelihood_grad", "nddm_wiener_marginal_log_likelihood", "nddm_wiener_marginal_log_likelihood_grad",
-    "nddm_wiener_hmc", "nddm_wiener_hmc_joint",
+    "nddm_wiener_hmc", "nddm_wiener_hmc_joint", "nddm_set_queue_split",
 ]
 
 

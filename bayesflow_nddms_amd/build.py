@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # NDDM_HIP_LIB: developer override (A/B runs of differently built libraries); the product path is the in-tree library
 SO_PATH = os.environ.get("NDDM_HIP_LIB") or os.path.join(_HERE, "libnddm_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", "nddm_kernels.hip")]
-HEADERS = [os.path.join(_HERE, "csrc", "nddm_rng.h"), os.path.join(_HERE, "csrc", "nddm_sim.h"),
+HEADERS = [os.path.join(_HERE, "csrc", "nddm_rng.h"), os.path.join(_HERE, "csrc", "nddm_sim.h"), os.path.join(_HERE, "csrc", "nddm_queue.h"),
            os.path.join(_HERE, "csrc", "nddm_prepass.h"), os.path.join(_HERE, "csrc", "nddm_ratcliff.h"),
            os.path.join(_HERE, "csrc", "nddm_wiener.h"), os.path.join(_HERE, "csrc", "nddm_wiener_cdf.h"),
            os.path.join(_HERE, "csrc", "nddm_wiener_quantile.h"), os.path.join(_HERE, "csrc", "nddm_wiener_grad.h"),

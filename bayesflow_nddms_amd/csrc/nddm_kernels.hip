@@ -98,12 +98,12 @@ static int check_stream(hipStream_t st)
 // ---- process-wide state, all of it behind one mutex -------------------------------------------------------------------
 // Entry points are re-entrant: each call takes a SNAPSHOT of the developer knobs at entry and owns the device memory it is
 // handed (a LaunchSlot) until the work it enqueued has completed.
-struct Tuning { int sets_per_chunk, ring, refill_thresh, variant, grid_waves, tile_trials, no_order; };
+struct Tuning { int sets_per_chunk, ring, refill_thresh, variant, grid_waves, tile_trials, no_order, queue_split; };
 // geometry of the calling thread's last launch (nddm_debug_last_launch)
 struct LastLaunch { int grid_waves, vkeys, ring, tile_trials, tiles_per_set, sets_per_chunk, refill_thresh, lds_bytes; };
 static thread_local LastLaunch g_last = {0, 0, 0, 0, 0, 0, 0, 0};
 static std::mutex g_mu;
-static Tuning g_tuning = {0, 0, 0, 0, 0, 0, 0};   // 0 = automatic (nddm_set_tuning overrides; benchmarking aid)
+static Tuning g_tuning = {0, 0, 0, 0, 0, 0, 0, -1};   // 0 = automatic (nddm_set_tuning overrides; benchmarking aid); queue_split: -1
 static unsigned long long *g_dbg = nullptr;       // nddm_set_debug_trace (profiling aid)
 static int g_dbg_waves = 0, g_dbg_chunks = 0;
 
@@ -329,18 +329,41 @@ static int resident_waves(K kernel, size_t lds_bytes, int cus)
     return cus * per_cu;
 }
 
+// The two-ended queue (nddm_sim.h: SimArgs::back_from): how many waves of a grid of `waves` pull their chunks from the BACK of the
+// processing order.  The eight waves of a SIMD do not progress evenly -- the arbiter favours the oldest, and the youngest (the highest
+// workgroup ids) execute a tenth of the blocks of the oldest (profiles/r20_wave_timeline_parent.txt) -- and the front of a sorted
+// queue holds the longest sets: a starved wave that pulls a chunk of cap-length trials at t = 0 is still on it when the queue runs dry,
+// and finishes it alone on its SIMD.  So the last waves of the grid take the short end, and the launch ends where the two ends meet.
+// queue_split: the knob (nddm_set_queue_split) n > 0 = that many waves, clamped; 0 = none; QUEUE_SPLIT_AUTO = the rule: a fraction of
+// the grid (QUEUE_SPLIT_NUM / QUEUE_SPLIT_DEN, chosen by the sweep in profiles/r20_queue_split_ab.txt) when the launch is sorted and runs
+// the full resident grid -- the caller says so by passing AUTO, else QUEUE_SPLIT_OFF -- and has QUEUE_SPLIT_MIN_CHUNKS chunks per wave;
+// not the VGPR-keys variant, which is chosen for launches whose SIMDs are not full.  Measured at 1M / 250k / 125k sets x 300 trials,
+// dt = .001 (41 / 31 / 15 chunks per wave): 1/8 of the grid -0.6 / +3.5 / +1.7 %, 1/4 +0.8 / +6.8 / +6.8 %, 3/8 +0.9 / +7.1 / +7.9 %.
+// The chunk sizing aims for 32 chunks per wave but cannot go below one set per chunk, and the shorter launches, whose tail weighs most,
+// gain most; below the 15 chunks per wave of the smallest shape measured nothing is known, so the rule stops a little under it.
+constexpr int QUEUE_SPLIT_AUTO = -1, QUEUE_SPLIT_OFF = 0;
+constexpr int QUEUE_SPLIT_NUM = 3, QUEUE_SPLIT_DEN = 8, QUEUE_SPLIT_MIN_CHUNKS = 12;
+static int back_waves(int queue_split, int waves, int n_chunks, bool vkeys)
+{
+    if (queue_split > 0) return queue_split < waves ? queue_split : waves;
+    if (queue_split != QUEUE_SPLIT_AUTO || vkeys || (long long)n_chunks < (long long)QUEUE_SPLIT_MIN_CHUNKS * waves) return 0;
+    return (int)((long long)waves * QUEUE_SPLIT_NUM / QUEUE_SPLIT_DEN);
+}
+
 // one (MODEL, BRIDGE, SMALL, PACKED, VKEYS) variant: pick the Gaussian transform and the step-cap form, size the grid
 template <int MODEL, bool BRIDGE, bool SMALL, bool PACKED, bool VKEYS, bool CODES = false, bool F64 = false>
-static void launch_variant(const SimArgs &A, bool fast, bool cap4, size_t lds_bytes, int n_chunks, int cus, int grid_override,
-                           bool grid_forced, hipStream_t st)
+static void launch_variant(const SimArgs &A0, bool fast, bool cap4, size_t lds_bytes, int n_chunks, int cus, int grid_override,
+                           bool grid_forced, int queue_split, hipStream_t st)
 {
     const dim3 block(WAVE);
+    SimArgs A = A0;
 #define NDDM_LAUNCH(KERNEL)                                                                    \
     do {                                                                                       \
         int waves = resident_waves(KERNEL, lds_bytes, cus);                                    \
         if (grid_override > 0 && (grid_override < waves || grid_forced)) waves = grid_override;\
         if (waves > n_chunks) waves = n_chunks;                                                \
         g_last.grid_waves = waves; g_last.vkeys = VKEYS ? 1 : 0;                               \
+        A.back_from = waves - back_waves(queue_split, waves, n_chunks, VKEYS);                 \
         hipLaunchKernelGGL(KERNEL, dim3(waves), block, lds_bytes, st, A);                      \
     } while (0)
     if (fast && cap4)       NDDM_LAUNCH((sim_kernel<MODEL, true, true, BRIDGE, SMALL, PACKED, VKEYS, CODES, F64>));
@@ -355,12 +378,12 @@ static void launch_variant(const SimArgs &A, bool fast, bool cap4, size_t lds_by
 // whose kernels have the registers to spare
 template <int MODEL, bool BRIDGE>
 static int launch_model(const SimArgs &A, bool fast, bool packed, bool vkeys, bool f64, size_t lds_bytes, int n_chunks, int cus,
-                        int grid_override, bool grid_forced, hipStream_t st)
+                        int grid_override, bool grid_forced, int queue_split, hipStream_t st)
 {
     const bool cap4 = (A.max_k % ((packed || BRIDGE) ? 8 : 4)) == 0;     // the step cap falls on a block boundary (bridge, packed: 8 steps per pass)
     const bool small = A.res16 == 2;
     constexpr bool HAS_VKEYS = !BRIDGE && (MODEL == NDDM_BASIC_DDM_DC || MODEL == NDDM_ALPHA_NOT_SCALED || MODEL == NDDM_EXPLICIT_BOUNDARY);
-#define NDDM_ARGS A, fast, cap4, lds_bytes, n_chunks, cus, grid_override, grid_forced, st
+#define NDDM_ARGS A, fast, cap4, lds_bytes, n_chunks, cus, grid_override, grid_forced, queue_split, st
     constexpr bool HAS_CODES = !BRIDGE && (MODEL == NDDM_BASIC_DDM_DC || MODEL == NDDM_ALPHA_NOT_SCALED);
     constexpr bool HAS_F64 = !BRIDGE && (MODEL == NDDM_BASIC_DDM_DC || MODEL == NDDM_SINGLE_TRIAL);
     if (f64) {                  // NDDM_STATE_F64 (the host has checked: basic / single, no bridge, not packed, no codes); round keys from LDS
@@ -675,17 +698,19 @@ static int simulate(int model, const float *params, const float *bounds, int64_t
         bool vkeys = plan_waves < 8ll * simds || n_chunks < 8ll * simds || est_blocks < 2.0e4 * (double)simds;
         if (tun.variant % 3 == 1) vkeys = false;                         // developer knob: 1 LDS keys, 2 VGPR keys, else the rule
         else if (tun.variant % 3 == 2) vkeys = true;
+        // the two-ended queue: the knob's value, or the rule (back_waves) for a sorted launch on the full resident grid
+        const int qsplit = tun.queue_split >= 0 ? tun.queue_split : (want_order && gw == 0 ? QUEUE_SPLIT_AUTO : QUEUE_SPLIT_OFF);
         g_last.ring = ring; g_last.tile_trials = tile_n; g_last.tiles_per_set = tiles; g_last.sets_per_chunk = spc;
         g_last.refill_thresh = A.refill_thresh; g_last.lds_bytes = (int)lds;
         switch (model) {
-        case NDDM_BASIC_DDM_DC: rc = launch_model<NDDM_BASIC_DDM_DC, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, st); break;
-        case NDDM_SINGLE_TRIAL: rc = launch_model<NDDM_SINGLE_TRIAL, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, st); break;
-        case NDDM_SINGLE_TRIAL_ALT: rc = launch_model<NDDM_SINGLE_TRIAL_ALT, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, st); break;
+        case NDDM_BASIC_DDM_DC: rc = launch_model<NDDM_BASIC_DDM_DC, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, qsplit, st); break;
+        case NDDM_SINGLE_TRIAL: rc = launch_model<NDDM_SINGLE_TRIAL, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, qsplit, st); break;
+        case NDDM_SINGLE_TRIAL_ALT: rc = launch_model<NDDM_SINGLE_TRIAL_ALT, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, qsplit, st); break;
         case NDDM_ALPHA_NOT_SCALED:
-            rc = bridge ? launch_model<NDDM_ALPHA_NOT_SCALED, true>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, st)
-                        : launch_model<NDDM_ALPHA_NOT_SCALED, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, st);
+            rc = bridge ? launch_model<NDDM_ALPHA_NOT_SCALED, true>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, qsplit, st)
+                        : launch_model<NDDM_ALPHA_NOT_SCALED, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, qsplit, st);
             break;
-        default: rc = launch_model<NDDM_EXPLICIT_BOUNDARY, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, st); break;
+        default: rc = launch_model<NDDM_EXPLICIT_BOUNDARY, false>(A, fast, packed, vkeys, f64, lds, (int)n_chunks, di.cus, gw, tun.grid_waves > 0, qsplit, st); break;
         }
     }
     if (rc == NDDM_OK && A.partials) {
@@ -842,8 +867,8 @@ int nddm_set_tuning(int sets_per_chunk, int ring, int refill_thresh, int variant
 {
     if (ring < 0 || ring == 1) return nddm::fail(NDDM_ERR_PARAM, "ring must be 0 (automatic) or >= 2%s");
     std::lock_guard<std::mutex> lock(nddm::g_mu);
-    const int no_order = nddm::g_tuning.no_order;
-    nddm::g_tuning = {sets_per_chunk, ring, refill_thresh, variant < 0 ? 0 : variant, grid_waves, tile_trials, no_order};
+    const int no_order = nddm::g_tuning.no_order, queue_split = nddm::g_tuning.queue_split;
+    nddm::g_tuning = {sets_per_chunk, ring, refill_thresh, variant < 0 ? 0 : variant, grid_waves, tile_trials, no_order, queue_split};
     return NDDM_OK;
 }
 
@@ -852,6 +877,15 @@ int nddm_set_ordering(int enabled)
 {
     std::lock_guard<std::mutex> lock(nddm::g_mu);
     nddm::g_tuning.no_order = enabled ? 0 : 1;
+    return NDDM_OK;
+}
+
+/* benchmarking aid: which waves pull their chunks from the back of the work queue.  -1 = the library's rule, 0 = none,
+ * n > 0 = the last n waves of whatever grid is launched (clamped to the grid) */
+int nddm_set_queue_split(int back_waves)
+{
+    std::lock_guard<std::mutex> lock(nddm::g_mu);
+    nddm::g_tuning.queue_split = back_waves < 0 ? -1 : back_waves;
     return NDDM_OK;
 }
 

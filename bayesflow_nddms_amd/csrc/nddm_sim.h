@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/nddm.h"
+#include "nddm_queue.h"
 #include "nddm_rng.h"
 
 namespace nddm {
@@ -51,8 +52,9 @@ struct SimArgs {
     uint32_t k0, k1;
     int sets_per_chunk;
     int n_chunks;
-    unsigned int *chunk_counter;   // device words [0] next chunk to hand out, [1] waves that have left; both are zero
-                                   // between launches: the last wave to leave resets them
+    unsigned int *chunk_counter;   // device words (8-byte aligned) [0] chunks pulled from the front of the queue, [1] chunks pulled
+                                   // from its back -- one 64-bit word, one atomic per pull (nddm_queue.h) --, [2] waves that have
+                                   // left; all zero between launches: the last wave to leave resets them
     int ring;                 // LDS ring slots (any number >= 2: the slot of tile t is t mod ring)
     int open_ahead;           // tiles staged ahead of the one being handed out (0 when work is scarce, else 1)
     float ext_sigma;
@@ -66,6 +68,8 @@ struct SimArgs {
                               // 2 = ... and the tile has <= 512 trials (the flush's 32-bit / DPP reduction path)
     int refill_thresh;        // leave the step loop once this many lanes hold a finished trial
     uint32_t ring_magic;      // floor(2^32 / ring): t mod ring by a multiply (ring_slot())
+    int back_from;            // workgroups >= back_from pull their chunks from the BACK of the processing order (the shortest expected
+                              // trials of a sorted launch), the others from the front; >= the grid: nobody does (open_tiles)
     double dt64, sqrt_dt64;   // NDDM_STATE_F64: (double)dt and its correctly rounded double square root (the reference's np.sqrt(dt))
 };
 
@@ -605,10 +609,16 @@ __global__ __launch_bounds__(WAVE) void sim_kernel(const SimArgs A)
             const bool have_pre = chunk_left > 0;                        // mid-chunk: this tile's record was prefetched
             if (chunk_left <= 0) {
                 if (chunk_left < 0) break;
-                unsigned int c = 0;
-                if (fresh_lane(lane) == 0) c = atomicAdd(R->chunk_counter, 1u);
-                c = __builtin_amdgcn_readfirstlane(c);
-                if (c >= (unsigned int)R->n_chunks) {
+                // one 64-bit atomic on the queue word: this wave's end of the queue is fixed by its workgroup id (kept in LDS)
+                const bool from_back = __builtin_amdgcn_readfirstlane((int)lds_raw[31]) >= R->back_from;
+                unsigned long long old = 0ull;
+                if (fresh_lane(lane) == 0)
+                    old = atomicAdd(reinterpret_cast<unsigned long long *>(R->chunk_counter), from_back ? QUEUE_BACK : QUEUE_FRONT);
+                old = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(old >> 32)) << 32) |
+                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)old);
+                const long long pulled = queue_pull(old, R->n_chunks, from_back);
+                const unsigned int c = (unsigned int)pulled;
+                if (pulled < 0) {
                     chunk_left = -1;
                     if (fresh_lane(lane) == 0 && R->dbg) dbg_stamp[3] = __builtin_amdgcn_s_memrealtime();      // the queue ran dry (trace)
                     break;
@@ -1087,8 +1097,8 @@ __global__ __launch_bounds__(WAVE) void sim_kernel(const SimArgs A)
     // per launch, and a captured launch is kernels only.
     if (lane == 0) {
         unsigned int *const q = fresh_args(Ak)->chunk_counter;
-        const unsigned int left = atomicAdd(q + 1, 1u);
-        if (left == gridDim.x - 1u) { atomicExch(q, 0u); atomicExch(q + 1, 0u); }
+        const unsigned int left = atomicAdd(q + 2, 1u);
+        if (left == gridDim.x - 1u) { atomicExch(reinterpret_cast<unsigned long long *>(q), 0ull); atomicExch(q + 2, 0u); }
     }
     unsigned long long *const dbg = fresh_args(Ak)->dbg;
     if (dbg && lane == 0) {

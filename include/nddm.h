@@ -175,6 +175,12 @@ int nddm_debug_last_launch(int32_t *out8);
 int nddm_set_tuning(int sets_per_chunk, int ring, int refill_thresh, int variant, int grid_waves, int tile_trials);
 /* 0 switches the longest-first ordering pre-pass off (sets are processed in the given order) */
 int nddm_set_ordering(int enabled);
+/* benchmarking aid: the two-ended work queue.  The waves of a launch pull chunks of sets from one queue; the last waves of the
+ * grid (the ones a full SIMD serves last) may pull from its BACK -- the shortest expected trials of a sorted launch -- so that
+ * none of them is left holding a chunk of long trials when the queue runs dry.  back_waves: -1 = the library's rule (a fraction
+ * of the grid, for sorted launches on the full resident grid with enough chunks per wave), 0 = every wave pulls from the front,
+ * n > 0 = the last n waves of whatever grid is launched, clamped to the grid.  Results never depend on it. */
+int nddm_set_queue_split(int back_waves);
 /* profiling aid: while set, every wave of the simulator kernels stores -- plain stores, no atomics -- one 8-word record
  * at buf[8 w ..], w = workgroup < wave_capacity: {step-loop blocks, refill phases, s_memtime cycles, lifetime, start, "found
  * the queue empty", end in s_memrealtime ticks (100 MHz), 1}; and the tick at which chunk c < chunk_capacity was pulled
