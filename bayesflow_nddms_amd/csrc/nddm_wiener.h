@@ -276,6 +276,9 @@ __device__ __forceinline__ float wiener_trial(const WienerRow &c, float x0, floa
     }
 }
 
+// Lane k's value as a wave-uniform one.  The kernels broadcast a struct of floats word by word with a loop written out in place: the same
+// loop as a function (by value, by reference or through a bit cast) cost the forward basic kernels 4 VGPRs and a wave per SIMD, and the
+// gradient kernels 8 to 14 VGPRs and a wave per SIMD (profiles/r21_wiener_sweep_resources.txt).
 __device__ __forceinline__ float wiener_bcast(float x, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), k)); }
 
 // The rows [rbase, rend) of workgroup blockIdx.x, ROWS at most.  STAGED (broadcast layout): the `chunks` workgroups of a data set split
@@ -299,6 +302,81 @@ __device__ __forceinline__ void wiener_stage_tile(float2 *tile, const float *src
     __syncthreads();                                                   // the previous tile is no longer read
     for (int j = threadIdx.x; j < nt; j += 256) tile[j] = make_float2(src[2 * j], src[2 * j + 1]);
     __syncthreads();
+}
+
+// The pairs of row `row`'s data set from trial t0 on
+__device__ __forceinline__ const float *wiener_pairs(const float *data, long long S, int N, long long row, int t0)
+{
+    return data + ((row / S) * (long long)N + t0) * 2;
+}
+
+// The one row of wave `wave`, for the kernels that give a wave one row and a workgroup ROWS = 4.  A wave without a row (the ragged last
+// workgroup) has nothing to do in the paired layout and returns; in the broadcast layout it still stages, so it goes on with the last
+// row's constants (`row` is clamped into range) and `has_row` keeps it from scoring and storing.
+struct WienerWaveRow {
+    long long rbase, row;
+    bool has_row;               // wave-uniform
+};
+template <bool STAGED, int ROWS>
+__device__ __forceinline__ WienerWaveRow wiener_wave_row(long long R, long long S, long long chunks, int wave)
+{
+    long long rbase, rend;
+    wiener_block_rows<STAGED, ROWS>(R, S, chunks, rbase, rend);
+    WienerWaveRow w;
+    w.rbase = rbase;
+    w.has_row = rbase + wave < rend;
+    w.row = w.has_row ? rbase + wave : rend - 1;
+    return w;
+}
+
+// The head of a kernel's tile loop, `for (int t0 = 0; t0 < N; t0 += WIENER_TILE)`: the number of trials nt <= WIENER_TILE of the tile
+// that begins at t0, after the workgroup has staged them (STAGED: every thread of the workgroup gets here; rbase tells the data set)
+template <bool STAGED>
+__device__ __forceinline__ int wiener_enter_tile(float2 *tile, const float *data, long long S, int N, long long rbase, int t0)
+{
+    const int nt = N - t0 < WIENER_TILE ? N - t0 : WIENER_TILE;
+    if (STAGED) wiener_stage_tile(tile, wiener_pairs(data, S, N, rbase, t0), nt);
+    return nt;
+}
+
+// A lane's pairs of one row in one tile: f(i, x0, x1) for the trials t0 + i, i = lane, lane + 64, ... below nt, in that order.
+// STAGED: from the staged tile; else from the row's own data set in HBM, and with PREFETCH the next pair is loaded before this one is
+// evaluated, so that HBM latency overlaps the arithmetic.
+template <bool STAGED, bool PREFETCH, class F>
+__device__ __forceinline__ void wiener_tile_trials(const float2 *tile, const float *data, long long S, int N, long long row, int t0, int nt, int lane,
+                                                   const F &f)
+{
+    const float *src = STAGED ? nullptr : wiener_pairs(data, S, N, row, t0);
+    float n0 = 0.0f, n1 = 0.0f;
+    if (!STAGED && PREFETCH && lane < nt) { n0 = src[2 * lane]; n1 = src[2 * lane + 1]; }
+    for (int i = lane; i < nt; i += 64) {
+        float x0, x1;
+        if (STAGED) { const float2 x = tile[i]; x0 = x.x; x1 = x.y; }
+        else if (PREFETCH) {
+            x0 = n0; x1 = n1;
+            if (i + 64 < nt) { n0 = src[2 * (i + 64)]; n1 = src[2 * (i + 64) + 1]; }
+        } else { x0 = src[2 * i]; x1 = src[2 * i + 1]; }
+        f(i, x0, x1);
+    }
+}
+
+// The whole sweep of a wave's one row: every tile staged by all, and f(t, x0, x1) for the lane's trials t = lane, lane + 64, ... below N
+// in the waves that have a row
+template <bool STAGED, bool PREFETCH, class F>
+__device__ __forceinline__ void wiener_row_trials(float2 *tile, const float *data, long long S, int N, const WienerWaveRow &w, int lane, const F &f)
+{
+    for (int t0 = 0; t0 < N; t0 += WIENER_TILE) {
+        const int nt = wiener_enter_tile<STAGED>(tile, data, S, N, w.rbase, t0);
+        if (w.has_row) wiener_tile_trials<STAGED, PREFETCH>(tile, data, S, N, w.row, t0, nt, lane, [&](int i, float x0, float x1) { f(t0 + i, x0, x1); });
+    }
+}
+
+// The sum of the 64 lanes' values in the butterfly's order (a + b == b + a: every lane ends with the same bits)
+__device__ __forceinline__ double wiener_wave_sum(double s)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m, 64);
+    return s;
 }
 
 // STAGED: the workgroup's rows all score one data set, read from LDS (broadcast layout); else every row reads its own (paired layout)
@@ -325,8 +403,7 @@ __global__ __launch_bounds__(256) void wiener_kernel(WienerArgs A)
     double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
     static_assert(WIENER_RPW == 4, "one partial sum per row of the wave");
     for (int t0 = 0; t0 < A.N; t0 += WIENER_TILE) {
-        const int nt = A.N - t0 < WIENER_TILE ? A.N - t0 : WIENER_TILE;
-        if (STAGED) wiener_stage_tile(tile, A.data + ((rbase / A.S) * (long long)A.N + t0) * 2, nt);
+        const int nt = wiener_enter_tile<STAGED>(tile, A.data, A.S, A.N, rbase, t0);       // (staged once for the wave's four rows)
 #pragma nounroll
         for (int k = 0; k < WIENER_RPW; ++k) {
             const long long row = wrow0 + 4ll * k;
@@ -336,23 +413,13 @@ __global__ __launch_bounds__(256) void wiener_kernel(WienerArgs A)
             float *cw = reinterpret_cast<float *>(&c);
 #pragma unroll
             for (int f = 0; f < WIENER_ROW_WORDS; ++f) cw[f] = wiener_bcast(m[f], k);
-            const float *src = STAGED ? nullptr : A.data + ((row / A.S) * (long long)A.N + t0) * 2;
             float *dst = A.out_trial ? A.out_trial + row * (long long)A.N + t0 : nullptr;
             double s = k == 0 ? acc0 : k == 1 ? acc1 : k == 2 ? acc2 : acc3;
-            // (paired layout: the next trial's pair is loaded before this one is evaluated, so that HBM latency overlaps the arithmetic)
-            float n0 = 0.0f, n1 = 0.0f;
-            if (!STAGED && lane < nt) { n0 = src[2 * lane]; n1 = src[2 * lane + 1]; }
-            for (int i = lane; i < nt; i += 64) {
-                float x0, x1;
-                if (STAGED) { const float2 x = tile[i]; x0 = x.x; x1 = x.y; }
-                else {
-                    x0 = n0; x1 = n1;
-                    if (i + 64 < nt) { n0 = src[2 * (i + 64)]; n1 = src[2 * (i + 64) + 1]; }
-                }
+            wiener_tile_trials<STAGED, true>(tile, A.data, A.S, A.N, row, t0, nt, lane, [&](int i, float x0, float x1) {
                 const float lf = wiener_trial<MODEL>(c, x0, x1);
                 if (dst) dst[i] = lf;
                 s += (double)lf;
-            }
+            });
             acc0 = k == 0 ? s : acc0; acc1 = k == 1 ? s : acc1; acc2 = k == 2 ? s : acc2; acc3 = k == 3 ? s : acc3;
         }
     }
@@ -360,9 +427,7 @@ __global__ __launch_bounds__(256) void wiener_kernel(WienerArgs A)
     for (int k = 0; k < WIENER_RPW; ++k) {
         const long long row = wrow0 + 4ll * k;
         if (row >= rend) break;
-        double s = k == 0 ? acc0 : k == 1 ? acc1 : k == 2 ? acc2 : acc3;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m, 64);       // a + b == b + a: every lane ends with the same bits
+        const double s = wiener_wave_sum(k == 0 ? acc0 : k == 1 ? acc1 : k == 2 ? acc2 : acc3);
         if (lane == 0) A.out_sum[row] = s;
     }
 }

@@ -213,8 +213,7 @@ __global__ __launch_bounds__(256) void wiener_cdf_kernel(WienerCdfArgs A)
     if (!A.out_cdf) return;
     const long long wrow0 = rbase + wave;                               // the wave's rows: wrow0 + 4k, k < WIENER_RPW
     for (int t0 = 0; t0 < A.N; t0 += WIENER_TILE) {
-        const int nt = A.N - t0 < WIENER_TILE ? A.N - t0 : WIENER_TILE;
-        if (STAGED) wiener_stage_tile(tile, A.data + ((rbase / A.S) * (long long)A.N + t0) * 2, nt);
+        const int nt = wiener_enter_tile<STAGED>(tile, A.data, A.S, A.N, rbase, t0);       // (staged once for the wave's four rows)
 #pragma nounroll
         for (int k = 0; k < WIENER_RPW; ++k) {
             const long long row = wrow0 + 4ll * k;
@@ -222,14 +221,9 @@ __global__ __launch_bounds__(256) void wiener_cdf_kernel(WienerCdfArgs A)
             const int lr = wave + 4 * k;
             const WienerCdfSide *cs = sides[lr];
             const WienerRow *wr = &wrows[MODEL == NDDM_BASIC_DDM_DC ? lr : 0];
-            const float *src = STAGED ? nullptr : A.data + ((row / A.S) * (long long)A.N + t0) * 2;
             float *dst = A.out_cdf + row * (long long)A.N + t0;
-            for (int i = lane; i < nt; i += 64) {
-                float x0, x1;
-                if (STAGED) { const float2 x = tile[i]; x0 = x.x; x1 = x.y; }
-                else { x0 = src[2 * i]; x1 = src[2 * i + 1]; }
-                dst[i] = wiener_cdf_trial<MODEL>(cs, wr, x0, x1);
-            }
+            wiener_tile_trials<STAGED, false>(tile, A.data, A.S, A.N, row, t0, nt, lane,
+                                              [&](int i, float x0, float x1) { dst[i] = wiener_cdf_trial<MODEL>(cs, wr, x0, x1); });
         }
     }
 }

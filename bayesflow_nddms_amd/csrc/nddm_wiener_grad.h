@@ -101,6 +101,33 @@ __device__ __forceinline__ WienerGradAcc wiener_grad_zero()
     return s;
 }
 
+// A lane's `poison` into its gradient sums, never into the value (basic_ddm_dc has no eta column: that sum stays 0).  The one place that
+// says which sums are poisoned: the kernels, the sampler's host build and the host tools all call it.
+template <int MODEL>
+__device__ __forceinline__ void wiener_grad_fold(WienerGradAcc &s)
+{
+    const double poison = (double)s.poison;
+    s.t += poison; s.a += poison; s.w += poison; s.nu += poison;
+    if (MODEL != NDDM_BASIC_DDM_DC) s.eta += poison;
+}
+
+// The fold, then every sum over the wave: every lane ends with the row's sums.  (wiener_wave_sum's butterfly with the sums side by side in
+// each step: as one wiener_wave_sum per sum the gradient kernels measured 0.6 to 1.2 % slower, profiles/r21_wiener_sweep_ab.txt.)
+template <int MODEL>
+__device__ __forceinline__ void wiener_grad_reduce(WienerGradAcc &s)
+{
+    wiener_grad_fold<MODEL>(s);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {                                  // a + b == b + a: every lane ends with the same bits
+        s.v += __shfl_xor(s.v, m, 64);
+        s.t += __shfl_xor(s.t, m, 64);
+        s.a += __shfl_xor(s.a, m, 64);
+        s.w += __shfl_xor(s.w, m, 64);
+        s.nu += __shfl_xor(s.nu, m, 64);
+        if (MODEL != NDDM_BASIC_DDM_DC) s.eta += __shfl_xor(s.eta, m, 64);
+    }
+}
+
 // One trial into a lane's sums.  The value is wiener_trial's; the partials repeat the density's expressions for A, B, q and the two sums
 // so that the compiler shares them.
 template <int MODEL>
@@ -190,12 +217,9 @@ __global__ __launch_bounds__(256) void wiener_grad_kernel(WienerGradArgs G)
     __shared__ float2 tile[STAGED ? WIENER_TILE : 1];
     static_assert(WIENER_GRAD_RPW == 1, "a wave holds one row's six partial sums");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long rbase, rend;
-    wiener_block_rows<STAGED, WIENER_GRAD_ROWS>(G.R, G.S, G.chunks, rbase, rend);
-    const bool has_row = rbase + wave < rend;                           // wave-uniform
-    if (!STAGED && !has_row) return;
-    const long long row = has_row ? rbase + wave : rend - 1;            // (a wave without a row still stages: it repeats the last one's constants)
-    const float *p = G.params + row * G.P;
+    const WienerWaveRow w = wiener_wave_row<STAGED, WIENER_GRAD_ROWS>(G.R, G.S, G.chunks, wave);
+    if (!STAGED && !w.has_row) return;
+    const float *p = G.params + w.row * G.P;
     // every lane works out the row's constants; the wave keeps lane 0's copy as uniform values
     WienerRow c;
     WienerGradRow g;
@@ -210,14 +234,12 @@ __global__ __launch_bounds__(256) void wiener_grad_kernel(WienerGradArgs G)
         for (int f = 0; f < WIENER_GRAD_ROW_WORDS; ++f) gw[f] = wiener_bcast(gm[f], 0);
     }
     WienerGradAcc s = wiener_grad_zero();
+    // wiener_row_trials<STAGED, true>, written out: with the trial as a functor this kernel's alpha_not_scaled broadcast launch measured 1 %
+    // slower than with the loop in place (profiles/r21_wiener_sweep_ab.txt), so here the sweep is its own copy of wiener_tile_trials' loop
     for (int t0 = 0; t0 < G.N; t0 += WIENER_TILE) {
-        const int nt = G.N - t0 < WIENER_TILE ? G.N - t0 : WIENER_TILE;
-        if (STAGED) {
-            wiener_stage_tile(tile, G.data + ((rbase / G.S) * (long long)G.N + t0) * 2, nt);
-            if (!has_row) continue;
-        }
-        const float *src = STAGED ? nullptr : G.data + ((row / G.S) * (long long)G.N + t0) * 2;
-        // (paired layout: the next trial's pair is loaded before this one is evaluated, as wiener_kernel does)
+        const int nt = wiener_enter_tile<STAGED>(tile, G.data, G.S, G.N, w.rbase, t0);
+        if (!w.has_row) continue;
+        const float *src = STAGED ? nullptr : wiener_pairs(G.data, G.S, G.N, w.row, t0);
         float n0 = 0.0f, n1 = 0.0f;
         if (!STAGED && lane < nt) { n0 = src[2 * lane]; n1 = src[2 * lane + 1]; }
         for (int i = lane; i < nt; i += 64) {
@@ -230,19 +252,9 @@ __global__ __launch_bounds__(256) void wiener_grad_kernel(WienerGradArgs G)
             wiener_grad_trial<MODEL>(c, g, x0, x1, s);
         }
     }
-    if (!has_row) return;
-    const double poison = (double)s.poison;
-    s.t += poison; s.a += poison; s.w += poison; s.nu += poison; s.eta += poison;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {                                  // a + b == b + a: every lane ends with the same bits
-        s.v += __shfl_xor(s.v, m, 64);
-        s.t += __shfl_xor(s.t, m, 64);
-        s.a += __shfl_xor(s.a, m, 64);
-        s.w += __shfl_xor(s.w, m, 64);
-        s.nu += __shfl_xor(s.nu, m, 64);
-        s.eta += __shfl_xor(s.eta, m, 64);
-    }
-    if (lane == 0) wiener_grad_finish<MODEL>(p, c.valid, s, G.out_sum ? G.out_sum + row : nullptr, G.out_grad + row * G.P);
+    if (!w.has_row) return;
+    wiener_grad_reduce<MODEL>(s);
+    if (lane == 0) wiener_grad_finish<MODEL>(p, c.valid, s, G.out_sum ? G.out_sum + w.row : nullptr, G.out_grad + w.row * G.P);
 }
 
 }  // namespace nddm

@@ -106,25 +106,21 @@ __device__ __forceinline__ void whmc_sigmoid(double x, double &sg, double &lsg, 
     l1sg = x >= 0.0 ? -x - l : -l;
 }
 
-// The row's six sums over the data set's N trials, every lane's copy alike.  `tile`: the wave's staged trials.
+// One lane's sums over its trials lane, lane + 64, ... of the data set.  `tile`: the wave's staged trials, all N of them (one tile from 0).
+__device__ __forceinline__ WienerGradAcc whmc_lane_sums(const WienerRow &c, const WienerGradRow &g, const float2 *tile, int N, int lane)
+{
+    WienerGradAcc s = wiener_grad_zero();
+    wiener_tile_trials<true, false>(tile, nullptr, 1, N, 0, 0, N, lane,
+                                    [&](int, float x0, float x1) { wiener_grad_trial<NDDM_BASIC_DDM_DC>(c, g, x0, x1, s); });
+    return s;
+}
+
+// The row's six sums over the data set's N trials, every lane's copy alike
 #ifndef WHMC_HOST
 __device__ __forceinline__ WienerGradAcc whmc_sums(const WienerRow &c, const WienerGradRow &g, const float2 *tile, int N, int lane)
 {
-    WienerGradAcc s = wiener_grad_zero();
-    for (int i = lane; i < N; i += 64) {
-        const float2 x = tile[i];
-        wiener_grad_trial<NDDM_BASIC_DDM_DC>(c, g, x.x, x.y, s);
-    }
-    const double poison = (double)s.poison;
-    s.t += poison; s.a += poison; s.w += poison; s.nu += poison;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {                                  // a + b == b + a: every lane ends with the same bits
-        s.v += __shfl_xor(s.v, m, 64);
-        s.t += __shfl_xor(s.t, m, 64);
-        s.a += __shfl_xor(s.a, m, 64);
-        s.w += __shfl_xor(s.w, m, 64);
-        s.nu += __shfl_xor(s.nu, m, 64);
-    }
+    WienerGradAcc s = whmc_lane_sums(c, g, tile, N, lane);
+    wiener_grad_reduce<NDDM_BASIC_DDM_DC>(s);
     return s;
 }
 
@@ -151,11 +147,8 @@ inline WienerGradAcc whmc_sums(const WienerRow &c, const WienerGradRow &g, const
 {
     WienerGradAcc L[64];
     for (int lane = 0; lane < 64; ++lane) {
-        WienerGradAcc s = wiener_grad_zero();
-        for (int i = lane; i < N; i += 64) wiener_grad_trial<NDDM_BASIC_DDM_DC>(c, g, tile[i].x, tile[i].y, s);
-        const double poison = (double)s.poison;
-        s.t += poison; s.a += poison; s.w += poison; s.nu += poison;
-        L[lane] = s;
+        L[lane] = whmc_lane_sums(c, g, tile, N, lane);
+        wiener_grad_fold<NDDM_BASIC_DDM_DC>(L[lane]);
     }
     for (int m = 1; m < 64; m <<= 1)                                    // lane 0's side of the butterfly: the pairwise tree in lane order
         for (int j = 0; j < 64; j += 2 * m) {

@@ -231,12 +231,9 @@ __global__ __launch_bounds__(256) void wiener_marginal_kernel(WienerMarginalArgs
     __shared__ float nodes[WMARG_K * 256];                              // a pass's node values, [k][thread]
     static_assert(WMARG_RPW == 1, "a wave holds one row");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long rbase, rend;
-    wiener_block_rows<STAGED, WMARG_ROWS>(G.R, G.S, G.chunks, rbase, rend);
-    const bool has_row = rbase + wave < rend;                           // wave-uniform
-    if (!STAGED && !has_row) return;
-    const long long row = has_row ? rbase + wave : rend - 1;            // (a wave without a row still stages: it repeats the last one's constants)
-    const float *p = G.params + row * G.P;
+    const WienerWaveRow w = wiener_wave_row<STAGED, WMARG_ROWS>(G.R, G.S, G.chunks, wave);
+    if (!STAGED && !w.has_row) return;
+    const float *p = G.params + w.row * G.P;
     // every lane works out the row's constants; the wave keeps lane 0's copy as uniform values
     WienerRow b;
     WienerMarginalRow r;
@@ -252,27 +249,15 @@ __global__ __launch_bounds__(256) void wiener_marginal_kernel(WienerMarginalArgs
     }
     float *buf = nodes + threadIdx.x;
     double s = 0.0;
-    for (int t0 = 0; t0 < G.N; t0 += WIENER_TILE) {
-        const int nt = G.N - t0 < WIENER_TILE ? G.N - t0 : WIENER_TILE;
-        if (STAGED) {
-            wiener_stage_tile(tile, G.data + ((rbase / G.S) * (long long)G.N + t0) * 2, nt);
-            if (!has_row) continue;
-        }
-        const float *src = STAGED ? nullptr : G.data + ((row / G.S) * (long long)G.N + t0) * 2;
-        float *dst = G.out_trial ? G.out_trial + row * (long long)G.N + t0 : nullptr;
-        for (int i = lane; i < nt; i += 64) {
-            float x0, x1;
-            if (STAGED) { const float2 x = tile[i]; x0 = x.x; x1 = x.y; }
-            else { x0 = src[2 * i]; x1 = src[2 * i + 1]; }
-            const float lf = wiener_marginal_trial(b, r, x0, x1, G.t_censor, buf, 256);
-            if (dst) dst[i] = lf;
-            s += (double)lf;
-        }
-    }
-    if (!G.out_sum || !has_row) return;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m, 64);           // a + b == b + a: every lane ends with the same bits
-    if (lane == 0) G.out_sum[row] = s;
+    float *dst = G.out_trial ? G.out_trial + w.row * (long long)G.N : nullptr;
+    wiener_row_trials<STAGED, false>(tile, G.data, G.S, G.N, w, lane, [&](int t, float x0, float x1) {
+        const float lf = wiener_marginal_trial(b, r, x0, x1, G.t_censor, buf, 256);
+        if (dst) dst[t] = lf;
+        s += (double)lf;
+    });
+    if (!G.out_sum || !w.has_row) return;
+    s = wiener_wave_sum(s);
+    if (lane == 0) G.out_sum[w.row] = s;
 }
 
 }  // namespace nddm

@@ -270,6 +270,27 @@ __device__ __forceinline__ WienerMarginalGradAcc wiener_marginal_grad_zero()
     return s;
 }
 
+// A lane's `poison` into its nine gradient sums, never into the value: the one place that says which sums are poisoned (the kernel and
+// the host tool both call it)
+__device__ __forceinline__ void wiener_marginal_grad_fold(WienerMarginalGradAcc &s)
+{
+    const double poison = (double)s.poison;
+    s.t += poison; s.a += poison; s.w += poison; s.nu += poison; s.m1 += poison; s.zm += poison; s.m2 += poison; s.dz += poison; s.dz2 += poison;
+}
+
+// The fold, then every sum over the wave: every lane ends with the row's sums (the sums side by side in each step of the butterfly, as
+// wiener_grad_reduce has them and for its reason: one wiener_wave_sum per sum measured 1.2 % slower on the broadcast launch)
+__device__ __forceinline__ void wiener_marginal_grad_reduce(WienerMarginalGradAcc &s)
+{
+    wiener_marginal_grad_fold(s);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {                                  // a + b == b + a: every lane ends with the same bits
+        s.v += __shfl_xor(s.v, m, 64); s.t += __shfl_xor(s.t, m, 64); s.a += __shfl_xor(s.a, m, 64); s.w += __shfl_xor(s.w, m, 64);
+        s.nu += __shfl_xor(s.nu, m, 64); s.m1 += __shfl_xor(s.m1, m, 64); s.zm += __shfl_xor(s.zm, m, 64); s.m2 += __shfl_xor(s.m2, m, 64);
+        s.dz += __shfl_xor(s.dz, m, 64); s.dz2 += __shfl_xor(s.dz2, m, 64);
+    }
+}
+
 // One trial into a lane's sums.  The window, the passes and the value are wiener_marginal_trial's, statement by statement; the last
 // pass also accumulates the weighted partials (file header).  `gmd`: gamma mu in float64.
 __device__ __forceinline__ void wiener_marginal_grad_trial(const WienerRow &b, const WienerMarginalRow &r, const WienerGradRow &g, double gmd, float y,
@@ -407,12 +428,9 @@ __global__ __launch_bounds__(256) void wiener_marginal_grad_kernel(WienerMargina
     __shared__ float nodes[WMARG_K * 256];                              // a pass's node values, [k][thread]
     static_assert(WMGRAD_RPW == 1, "a wave holds one row's ten partial sums");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long rbase, rend;
-    wiener_block_rows<STAGED, WMGRAD_ROWS>(G.R, G.S, G.chunks, rbase, rend);
-    const bool has_row = rbase + wave < rend;                           // wave-uniform
-    if (!STAGED && !has_row) return;
-    const long long row = has_row ? rbase + wave : rend - 1;            // (a wave without a row still stages: it repeats the last one's constants)
-    const float *p = G.params + row * G.P;
+    const WienerWaveRow w = wiener_wave_row<STAGED, WMGRAD_ROWS>(G.R, G.S, G.chunks, wave);
+    if (!STAGED && !w.has_row) return;
+    const float *p = G.params + w.row * G.P;
     // every lane works out the row's constants; the wave keeps lane 0's copy as uniform values
     WienerRow b;
     WienerMarginalRow r;
@@ -435,37 +453,11 @@ __global__ __launch_bounds__(256) void wiener_marginal_grad_kernel(WienerMargina
     const double gmd = (double)p[7] * (double)p[1];
     float *buf = nodes + threadIdx.x;
     WienerMarginalGradAcc s = wiener_marginal_grad_zero();
-    for (int t0 = 0; t0 < G.N; t0 += WIENER_TILE) {
-        const int nt = G.N - t0 < WIENER_TILE ? G.N - t0 : WIENER_TILE;
-        if (STAGED) {
-            wiener_stage_tile(tile, G.data + ((rbase / G.S) * (long long)G.N + t0) * 2, nt);
-            if (!has_row) continue;
-        }
-        const float *src = STAGED ? nullptr : G.data + ((row / G.S) * (long long)G.N + t0) * 2;
-        for (int i = lane; i < nt; i += 64) {
-            float x0, x1;
-            if (STAGED) { const float2 x = tile[i]; x0 = x.x; x1 = x.y; }
-            else { x0 = src[2 * i]; x1 = src[2 * i + 1]; }
-            wiener_marginal_grad_trial(b, r, g, gmd, x0, x1, G.t_censor, buf, 256, s);
-        }
-    }
-    if (!has_row) return;
-    const double poison = (double)s.poison;
-    s.t += poison; s.a += poison; s.w += poison; s.nu += poison; s.m1 += poison; s.zm += poison; s.m2 += poison; s.dz += poison; s.dz2 += poison;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {                                  // a + b == b + a: every lane ends with the same bits
-        s.v += __shfl_xor(s.v, m, 64);
-        s.t += __shfl_xor(s.t, m, 64);
-        s.a += __shfl_xor(s.a, m, 64);
-        s.w += __shfl_xor(s.w, m, 64);
-        s.nu += __shfl_xor(s.nu, m, 64);
-        s.m1 += __shfl_xor(s.m1, m, 64);
-        s.zm += __shfl_xor(s.zm, m, 64);
-        s.m2 += __shfl_xor(s.m2, m, 64);
-        s.dz += __shfl_xor(s.dz, m, 64);
-        s.dz2 += __shfl_xor(s.dz2, m, 64);
-    }
-    if (lane == 0) wiener_marginal_grad_finish(p, r.valid * b.valid, G.N, s, G.out_sum ? G.out_sum + row : nullptr, G.out_grad + row * WMGRAD_COLS);
+    wiener_row_trials<STAGED, false>(tile, G.data, G.S, G.N, w, lane,
+                                     [&](int, float x0, float x1) { wiener_marginal_grad_trial(b, r, g, gmd, x0, x1, G.t_censor, buf, 256, s); });
+    if (!w.has_row) return;
+    wiener_marginal_grad_reduce(s);
+    if (lane == 0) wiener_marginal_grad_finish(p, r.valid * b.valid, G.N, s, G.out_sum ? G.out_sum + w.row : nullptr, G.out_grad + w.row * WMGRAD_COLS);
 }
 
 }  // namespace nddm

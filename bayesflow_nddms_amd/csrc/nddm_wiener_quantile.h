@@ -171,22 +171,17 @@ __global__ __launch_bounds__(256) void wiener_quantile_kernel(WienerQuantileArgs
     __syncthreads();
     const long long wrow0 = rbase + wave;                               // the wave's rows: wrow0 + 4k, k < WIENER_RPW
     for (int t0 = 0; t0 < A.N; t0 += WIENER_TILE) {
-        const int nt = A.N - t0 < WIENER_TILE ? A.N - t0 : WIENER_TILE;
-        if (STAGED) wiener_stage_tile(tile, A.data + ((rbase / A.S) * (long long)A.N + t0) * 2, nt);
+        const int nt = wiener_enter_tile<STAGED>(tile, A.data, A.S, A.N, rbase, t0);       // (staged once for the wave's four rows)
 #pragma nounroll
         for (int k = 0; k < WIENER_RPW; ++k) {
             const long long row = wrow0 + 4ll * k;
             if (row >= rend) break;                                     // wave-uniform
             const int lr = wave + 4 * k;
-            const float *src = STAGED ? nullptr : A.data + ((row / A.S) * (long long)A.N + t0) * 2;
             float *dst = A.out_q + row * (long long)A.N + t0;
-            for (int i = lane; i < nt; i += 64) {
-                float x0, x1;
-                if (STAGED) { const float2 x = tile[i]; x0 = x.x; x1 = x.y; }
-                else { x0 = src[2 * i]; x1 = src[2 * i + 1]; }
+            wiener_tile_trials<STAGED, false>(tile, A.data, A.S, A.N, row, t0, nt, lane, [&](int i, float x0, float x1) {
                 int evals;
                 dst[i] = wiener_quantile_request(sides[lr], qsides[lr], x0, x1, A.flags, evals);
-            }
+            });
         }
     }
 }

@@ -10,8 +10,9 @@ import wiener_marginal_ref as M
 pytestmark = pytest.mark.gpu
 
 # (D, S, N): paired layouts (S = 1) with N < 64, a partial last wave and workgroup, more than one LDS tile's worth of trials; broadcast
-# layouts (S >= 16) with a partial last workgroup per data set and N no multiple of 64
-SHAPES = [(1, 1, 1), (5, 1, 65), (3, 1, 1025), (2, 16, 1), (2, 17, 130)]
+# layouts (S >= 16) with a partial last workgroup per data set and N no multiple of 64; (2, 17, 1025): S = 17 is the smallest S the plan
+# stages (S >= 16) with S % 4 == 1, so each data set's last workgroup has one row and three waves that only stage, across two tiles
+SHAPES = [(1, 1, 1), (5, 1, 65), (3, 1, 1025), (2, 16, 1), (2, 17, 130), (2, 17, 1025)]
 K_TRIALS = 6              # distinct trials per data set; a data set of N trials cycles through them
 GOOD = [0.8, 1.2, 0.45, 0.2, 0.5, 1.1, 0.7, 1.0]
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The per-trial code and the chain rule of csrc/nddm_wiener_grad.h run on the HOST, without a GPU: the header's own wiener_grad_row,
-wiener_grad_trial and wiener_grad_finish (over nddm_wiener.h's wiener_row and wiener_trial) compiled by the host compiler as a stand-alone
+wiener_grad_trial, wiener_grad_fold and wiener_grad_finish (over nddm_wiener.h's wiener_row and wiener_trial) compiled by the host compiler as a stand-alone
 program against the stand-in for <hip/hip_runtime.h> of tools/host_build.py (the hardware's rcp / exp / log become the C
 library's), optionally under AddressSanitizer and UndefinedBehaviorSanitizer.  A row's trials are summed in one sequence here (one lane), not
 in the kernel's 64 interleaved ones: the float64 sums differ in their last bits, nothing more.
@@ -37,8 +37,7 @@ template <int MODEL> void run(int n, int N, int P, const float *in, double *out)
         const WienerGradRow g = wiener_grad_row<MODEL>(p, c);
         WienerGradAcc s = wiener_grad_zero();
         for (int j = 0; j < N; ++j) wiener_grad_trial<MODEL>(c, g, d[2 * j], d[2 * j + 1], s);
-        const double poison = (double)s.poison;
-        s.t += poison; s.a += poison; s.w += poison; s.nu += poison; s.eta += poison;
+        wiener_grad_fold<MODEL>(s);
         wiener_grad_finish<MODEL>(p, c.valid, s, out + (size_t)i * (1 + P), out + (size_t)i * (1 + P) + 1);
     }
 }

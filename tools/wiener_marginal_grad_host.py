@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The per-trial code and the chain rule of csrc/nddm_wiener_marginal_grad.h run on the HOST, without a GPU: the header's own
-wiener_marginal_grad_trial and wiener_marginal_grad_finish (over nddm_wiener_marginal.h's row constants and node, nddm_wiener_grad.h's row
+wiener_marginal_grad_trial, wiener_marginal_grad_fold and wiener_marginal_grad_finish (over nddm_wiener_marginal.h's row constants and node, nddm_wiener_grad.h's row
 constants and the header's own partials of log S) compiled by the host compiler as a stand-alone program with its own main against the
 stand-in for <hip/hip_runtime.h> of tools/host_build.py (the hardware's rcp / exp / log become the C library's), optionally under
 AddressSanitizer and UndefinedBehaviorSanitizer.  Nothing is loaded into Python.  A pass's node values live in a local array here, in LDS in the
@@ -70,8 +70,7 @@ int main(int argc, char **argv) {
             const WienerGradRow g = wiener_grad_row<NDDM_BASIC_DDM_DC>(pb, b);
             WienerMarginalGradAcc s = wiener_marginal_grad_zero();
             for (int j = 0; j < N; ++j) wiener_marginal_grad_trial(b, r, g, (double)p[7] * (double)p[1], d[2 * j], d[2 * j + 1], t_censor, buf, 1, s);
-            const double poison = (double)s.poison;
-            s.t += poison; s.a += poison; s.w += poison; s.nu += poison; s.m1 += poison; s.zm += poison; s.m2 += poison; s.dz += poison; s.dz2 += poison;
+            wiener_marginal_grad_fold(s);
             wiener_marginal_grad_finish(p, r.valid * b.valid, N, s, &out[(size_t)i * 9], &out[(size_t)i * 9 + 1]);
         }
         fwrite(out.data(), 8, out.size(), f);
