@@ -9,6 +9,7 @@ NDDM_OK, NDDM_ERR_NULL, NDDM_ERR_SHAPE, NDDM_ERR_PARAM, NDDM_ERR_HIP, NDDM_ERR_N
 GAUSS_EXACT, GAUSS_FAST, BRIDGE, GAUSS_PACKED, STATE_F64 = 0, 1, 2, 4, 8
 QUANTILE_CONDITIONAL = 1             # nddm_wiener_quantile's flag (a namespace of its own)
 HMC_SIGMA_FIXED = 1                  # nddm_wiener_hmc_joint's flag (a namespace of its own)
+WIENER_CENSORED = 4                  # nddm_wiener_log_likelihood_grad's flag: score basic_ddm_dc's timeouts in the gradient too
 ABI_VERSION = 4
 
 _lib = None

@@ -96,18 +96,19 @@ def log_likelihood(params, sim_data, per_trial=False):
     return (r["loglik"], r["trial_logp"]) if per_trial else r["loglik"]
 
 
-def log_likelihood_and_grad(params, sim_data):
+def log_likelihood_and_grad(params, sim_data, censored=False):
     """log p(sim_data | params) and its gradient in (drift, boundary, beta, tau, dc), one launch (engine.wiener_log_likelihood_grad): the
     arguments of log_likelihood.  Returns (float64 [R], float64 [R, 5]) on the device; the first has log_likelihood's bits.
-    NOT IMPLEMENTED: the gradient of a censored timeout (choice 0) -- a row that holds one keeps its value and gets NaN in every
-    gradient column.  For a differentiable torch value see likelihood.wiener_loglik."""
+    censored=True: a censored timeout (choice 0, as simulate_trials writes it) adds the gradient of log P(T > rt - tau), so data straight
+    from the simulator have a finite gradient.  With the default that is NOT IMPLEMENTED -- a row that holds a timeout keeps its value and
+    gets NaN in every gradient column.  For a differentiable torch value see likelihood.wiener_loglik."""
     p = params if hasattr(params, "is_cuda") else np.asarray(params, dtype=np.float64).reshape(-1, 5)
     d = sim_data if hasattr(sim_data, "is_cuda") else np.asarray(sim_data, dtype=np.float64)
     R = p.shape[0] if p.ndim == 2 else 1
     D = d.shape[0] if d.ndim == 3 else 1
     if R % D:
         raise ValueError(f"{R} parameter rows cannot be split over {D} data sets")
-    r = engine.wiener_log_likelihood_grad(MODEL, p, d, draws_per_dataset=R // D)
+    r = engine.wiener_log_likelihood_grad(MODEL, p, d, draws_per_dataset=R // D, **({"censored": True} if censored else {}))
     return r["loglik"], r["grad"]
 
 
@@ -137,6 +138,8 @@ def quantile(params, probs=(.1, .3, .5, .7, .9)):
 def fit_hmc(data, **kw):
     """The reference's likelihood-based fit of this model (basic_ddm_dc_pyjags.py: JAGS over dwiener) by batched Hamiltonian Monte Carlo on
     the device: mcmc.hmc_fit's arguments and its result, the reference's JAGS-sample layout (alpha, ndt, beta, delta, varsigma, each
-    [participants, samples, chains]) that diagnostics.rhat_neff reads."""
+    [participants, samples, chains]) that diagnostics.rhat_neff reads.  censored=True: data straight from simulate_trials /
+    batch_simulate_trials, timeouts (choice 0 at rt = max_steps * dt + tau) included, scored right-censored; without it a data set that
+    holds a timeout is refused (a host array) or flagged (a device tensor)."""
     from . import mcmc
     return mcmc.hmc_fit(data, **kw)

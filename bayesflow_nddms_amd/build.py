@@ -17,6 +17,7 @@ HEADERS = [os.path.join(_HERE, "csrc", "nddm_rng.h"), os.path.join(_HERE, "csrc"
            os.path.join(_HERE, "csrc", "nddm_prepass.h"), os.path.join(_HERE, "csrc", "nddm_ratcliff.h"),
            os.path.join(_HERE, "csrc", "nddm_wiener.h"), os.path.join(_HERE, "csrc", "nddm_wiener_cdf.h"),
            os.path.join(_HERE, "csrc", "nddm_wiener_quantile.h"), os.path.join(_HERE, "csrc", "nddm_wiener_grad.h"),
+           os.path.join(_HERE, "csrc", "nddm_wiener_survival_grad.h"),
            os.path.join(_HERE, "csrc", "nddm_wiener_marginal.h"), os.path.join(_HERE, "csrc", "nddm_wiener_marginal_grad.h"),
            os.path.join(_HERE, "csrc", "nddm_wiener_hmc.h"),
            os.path.join(_HERE, "csrc", "nddm_wiener_hmc_joint.h"),

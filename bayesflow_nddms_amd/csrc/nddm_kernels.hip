@@ -1218,20 +1218,28 @@ int nddm_wiener_quantile(int32_t model, const float *params, int64_t R, int64_t 
                          params && probs, out_q != nullptr, stream, A, K[model == NDDM_ALPHA_NOT_SCALED]);
 }
 
-/* the value and the gradient of the Wiener first-passage log-likelihood in one launch: csrc/nddm_wiener_grad.h.  out_loglik may be NULL. */
+/* the value and the gradient of the Wiener first-passage log-likelihood in one launch: csrc/nddm_wiener_grad.h.  out_loglik may be NULL.
+ * NDDM_WIENER_CENSORED (basic_ddm_dc only) dispatches the instantiations that score a timeout's gradient; without it the kernels are the
+ * ones there were. */
 int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
                                     int32_t n_trials, uint32_t flags, double *out_loglik, double *out_grad, void *stream)
 {
     using namespace nddm;
-    static const WienerEntry E = {"nddm_wiener_log_likelihood_grad: model %s has no closed-form likelihood here (NDDM_BASIC_DDM_DC and "
-                                  "NDDM_ALPHA_NOT_SCALED only)", "nddm_wiener_log_likelihood_grad: flags must be 0 (reserved)%s", WIENER_SHAPE_MSG,
-                                  WIENER_NULL_IN_MSG, "out_grad is NULL%s", "wiener gradient kernel launch failed: %s", WIENER_GRAD_ROWS};
+#define NDDM_GRAD_ENTRY(flags_msg)                                                                                                          \
+    {"nddm_wiener_log_likelihood_grad: model %s has no closed-form likelihood here (NDDM_BASIC_DDM_DC and NDDM_ALPHA_NOT_SCALED only)",      \
+     flags_msg, WIENER_SHAPE_MSG, WIENER_NULL_IN_MSG, "out_grad is NULL%s", "wiener gradient kernel launch failed: %s", WIENER_GRAD_ROWS}
+    static const WienerEntry E = NDDM_GRAD_ENTRY("nddm_wiener_log_likelihood_grad: flags must be 0 (reserved)%s");
+    static const WienerEntry EC = NDDM_GRAD_ENTRY("nddm_wiener_log_likelihood_grad: NDDM_WIENER_CENSORED takes NDDM_BASIC_DDM_DC only "
+                                                  "(alpha_not_scaled's y == 0 carries no time)%s");
+#undef NDDM_GRAD_ENTRY
     static void (*const K[2][2])(WienerGradArgs) = {{wiener_grad_kernel<NDDM_BASIC_DDM_DC, false>, wiener_grad_kernel<NDDM_BASIC_DDM_DC, true>},
                                                     {wiener_grad_kernel<NDDM_ALPHA_NOT_SCALED, false>, wiener_grad_kernel<NDDM_ALPHA_NOT_SCALED, true>}};
+    static void (*const KC[2])(WienerGradArgs) = {wiener_grad_kernel<NDDM_BASIC_DDM_DC, false, true>, wiener_grad_kernel<NDDM_BASIC_DDM_DC, true, true>};
+    const bool censored = flags == NDDM_WIENER_CENSORED, alpha = model == NDDM_ALPHA_NOT_SCALED;
     WienerGradArgs A;
     A.out_sum = out_loglik; A.out_grad = out_grad;
-    return wiener_launch(E, model, wiener_closed_form(model), flags == 0u, params, data, R, draws_per_dataset, n_trials, params && data,
-                         out_grad != nullptr, stream, A, K[model == NDDM_ALPHA_NOT_SCALED]);
+    return wiener_launch(censored && alpha ? EC : E, model, wiener_closed_form(model), flags == 0u || (censored && !alpha), params, data, R,
+                         draws_per_dataset, n_trials, params && data, out_grad != nullptr, stream, A, censored ? KC : K[alpha]);
 }
 
 /* batched Hamiltonian Monte Carlo over the basic_ddm_dc Wiener posterior, one wave per chain: csrc/nddm_wiener_hmc.h.  A chain is a row of
@@ -1243,7 +1251,7 @@ int nddm_wiener_hmc(int32_t model, const float *data, int64_t D, int32_t n_trial
 {
     using namespace nddm;
     static const WienerEntry E = {"nddm_wiener_hmc: model %s has no sampler here (NDDM_BASIC_DDM_DC only)",
-                                  "nddm_wiener_hmc: flags must be 0 (reserved) and free_mask < 32%s",
+                                  "nddm_wiener_hmc: flags must be 0 (reserved) and free_mask < 32%s",   /* (or NDDM_WIENER_CENSORED; the words are pinned) */
                                   "C >= 0 chains = D x chains_per_dataset > 0, 0 < n_trials <= 2048, n_iter, n_leapfrog, thin > 0, n_adapt >= 0, "
                                   "n_iter x n_leapfrog x ceil(n_trials / 64) <= 2^19 per launch and chain / iteration indices < 2^32 are required%s",
                                   "data or state is NULL%s", WIENER_NULL_OUT_MSG, "wiener hmc kernel launch failed: %s", 4};
@@ -1251,7 +1259,8 @@ int nddm_wiener_hmc(int32_t model, const float *data, int64_t D, int32_t n_trial
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool shape_ok = whmc_shape_ok(D, chains_per_dataset, C, n_trials, n_iter, n_adapt, n_leapfrog, thin, chain_offset, iter_offset);
     bool empty;
-    if (const int rc = wiener_checks(E, model, model == NDDM_BASIC_DDM_DC, flags == 0u && free_mask < 32u, C, chains_per_dataset, n_trials,
+    const bool censored = flags == NDDM_WIENER_CENSORED;
+    if (const int rc = wiener_checks(E, model, model == NDDM_BASIC_DDM_DC, (flags == 0u || censored) && free_mask < 32u, C, chains_per_dataset, n_trials,
                                      data && state, out_draws || out_log_post || out_accept || out_divergent || out_flagged, st, &empty,
                                      shape_ok)) return rc;
     if (empty) return NDDM_OK;
@@ -1259,7 +1268,7 @@ int nddm_wiener_hmc(int32_t model, const float *data, int64_t D, int32_t n_trial
     whmc_fill(A, data, state, inv_mass, chains_per_dataset, n_trials, n_iter, n_adapt, n_leapfrog, thin, free_mask, seed, chain_offset, iter_offset,
               out_draws, out_log_post, out_accept, out_divergent, out_flagged);
     A.C = C;
-    hipLaunchKernelGGL(wiener_hmc_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(censored ? wiener_hmc_censored_kernel : wiener_hmc_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, A);
     return launch_status(hipGetLastError(), E.launch_msg);
 }
 
@@ -1284,7 +1293,9 @@ int nddm_wiener_hmc_joint(int32_t model, const float *data, int64_t P, int32_t n
     const bool shape_ok = whmc_shape_ok(P, chains, C, n_trials, n_iter, n_adapt, n_leapfrog, thin, chain_offset, iter_offset) &&
                           n_iter <= WHMCJ_MAX_ITER && (fixed || P >= 2 || C == 0);
     bool empty;
-    if (const int rc = wiener_checks(E, model, model == NDDM_BASIC_DDM_DC, (flags & ~NDDM_HMC_SIGMA_FIXED) == 0u && free_mask < 32u, C, chains,
+    const bool censored = (flags & NDDM_WIENER_CENSORED) != 0u;
+    if (const int rc = wiener_checks(E, model, model == NDDM_BASIC_DDM_DC,
+                                     (flags & ~(NDDM_HMC_SIGMA_FIXED | NDDM_WIENER_CENSORED)) == 0u && free_mask < 32u, C, chains,
                                      n_trials, data && extdata && state && sigma && workspace,
                                      out_draws || out_log_post || out_accept || out_divergent || out_flagged || out_sigma || out_sigma_accept, st,
                                      &empty, shape_ok)) return rc;
@@ -1293,12 +1304,12 @@ int nddm_wiener_hmc_joint(int32_t model, const float *data, int64_t P, int32_t n
     whmc_fill(A, data, state, inv_mass, chains, n_trials, n_iter, n_adapt, n_leapfrog, thin, free_mask, seed, chain_offset, iter_offset, out_draws,
               out_log_post, out_accept, out_divergent, out_flagged);
     A.ext = extdata; A.sigma = sigma; A.ws = workspace; A.out_sigma = out_sigma; A.out_sigma_accept = out_sigma_accept;
-    A.P = P; A.sigma_fixed = fixed ? 1 : 0; A.it = 0;
+    A.P = P; A.sigma_fixed = fixed ? 1 : 0; A.it = 0; A.censored = censored ? 1 : 0;
     hipLaunchKernelGGL(wiener_hmc_joint_prepass_kernel, dim3(1), dim3(256), 0, st, A);
     hipError_t e = hipGetLastError();
     for (int it = 0; it < n_iter && e == hipSuccess; ++it) {
         A.it = it;
-        hipLaunchKernelGGL(wiener_hmc_joint_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(censored ? wiener_hmc_censored_joint_kernel : wiener_hmc_joint_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, A);
         if (!fixed) hipLaunchKernelGGL(wiener_hmc_joint_sigma_kernel, dim3((unsigned)((chains + 3) / 4)), dim3(256), 0, st, A);
         e = hipGetLastError();
     }

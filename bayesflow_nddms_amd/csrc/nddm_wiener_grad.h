@@ -32,9 +32,13 @@
 // its neighbours unaffected; a trial with t <= 0 gives -inf in the value, as the density does, and NaN in every gradient column of its
 // row; alpha_not_scaled's y == 0 gives NaN in both.
 //   basic_ddm_dc's censored timeouts (choice 0): the VALUE scores them exactly as wiener_kernel does (wiener_log_survival), so the row's
-//   log-likelihood is unchanged; the GRADIENT of log S in its two forms is NOT IMPLEMENTED, and a row with a censored trial gets NaN in
-//   every gradient column, never a partial gradient that silently leaves the censored trials out.  (Done by poisoning the row's sums; the
-//   value's summation order does not change.)
+//   log-likelihood is unchanged.  The GRADIENT is opt-in (NDDM_WIENER_CENSORED, the CENSORED instantiations): without the flag a row with a
+//   censored trial gets NaN in every gradient column, never a partial gradient that silently leaves the censored trials out (done by
+//   poisoning the row's sums; the value's summation order does not change).  With it a censored trial adds the partials of
+//   log S(t; a', w, v') to the same sums: d/da', d/dw, d/dv' from wiener_log_survival_grad (nddm_wiener_survival_grad.h, both forms, the
+//   value's select) and d/dt = -(f_lower + f_upper) / S (wiener_grad_censored), so d/dtau = +(f_lower + f_upper) / S through the row's chain
+//   rule.  A censored trial with t <= 0 is log 1 = 0 with zero partials; a non-finite rt or a choice other than 1, -1, 0 poisons the row.
+//   The value is wiener_trial's in either case, bit for bit.
 //
 // Execution: the two layouts and the dispatch rule of wiener_kernel (broadcast, the data set staged in LDS one WIENER_TILE at a time,
 // when draws_per_dataset >= WIENER_ROWS; paired otherwise).  Six float64 partial sums per row do not fit four rows per wave in the
@@ -45,6 +49,7 @@
 // the grid, the stream or a capture.  No scratch memory, no atomics; stores are plain vector stores.
 #pragma once
 #include "nddm_wiener.h"
+#include "nddm_wiener_survival_grad.h"
 
 namespace nddm {
 
@@ -128,16 +133,47 @@ __device__ __forceinline__ void wiener_grad_reduce(WienerGradAcc &s)
     }
 }
 
+// A censored timeout of basic_ddm_dc (choice 0 at response time rt) into a lane's gradient sums: the partials of log S(t; a', w, v') at
+// t = rt - tau.  a', w = beta and v' are wiener_log_survival_grad's; d/dt log S = -(f_lower(t) + f_upper(t)) / S(t) is formed as
+// -(e^{log f_lower - log S} + e^{log f_upper - log S}) from wiener_logpdf's two values and the same log S: exact (no second series to
+// truncate), it cannot overflow where S is small, and at large t it tends to lambda_1 as it must.  t <= 0 is log 1 = 0 with zero partials,
+// not a poison; a non-finite rt poisons the row.  (The value has already been added by the caller: wiener_trial's.)
+__device__ __forceinline__ void wiener_grad_censored(const WienerRow &c, float rt, WienerGradAcc &s)
+{
+    const float t = rt - c.tau;
+    if (t > 0.0f) {
+        const WienerSurvivalGrad h = wiener_log_survival_grad(c, t);
+        const float fl = wiener_logpdf<NDDM_BASIC_DDM_DC>(c, rt, 0), fu = wiener_logpdf<NDDM_BASIC_DDM_DC>(c, rt, 1);
+        const float haz = __expf(fminf(fl - h.ls, 80.0f)) + __expf(fminf(fu - h.ls, 80.0f));
+        s.t -= (double)haz;
+        s.a += (double)h.da;
+        s.w += (double)h.dw;
+        s.nu += (double)h.dv;
+    }
+    s.poison += fabsf(rt) < __builtin_inff() ? 0.0f : __builtin_nanf("");
+}
+
 // One trial into a lane's sums.  The value is wiener_trial's; the partials repeat the density's expressions for A, B, q and the two sums
-// so that the compiler shares them.
-template <int MODEL>
+// so that the compiler shares them.  CENSORED (basic_ddm_dc, NDDM_WIENER_CENSORED): a choice-0 trial adds the partials of log S
+// (wiener_grad_censored) and any choice other than 1, -1 and 0 poisons the row; the branch is taken by the lanes that hold a timeout, so
+// a sweep in which no lane holds one skips the survival code as a wave.  Without it a choice-0 trial poisons the row, and the
+// instantiation holds none of the survival code.
+template <int MODEL, bool CENSORED = false>
 __device__ __forceinline__ void wiener_grad_trial(const WienerRow &c, const WienerGradRow &g, float x0, float x1, WienerGradAcc &s)
 {
+    static_assert(!CENSORED || MODEL == NDDM_BASIC_DDM_DC, "only basic_ddm_dc's timeouts carry a time");
     s.v += (double)wiener_trial<MODEL>(c, x0, x1);
+    if (CENSORED && x1 == 0.0f) {
+        wiener_grad_censored(c, x0, s);
+        return;
+    }
     float rt;
     int sd;
     bool bad;
-    if (MODEL == NDDM_BASIC_DDM_DC) { rt = x0; sd = x1 > 0.0f ? 1 : 0; bad = x1 == 0.0f || x1 != x1; }    // censored: no gradient here
+    if (MODEL == NDDM_BASIC_DDM_DC) {                                   // without CENSORED a timeout has no gradient here
+        rt = x0; sd = x1 > 0.0f ? 1 : 0;
+        bad = CENSORED ? !(x1 == 1.0f || x1 == -1.0f) : x1 == 0.0f || x1 != x1;
+    }
     else { rt = fabsf(x0); sd = x0 > 0.0f ? 1 : 0; bad = false; }                                          // (y == 0: t = -tau <= 0)
     const float t = rt - c.tau;
     bad = bad || !(t > 0.0f);
@@ -210,8 +246,9 @@ __device__ __forceinline__ void wiener_grad_finish(const float *p, float valid, 
     else { out_grad[4] = de * nan; out_grad[5] = dsc * nan; }
 }
 
-// STAGED: the workgroup's rows all score one data set, read from LDS (broadcast layout); else every row reads its own (paired layout)
-template <int MODEL, bool STAGED>
+// STAGED: the workgroup's rows all score one data set, read from LDS (broadcast layout); else every row reads its own (paired layout).
+// CENSORED: wiener_grad_trial's switch (NDDM_WIENER_CENSORED); the instantiations without it are the kernels as they were.
+template <int MODEL, bool STAGED, bool CENSORED = false>
 __global__ __launch_bounds__(256) void wiener_grad_kernel(WienerGradArgs G)
 {
     __shared__ float2 tile[STAGED ? WIENER_TILE : 1];
@@ -249,7 +286,7 @@ __global__ __launch_bounds__(256) void wiener_grad_kernel(WienerGradArgs G)
                 x0 = n0; x1 = n1;
                 if (i + 64 < nt) { n0 = src[2 * (i + 64)]; n1 = src[2 * (i + 64) + 1]; }
             }
-            wiener_grad_trial<MODEL>(c, g, x0, x1, s);
+            wiener_grad_trial<MODEL, CENSORED>(c, g, x0, x1, s);
         }
     }
     if (!w.has_row) return;

@@ -41,8 +41,13 @@
 // memory, no atomics; stores are plain vector stores.
 //
 // A chain is FLAGGED -- no iteration, NaN draws, flagged = 1, state unchanged, neighbours unaffected -- when its data set holds a
-// choice-0 trial (the censored gradient does not exist: nddm_wiener_grad.h), a non-finite value or a response time <= 0, or when its
-// incoming state is not finite.  All of it is found by reading values.
+// choice-0 trial (without NDDM_WIENER_CENSORED), a non-finite value or a response time <= 0, or when its incoming state is not finite.
+// All of it is found by reading values.
+//
+// NDDM_WIENER_CENSORED (the CENSORED template argument, from the kernel's body down to wiener_grad_trial): choice 0 is a trial, scored
+// right-censored by nddm_wiener_grad.h's censored instantiation in the same sweep, and T is the smallest rt of the RESPONSES (1.5 when the
+// data set has none).  The streams, the state, the bounds and the purity statement are unchanged; with no timeout in the data the bits
+// are the unflagged chain's.  wiener_hmc_kernel holds none of the survival code; wiener_hmc_censored_kernel is a kernel of its own.
 //
 // WHMC_HOST: the host build (tools/wiener_hmc_host.py) compiles everything but the kernel against a stand-in for <hip/hip_runtime.h>, the
 // 64 lanes as a loop and the butterfly in the same order.  WHMC_REAL: the type theta is cast to (float; the host tool's float64 build of
@@ -107,24 +112,29 @@ __device__ __forceinline__ void whmc_sigmoid(double x, double &sg, double &lsg, 
 }
 
 // One lane's sums over its trials lane, lane + 64, ... of the data set.  `tile`: the wave's staged trials, all N of them (one tile from 0).
+// CENSORED (NDDM_WIENER_CENSORED), here and below: wiener_grad_trial's switch -- a choice-0 trial adds the partials of log S.
+template <bool CENSORED = false>
 __device__ __forceinline__ WienerGradAcc whmc_lane_sums(const WienerRow &c, const WienerGradRow &g, const float2 *tile, int N, int lane)
 {
     WienerGradAcc s = wiener_grad_zero();
     wiener_tile_trials<true, false>(tile, nullptr, 1, N, 0, 0, N, lane,
-                                    [&](int, float x0, float x1) { wiener_grad_trial<NDDM_BASIC_DDM_DC>(c, g, x0, x1, s); });
+                                    [&](int, float x0, float x1) { wiener_grad_trial<NDDM_BASIC_DDM_DC, CENSORED>(c, g, x0, x1, s); });
     return s;
 }
 
 // The row's six sums over the data set's N trials, every lane's copy alike
 #ifndef WHMC_HOST
+template <bool CENSORED = false>
 __device__ __forceinline__ WienerGradAcc whmc_sums(const WienerRow &c, const WienerGradRow &g, const float2 *tile, int N, int lane)
 {
-    WienerGradAcc s = whmc_lane_sums(c, g, tile, N, lane);
+    WienerGradAcc s = whmc_lane_sums<CENSORED>(c, g, tile, N, lane);
     wiener_grad_reduce<NDDM_BASIC_DDM_DC>(s);
     return s;
 }
 
-// Lane j stages trials j, j + 64, ... (the ones it reads back) and the wave reduces what it saw
+// Lane j stages trials j, j + 64, ... (the ones it reads back) and the wave reduces what it saw.  CENSORED: choice 0 is a trial like the
+// others, and T is the smallest rt OF THE RESPONSES (a timeout's rt bounds nothing: tau beyond it leaves log S = 0); no response, T = 1.5.
+template <bool CENSORED = false>
 __device__ __forceinline__ WhmcData whmc_stage(float2 *tile, const float *src, int N, int lane)
 {
     float mn = __builtin_inff();
@@ -132,8 +142,8 @@ __device__ __forceinline__ WhmcData whmc_stage(float2 *tile, const float *src, i
     for (int i = lane; i < N; i += 64) {
         const float rt = src[2 * i], ch = src[2 * i + 1];
         tile[i] = make_float2(rt, ch);
-        bad = bad || !(rt > 0.0f) || !(rt < __builtin_inff()) || !(ch == 1.0f || ch == -1.0f);
-        mn = fminf(mn, rt);
+        bad = bad || !(rt > 0.0f) || !(rt < __builtin_inff()) || !(ch == 1.0f || ch == -1.0f || (CENSORED && ch == 0.0f));
+        mn = fminf(mn, CENSORED && ch == 0.0f ? __builtin_inff() : rt);
     }
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) mn = fminf(mn, __shfl_xor(mn, m, 64));
@@ -143,11 +153,12 @@ __device__ __forceinline__ WhmcData whmc_stage(float2 *tile, const float *src, i
     return d;
 }
 #else
+template <bool CENSORED = false>
 inline WienerGradAcc whmc_sums(const WienerRow &c, const WienerGradRow &g, const float2 *tile, int N, int)
 {
     WienerGradAcc L[64];
     for (int lane = 0; lane < 64; ++lane) {
-        L[lane] = whmc_lane_sums(c, g, tile, N, lane);
+        L[lane] = whmc_lane_sums<CENSORED>(c, g, tile, N, lane);
         wiener_grad_fold<NDDM_BASIC_DDM_DC>(L[lane]);
     }
     for (int m = 1; m < 64; m <<= 1)                                    // lane 0's side of the butterfly: the pairwise tree in lane order
@@ -157,6 +168,7 @@ inline WienerGradAcc whmc_sums(const WienerRow &c, const WienerGradRow &g, const
     return L[0];
 }
 
+template <bool CENSORED = false>
 inline WhmcData whmc_stage(float2 *tile, const float *src, int N, int)
 {
     float mn = __builtin_inff();
@@ -164,8 +176,8 @@ inline WhmcData whmc_stage(float2 *tile, const float *src, int N, int)
     for (int i = 0; i < N; ++i) {
         const float rt = src[2 * i], ch = src[2 * i + 1];
         tile[i] = make_float2(rt, ch);
-        bad = bad || !(rt > 0.0f) || !(rt < __builtin_inff()) || !(ch == 1.0f || ch == -1.0f);
-        mn = fminf(mn, rt);
+        bad = bad || !(rt > 0.0f) || !(rt < __builtin_inff()) || !(ch == 1.0f || ch == -1.0f || (CENSORED && ch == 0.0f));
+        mn = fminf(mn, CENSORED && ch == 0.0f ? __builtin_inff() : rt);
     }
     WhmcData d;
     d.bad = bad;
@@ -184,7 +196,7 @@ struct WhmcExt {
 };
 
 // log posterior (up to a constant) and its gradient at q, in the unconstrained coordinates; theta: the point in the model's columns
-template <class Ext = WhmcNoExt>
+template <class Ext = WhmcNoExt, bool CENSORED = false>
 __device__ __forceinline__ double whmc_log_post(const double (&q)[5], unsigned mask, double T, const float2 *tile, int N, int lane,
                                                 double (&dq)[5], double (&theta)[5], const Ext &ext = Ext())
 {
@@ -206,7 +218,7 @@ __device__ __forceinline__ double whmc_log_post(const double (&q)[5], unsigned m
     for (int j = 0; j < 5; ++j) p[j] = (whmc_real)theta[j];
     const WienerRow c = wiener_row<NDDM_BASIC_DDM_DC>(p);
     const WienerGradRow g = wiener_grad_row<NDDM_BASIC_DDM_DC>(p, c);
-    const WienerGradAcc s = whmc_sums(c, g, tile, N, lane);
+    const WienerGradAcc s = whmc_sums<CENSORED>(c, g, tile, N, lane);
     double ll, gl[5];
     wiener_grad_finish<NDDM_BASIC_DDM_DC>(p, c.valid, s, &ll, gl);
     // the priors and their derivatives in theta
@@ -252,7 +264,7 @@ struct WhmcTally {
 
 // One chain through iterations [iter_offset, iter_offset + n_iter): st is its state (updated), im its inverse mass; kept draws go to
 // draws / log_post (either may be NULL) through `keep` (lane 0 on the device).  The data set is staged in `tile`.  `ext`: see WhmcNoExt.
-template <class Ext = WhmcNoExt>
+template <class Ext = WhmcNoExt, bool CENSORED = false>
 __device__ __forceinline__ WhmcTally whmc_chain(double *st, const double (&im)[5], const float2 *tile, int N, double T, unsigned mask,
                                                 unsigned k0, unsigned k1, unsigned chain, unsigned long long iter_offset, int n_iter,
                                                 int n_adapt, int n_leapfrog, int thin, float *draws, float *log_post, int lane, bool keep,
@@ -264,7 +276,7 @@ __device__ __forceinline__ WhmcTally whmc_chain(double *st, const double (&im)[5
     double leps = st[5], lbar = st[6], hbar = st[7];
     const double mu = st[8];
     double adapted = st[9], elast = st[10], emax = st[11];
-    double lp = whmc_log_post(q, mask, T, tile, N, lane, g, th, ext);
+    double lp = whmc_log_post<Ext, CENSORED>(q, mask, T, tile, N, lane, g, th, ext);
     WhmcTally tally = {0.0, 0, 0};
     long long kept = 0;
     for (int it = 0; it < n_iter; ++it) {
@@ -287,7 +299,7 @@ __device__ __forceinline__ WhmcTally whmc_chain(double *st, const double (&im)[5
                 p[j] += 0.5 * eps * gn[j];
                 qn[j] += eps * im[j] * p[j];
             }
-            lpn = whmc_log_post(qn, mask, T, tile, N, lane, gn, thn, ext);
+            lpn = whmc_log_post<Ext, CENSORED>(qn, mask, T, tile, N, lane, gn, thn, ext);
 #pragma unroll
             for (int j = 0; j < 5; ++j) p[j] += 0.5 * eps * gn[j];
         }
@@ -347,14 +359,16 @@ __device__ __forceinline__ bool whmc_state_ok(const double *st, const double (&i
 }
 
 #ifndef WHMC_HOST
-__global__ __launch_bounds__(256) void wiener_hmc_kernel(WienerHmcArgs A)
+// The kernel's body (the workgroup's 4 x WHMC_MAX_TRIALS pairs of LDS are declared in it: each kernel gets its own)
+template <bool CENSORED>
+__device__ __forceinline__ void wiener_hmc_body(const WienerHmcArgs &A)
 {
     __shared__ float2 tiles[4 * WHMC_MAX_TRIALS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long c = (long long)blockIdx.x * 4 + wave;
     if (c >= A.C) return;                                               // wave-uniform; no barrier follows
     float2 *tile = tiles + wave * WHMC_MAX_TRIALS;
-    const WhmcData dat = whmc_stage(tile, A.data + (c / A.S) * (long long)A.N * 2, A.N, lane);
+    const WhmcData dat = whmc_stage<CENSORED>(tile, A.data + (c / A.S) * (long long)A.N * 2, A.N, lane);
     double st[WHMC_STATE], im[5];
 #pragma unroll
     for (int j = 0; j < WHMC_STATE; ++j) st[j] = A.state[c * WHMC_STATE + j];
@@ -373,8 +387,9 @@ __global__ __launch_bounds__(256) void wiener_hmc_kernel(WienerHmcArgs A)
         }
         return;
     }
-    const WhmcTally t = whmc_chain(st, im, tile, A.N, dat.T, A.free_mask, A.k0, A.k1, (unsigned)(A.chain_offset + (unsigned long long)c),
-                                   A.iter_offset, A.n_iter, A.n_adapt, A.n_leapfrog, A.thin, draws, log_post, lane, lane == 0);
+    const WhmcTally t = whmc_chain<WhmcNoExt, CENSORED>(st, im, tile, A.N, dat.T, A.free_mask, A.k0, A.k1,
+                                                        (unsigned)(A.chain_offset + (unsigned long long)c), A.iter_offset, A.n_iter, A.n_adapt,
+                                                        A.n_leapfrog, A.thin, draws, log_post, lane, lane == 0);
     if (lane == 0) {
 #pragma unroll
         for (int j = 0; j < WHMC_STATE; ++j) A.state[c * WHMC_STATE + j] = st[j];
@@ -382,6 +397,17 @@ __global__ __launch_bounds__(256) void wiener_hmc_kernel(WienerHmcArgs A)
         if (A.out_divergent) A.out_divergent[c] = t.n_divergent;
         if (A.out_flagged) A.out_flagged[c] = 0;
     }
+}
+
+__global__ __launch_bounds__(256) void wiener_hmc_kernel(WienerHmcArgs A)
+{
+    wiener_hmc_body<false>(A);
+}
+
+// NDDM_WIENER_CENSORED: the same chain with timeouts scored (a kernel of its own: wiener_hmc_kernel holds none of the survival code)
+__global__ __launch_bounds__(256) void wiener_hmc_censored_kernel(WienerHmcArgs A)
+{
+    wiener_hmc_body<true>(A);
 }
 #endif
 

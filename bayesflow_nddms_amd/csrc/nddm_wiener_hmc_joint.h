@@ -70,6 +70,7 @@ struct WienerHmcJointArgs {
     int N, n_iter, n_adapt, n_leapfrog, thin;
     int sigma_fixed;
     int it;                     // the launch's iteration of the call, 0 .. n_iter - 1
+    int censored;               // NDDM_WIENER_CENSORED: what the pre-pass takes for a trial (the participant kernel is the censored one)
 };
 
 // f(lane) summed over the 64 lanes in the butterfly's order (every lane's copy alike on the device; lane 0's side of the tree on the host)
@@ -148,14 +149,15 @@ __device__ __forceinline__ bool whmcj_sigma_step(double &sigma, double SS, long 
 }
 
 // PART 1: iteration gi of participant chain `chain` given sigma: one iteration of nddm_wiener_hmc.h's chain with the ext term.  draws /
-// log_post: where THIS iteration's kept draw goes (read only when (gi + 1) % thin == 0).
+// log_post: where THIS iteration's kept draw goes (read only when (gi + 1) % thin == 0).  CENSORED: nddm_wiener_hmc.h's switch, passed through.
+template <bool CENSORED = false>
 __device__ __forceinline__ WhmcTally whmcj_participant(double *st, const double (&im)[5], const float2 *tile, int N, double T, unsigned mask,
                                                        unsigned k0, unsigned k1, unsigned chain, unsigned long long gi, int n_adapt,
                                                        int n_leapfrog, int thin, float *draws, float *log_post, int lane, bool keep,
                                                        double ext, double sigma)
 {
     const WhmcExt e = {ext, 1.0 / (sigma * sigma)};
-    return whmc_chain<WhmcExt>(st, im, tile, N, T, mask, k0, k1, chain, gi, 1, n_adapt, n_leapfrog, thin, draws, log_post, lane, keep, e);
+    return whmc_chain<WhmcExt, CENSORED>(st, im, tile, N, T, mask, k0, k1, chain, gi, 1, n_adapt, n_leapfrog, thin, draws, log_post, lane, keep, e);
 }
 
 // the sigma a joint chain can run from
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(256) void wiener_hmc_joint_prepass_kernel(WienerHmc
         const float *src = A.data + p * (long long)A.N * 2;
         for (int i = lane; i < A.N; i += 64) {
             const float rt = src[2 * i], ch = src[2 * i + 1];
-            bad = bad || !(rt > 0.0f) || !(rt < __builtin_inff()) || !(ch == 1.0f || ch == -1.0f);
+            bad = bad || !(rt > 0.0f) || !(rt < __builtin_inff()) || !(ch == 1.0f || ch == -1.0f || (A.censored && ch == 0.0f));
         }
     }
     bad = __any(bad) != 0;
@@ -228,8 +230,10 @@ __global__ __launch_bounds__(256) void wiener_hmc_joint_prepass_kernel(WienerHmc
     }
 }
 
-// PART 1 of iteration A.it: 256 threads = 4 waves = 4 participant chains per workgroup, as wiener_hmc_kernel
-__global__ __launch_bounds__(256) void wiener_hmc_joint_kernel(WienerHmcJointArgs A)
+// PART 1 of iteration A.it: 256 threads = 4 waves = 4 participant chains per workgroup, as wiener_hmc_kernel.  The body (the
+// workgroup's LDS is declared in it: each kernel gets its own)
+template <bool CENSORED>
+__device__ __forceinline__ void wiener_hmc_joint_body(const WienerHmcJointArgs &A)
 {
     __shared__ float2 tiles[4 * WHMC_MAX_TRIALS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -238,7 +242,7 @@ __global__ __launch_bounds__(256) void wiener_hmc_joint_kernel(WienerHmcJointArg
     const long long p = c / A.S, k = c % A.S;
     if (A.ws[(C + k) * WHMCJ_WS + 2] != 0.0) return;                    // a flagged joint chain runs no iteration
     float2 *tile = tiles + wave * WHMC_MAX_TRIALS;
-    const WhmcData dat = whmc_stage(tile, A.data + p * (long long)A.N * 2, A.N, lane);
+    const WhmcData dat = whmc_stage<CENSORED>(tile, A.data + p * (long long)A.N * 2, A.N, lane);
     double st[WHMC_STATE], im[5];
 #pragma unroll
     for (int j = 0; j < WHMC_STATE; ++j) st[j] = A.state[c * WHMC_STATE + j];
@@ -249,7 +253,7 @@ __global__ __launch_bounds__(256) void wiener_hmc_joint_kernel(WienerHmcJointArg
     const long long slot = kept ? whmcj_slot(gi, A.iter_offset, A.thin) : 0;
     float *draws = kept && A.out_draws ? A.out_draws + (c * A.K + slot) * 5 : nullptr;
     float *log_post = kept && A.out_log_post ? A.out_log_post + c * A.K + slot : nullptr;
-    const WhmcTally t = whmcj_participant(st, im, tile, A.N, dat.T, A.free_mask, A.k0, A.k1, (unsigned)(A.chain_offset + (unsigned long long)c), gi,
+    const WhmcTally t = whmcj_participant<CENSORED>(st, im, tile, A.N, dat.T, A.free_mask, A.k0, A.k1, (unsigned)(A.chain_offset + (unsigned long long)c), gi,
                                           A.n_adapt, A.n_leapfrog, A.thin, draws, log_post, lane, lane == 0, A.ext[p], A.sigma[k]);
     if (lane == 0) {
 #pragma unroll
@@ -262,6 +266,17 @@ __global__ __launch_bounds__(256) void wiener_hmc_joint_kernel(WienerHmcJointArg
             if (A.out_divergent) A.out_divergent[c] = (int)nd;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void wiener_hmc_joint_kernel(WienerHmcJointArgs A)
+{
+    wiener_hmc_joint_body<false>(A);
+}
+
+// NDDM_WIENER_CENSORED's participant kernel (a kernel of its own: wiener_hmc_joint_kernel holds none of the survival code)
+__global__ __launch_bounds__(256) void wiener_hmc_censored_joint_kernel(WienerHmcJointArgs A)
+{
+    wiener_hmc_joint_body<true>(A);
 }
 
 // PART 2 of iteration A.it: one wave per joint chain

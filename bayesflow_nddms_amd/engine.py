@@ -458,10 +458,10 @@ def wiener_hmc_max_iter(n_trials, n_leapfrog):
 
 
 def _hmc_host_checks(model, data, sets, n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset, max_iter_of, bound,
-                     chains_per_dataset=None):
+                     chains_per_dataset=None, censored=False):
     """The front end wiener_hmc and wiener_hmc_joint share, up to the launch bound: host inputs are refused here (ValueError), before any
     device work.  sets: the letter of data's first axis; max_iter_of / bound: the sampler's launch bound and its sentence ({m}: the bound,
-    {N}, {L}); chains_per_dataset: wiener_hmc's.  -> (the counts, mask and offsets as ints, data's row description, its host array or None,
+    {N}, {L}); chains_per_dataset: wiener_hmc's; censored: timeouts (choice 0) are trials.  -> (the counts, mask and offsets as ints, data's row description, its host array or None,
     the number of data sets, n_trials)."""
     if model != BASIC_DDM_DC:
         raise ValueError(f"model {model} has no sampler here (BASIC_DDM_DC only)")
@@ -480,7 +480,9 @@ def _hmc_host_checks(model, data, sets, n_iter, n_adapt, n_leapfrog, thin, free_
     if d_np is not None:
         if not np.all(np.isfinite(d_np)):
             raise ValueError("data must be finite")
-        if not np.all(np.isin(d_np[..., 1], (-1.0, 1.0))):
+        if censored and not np.all(np.isin(d_np[..., 1], (-1.0, 0.0, 1.0))):
+            raise ValueError("with censored=True the sampler takes (rt, choice) with choice in {1, -1, 0}")
+        if not censored and not np.all(np.isin(d_np[..., 1], (-1.0, 1.0))):
             raise ValueError("the sampler takes (rt, choice) with choice in {1, -1}: a timeout (choice 0) has no gradient here")
         if np.any(d_np[..., 0] <= 0):
             raise ValueError("response times must be > 0")
@@ -545,7 +547,7 @@ def _hmc_device_call(data, d_rows, d_np, f64, C, K, want_draws, want_log_post, o
 
 
 def wiener_hmc(model, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1, n_adapt=0, n_leapfrog=16, thin=1, free_mask=31, seed=0,
-               chain_offset=0, iter_offset=0, want_draws=True, want_log_post=True, device=None):
+               chain_offset=0, iter_offset=0, want_draws=True, want_log_post=True, device=None, censored=False):
     """Batched Hamiltonian Monte Carlo over the basic_ddm_dc Wiener posterior, one wave per chain, all n_iter iterations in ONE launch
     (include/nddm.h: nddm_wiener_hmc; the chain: csrc/nddm_wiener_hmc.h).
 
@@ -555,18 +557,21 @@ def wiener_hmc(model, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1
     cuts a long run into such launches.  Returns a dict of device tensors: 'draws' float32 [C, K, 5] in the model's columns, 'log_post'
     float32 [C, K], 'accept' float32 [C], 'divergent' int32 [C], 'flagged' int32 [C] and 'state' float64 [C, 12]; K = (iter_offset +
     n_iter) // thin - iter_offset // thin.  Host inputs are shape- and range-checked (ValueError); a data set that cannot be sampled (a
-    timeout, a non-finite value, an rt <= 0) that arrives on the device flags its chains instead."""
+    timeout, a non-finite value, an rt <= 0) that arrives on the device flags its chains instead.
+    censored=True (NDDM_WIENER_CENSORED): timeouts (choice 0) are scored right-censored, log P(T > rt - tau), in the posterior and its
+    gradient; tau's upper limit is min(1.5, the smallest rt of the RESPONSES).  With no timeout in the data the chains' bits are the default's."""
     (n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset), d_rows, d_np, D, N = _hmc_host_checks(
         model, data, "D", n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset, wiener_hmc_max_iter,
         "one launch runs at most {m} iterations at n_trials {N} and n_leapfrog {L} (n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19): cut the "
-        "run (mcmc.hmc_fit does)", chains_per_dataset=chains_per_dataset)
+        "run (mcmc.hmc_fit does)", chains_per_dataset=chains_per_dataset, censored=censored)
+    flags = _lib.WIENER_CENSORED if censored else 0
     S, K = int(chains_per_dataset), (iter_offset + n_iter) // thin - iter_offset // thin
     C = D * S
     f64 = _hmc_chain_checks(C, chain_offset, state, inv_mass, f" (D {D} x chains_per_dataset {S})")
     res, ins = _hmc_device_call(
         data, d_rows, d_np, f64, C, K, want_draws, want_log_post, [], device,
         lambda L, d, i, o, st: _lib.check(L.nddm_wiener_hmc(int(model), d, D, N, C, S, i["state"], i["inv_mass"], n_iter, n_adapt, n_leapfrog, thin,
-                                                            free_mask, _u64(seed), chain_offset, iter_offset, 0, o["draws"], o["log_post"],
+                                                            free_mask, _u64(seed), chain_offset, iter_offset, flags, o["draws"], o["log_post"],
                                                             o["accept"], o["divergent"], o["flagged"], st)))
     res["state"] = ins["state"]
     return res
@@ -581,7 +586,7 @@ def wiener_hmc_joint_max_iter(n_trials, n_leapfrog):
 
 
 def wiener_hmc_joint(model, data, extdata, state, sigma, inv_mass=None, n_iter=1, n_adapt=0, n_leapfrog=16, thin=1, free_mask=31, seed=0,
-                     chain_offset=0, iter_offset=0, sigma_fixed=False, want_draws=True, want_log_post=True, device=None):
+                     chain_offset=0, iter_offset=0, sigma_fixed=False, want_draws=True, want_log_post=True, device=None, censored=False):
     """The alpha_not_scaled JAGS fit's sampler: wiener_hmc's chains coupled by one shared sigma, Metropolis within Gibbs (include/nddm.h:
     nddm_wiener_hmc_joint; csrc/nddm_wiener_hmc_joint.h).  Per joint iteration one participant launch and one sigma launch are enqueued on
     the current stream; nothing waits on the host.
@@ -592,11 +597,13 @@ def wiener_hmc_joint(model, data, extdata, state, sigma, inv_mass=None, n_iter=1
     n_iter <= wiener_hmc_joint_max_iter(n_trials, n_leapfrog).  Returns wiener_hmc's dict -- 'log_post' is the participant's conditional
     log posterior given sigma, the ext term included -- plus 'sigma_draws' float32 [S, K], 'sigma_accept' float32 [S] (the share of the
     call's sigma proposals accepted; NaN with sigma_fixed) and 'sigma' float64 [S].  Host inputs are shape- and range-checked (ValueError);
-    on the device a data set that cannot be sampled flags every chain, a bad state or sigma its joint chain."""
+    on the device a data set that cannot be sampled flags every chain, a bad state or sigma its joint chain.  censored=True: wiener_hmc's,
+    passed through to the participants' chains."""
     (n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset), d_rows, d_np, P, N = _hmc_host_checks(
         model, data, "P", n_iter, n_adapt, n_leapfrog, thin, free_mask, chain_offset, iter_offset, wiener_hmc_joint_max_iter,
         "one call runs at most {m} joint iterations at n_trials {N} and n_leapfrog {L} (n_iter <= 4096 and n_iter * n_leapfrog * ceil(n_trials / "
-        "64) <= 2^19): cut the run (mcmc.hmc_fit_joint does)")
+        "64) <= 2^19): cut the run (mcmc.hmc_fit_joint does)", censored=censored)
+    flags = (_lib.HMC_SIGMA_FIXED if sigma_fixed else 0) | (_lib.WIENER_CENSORED if censored else 0)
     if not sigma_fixed and P < 2:
         raise ValueError("sampling sigma needs at least 2 participants")
     g_shape = tuple(sigma.shape) if hasattr(sigma, "shape") else np.shape(sigma)
@@ -619,7 +626,7 @@ def wiener_hmc_joint(model, data, extdata, state, sigma, inv_mass=None, n_iter=1
         [("sigma_draws", (S, K), "float32"), ("sigma_accept", (S,), "float32"), ("workspace", (C + S, 4), "float64")], device,
         lambda L, d, i, o, st: _lib.check(L.nddm_wiener_hmc_joint(
             int(model), d, P, N, C, S, i["extdata"], i["state"], i["inv_mass"], i["sigma"], o["workspace"], n_iter, n_adapt, n_leapfrog, thin,
-            free_mask, _u64(seed), chain_offset, iter_offset, _lib.HMC_SIGMA_FIXED if sigma_fixed else 0, o["draws"], o["log_post"], o["accept"],
+            free_mask, _u64(seed), chain_offset, iter_offset, flags, o["draws"], o["log_post"], o["accept"],
             o["divergent"], o["flagged"], o["sigma_draws"], o["sigma_accept"], st)), always=True)
     del res["workspace"]
     res["state"], res["sigma"] = ins["state"], ins["sigma"]
@@ -635,21 +642,27 @@ def wiener_grad_launches():
     return _WIENER_GRAD_LAUNCHES[0]
 
 
-def wiener_log_likelihood_grad(model, params, data, draws_per_dataset=1, device=None):
+def wiener_log_likelihood_grad(model, params, data, draws_per_dataset=1, device=None, censored=False):
     """Log-likelihood of observed trials under the Wiener first-passage density AND its gradient in the parameter columns, one kernel
     launch (include/nddm.h: nddm_wiener_log_likelihood_grad): what a gradient-based fit consumes per step.  The arguments of
     wiener_log_likelihood.  Returns {'loglik': float64 [R], 'grad': float64 [R, P]} on the device; 'loglik' has the bits of
     wiener_log_likelihood's.  alpha_not_scaled's Nu is clipped to +-5: where the clip is active d/dNu is 0.
 
     An invalid row gives NaN in both; a trial at or below tau (-inf in the value) or an alpha_not_scaled y == 0 gives a NaN gradient.
-    NOT IMPLEMENTED: the gradient of basic_ddm_dc's censored timeouts (choice 0).  They are scored in 'loglik' exactly as
-    wiener_log_likelihood scores them, and the row's gradient is NaN in every column -- never a partial gradient.
+    basic_ddm_dc's censored timeouts (choice 0) are scored in 'loglik' exactly as wiener_log_likelihood scores them, either way.
+    censored=False (the default, every bit as it was) -- NOT IMPLEMENTED there: such a row's gradient is NaN in every column, never a
+    partial gradient.  censored=True (NDDM_WIENER_CENSORED, BASIC_DDM_DC only: ValueError otherwise): a timeout adds the gradient of
+    log P(T > rt - tau) and the row's gradient is finite; a timeout with rt <= tau adds zero; a non-finite rt or a choice other than
+    1, -1, 0 gives a NaN gradient.  With no timeout in the data the two give the same bits.
     Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are."""
     checked = _wiener_host_checks(model, params, data, draws_per_dataset, "likelihood", {"grad": True})
+    if censored and model != BASIC_DDM_DC:
+        raise ValueError("censored=True takes BASIC_DDM_DC only (alpha_not_scaled's y == 0 carries no time)")
     S, R = checked[0], checked[-1]
+    flags = _lib.WIENER_CENSORED if censored else 0
 
     def call(L, p, d, N, o, st):
-        _lib.check(L.nddm_wiener_log_likelihood_grad(int(model), p, R, S, d, N, 0, o["loglik"], o["grad"], st))
+        _lib.check(L.nddm_wiener_log_likelihood_grad(int(model), p, R, S, d, N, flags, o["loglik"], o["grad"], st))
         _WIENER_GRAD_LAUNCHES[0] += 1
 
     return _wiener_device_call(checked, params, data, device,

@@ -174,9 +174,10 @@ def _wiener_loglik_function():
 
         class WienerLoglik(torch.autograd.Function):
             @staticmethod
-            def forward(ctx, params, data, model, draws_per_dataset, device):
+            def forward(ctx, params, data, model, draws_per_dataset, device, censored):
+                kw = {"censored": True} if censored else {}             # (the default makes the engine call it always made)
                 r = engine.wiener_log_likelihood_grad(model, params.detach(), data.detach() if hasattr(data, "detach") else data,
-                                                      draws_per_dataset=draws_per_dataset, device=device)
+                                                      draws_per_dataset=draws_per_dataset, device=device, **kw)
                 ctx.save_for_backward(r["grad"])
                 ctx.params_shape, ctx.params_dtype, ctx.params_device = params.shape, params.dtype, params.device
                 return r["loglik"]
@@ -185,26 +186,27 @@ def _wiener_loglik_function():
             def backward(ctx, grad_output):
                 (grad,) = ctx.saved_tensors                             # the forward's launch computed it: nothing is launched here
                 g = (grad_output.to(grad.dtype)[:, None] * grad).reshape(ctx.params_shape)
-                return g.to(device=ctx.params_device, dtype=ctx.params_dtype), None, None, None, None
+                return g.to(device=ctx.params_device, dtype=ctx.params_dtype), None, None, None, None, None
 
         _WienerLoglik = WienerLoglik
     return _WienerLoglik
 
 
-def wiener_loglik(model, params, data, draws_per_dataset=1, device=None):
+def wiener_loglik(model, params, data, draws_per_dataset=1, device=None, censored=False):
     """A row's log-likelihood under the Wiener first-passage density, float64 [R] on the device, DIFFERENTIABLE with respect to `params`
     (a torch tensor; [R, P] in the model's column order): the arguments of engine.wiener_log_likelihood_grad, whose ONE launch the forward
     makes; it keeps the gradient, and the backward is grad_output[:, None] * grad cast to params' dtype -- no second launch.  `data` gets no
     gradient.  With nothing requiring grad the values are the same.
 
-        loss = -likelihood.wiener_loglik(engine.BASIC_DDM_DC, theta, data).sum(); loss.backward()
+        loss = -likelihood.wiener_loglik(engine.BASIC_DDM_DC, theta, data, censored=True).sum(); loss.backward()
 
-    alpha_not_scaled's Nu is clipped to +-5 (zero gradient where the clip is active).  NOT IMPLEMENTED: the gradient of basic_ddm_dc's
-    censored timeouts (choice 0) -- such a row's value is right and its gradient is NaN in every column, never a partial one."""
+    alpha_not_scaled's Nu is clipped to +-5 (zero gradient where the clip is active).  basic_ddm_dc's censored timeouts (choice 0): with
+    censored=True (BASIC_DDM_DC only) the value is differentiable through rows that hold them, still in the one launch.  With the default
+    that is NOT IMPLEMENTED -- such a row's value is right and its gradient is NaN in every column, never a partial one."""
     torch = engine._torch()                                             # (the engine call refuses bad host input before it asks for a device)
     if not isinstance(params, torch.Tensor):
         params = torch.as_tensor(np.asarray(params, dtype=np.float64))
-    return _wiener_loglik_function().apply(params, data, model, int(draws_per_dataset), device)
+    return _wiener_loglik_function().apply(params, data, model, int(draws_per_dataset), device, bool(censored))
 
 
 _SingleTrialLoglik = None

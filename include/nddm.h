@@ -75,6 +75,8 @@ extern "C" {
 /* 4 (additive): nddm_wiener_marginal_log_likelihood_grad.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_hmc.  No existing entry point changes. */
 /* 4 (additive): nddm_wiener_hmc_joint.  No existing entry point changes. */
+/* 4 (additive): NDDM_WIENER_CENSORED (flag 4 of nddm_wiener_log_likelihood_grad, nddm_wiener_hmc and nddm_wiener_hmc_joint).  With the
+ *    flag clear no output changes. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -285,22 +287,31 @@ int nddm_wiener_log_likelihood(int32_t model, const float *params, int64_t R, in
 /* The same log-likelihood AND its gradient in the model's parameter columns, one fused launch: what a gradient-based fit consumes per
  * step (Stan's NUTS over wiener_lpdf, MAP refinement, Laplace / variational fits, HMC or MALA on many data sets at once).  (ABI 4, additive)
  *   model, params, draws_per_dataset, data, n_trials: exactly as nddm_wiener_log_likelihood takes them
- *   flags              must be 0 (reserved): NDDM_ERR_PARAM otherwise
+ *   flags              0 or NDDM_WIENER_CENSORED (basic_ddm_dc only: with NDDM_ALPHA_NOT_SCALED, whose y == 0 carries no time, it is
+ *                      NDDM_ERR_PARAM); any other value: NDDM_ERR_PARAM
  *   out_loglik         device f64 [R] or NULL: the row's log-likelihood, BIT FOR BIT nddm_wiener_log_likelihood's out_loglik
  *   out_grad           device f64 [R, P] (NULL: NDDM_ERR_NULL): d out_loglik[r] / d params[r, j], in params' column order; alpha_not_scaled's Nu
  *                      is clipped to +-5: where the clip is active the Nu column is 0 and the others are those of the clipped value
  * Special values (none an error): an invalid row (nddm_wiener_log_likelihood's conditions) gives NaN in out_loglik and in every gradient
  * column, the other rows unaffected; a trial with rt <= tau (-inf in the value) or an alpha_not_scaled y == 0 (NaN in the value) gives NaN
  * in every gradient column of its row.
- * NOT IMPLEMENTED: the gradient of basic_ddm_dc's censored timeouts (choice 0).  out_loglik scores them exactly as
- * nddm_wiener_log_likelihood does (log P(T > rt - tau)); the row's gradient is NaN in EVERY column, never a partial gradient.
+ * NOT IMPLEMENTED: the gradient of basic_ddm_dc's censored timeouts (choice 0) under flags 0.  out_loglik scores them exactly as
+ * nddm_wiener_log_likelihood does (log P(T > rt - tau)), whatever the flags; with flags 0 the row's gradient is NaN in EVERY column,
+ * never a partial gradient.  IMPLEMENTED, opt-in, under NDDM_WIENER_CENSORED (the default keeps every bit it had): there a
+ * timeout adds the gradient of log P(T > rt - tau) -- in tau it is +(f_lower + f_upper) / S -- and the row's gradient is finite; a timeout
+ * with rt <= tau is log 1 = 0 with a zero gradient; a non-finite rt, or a choice other than 1, -1 and 0, gives NaN in every gradient
+ * column of its row.  Where no trial is a timeout the flag changes no bit of either output.
  * The bits of both outputs are a function of (the row's parameters, its data set, n_trials) alone: the same whatever the layout, the
  * draws_per_dataset factorisation, the stream or a capture.  No scratch memory, no atomics: a call made while `stream` is capturing is one
  * kernel node.  Error checks, their order and their status codes are nddm_wiener_log_likelihood's; R = 0 is NDDM_OK.  The math:
  * csrc/nddm_wiener_grad.h, DESIGN.md section 14. */
 int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
-                                    int32_t n_trials, uint32_t flags /* 0, reserved */, double *out_loglik /* [R] or NULL */,
+                                    int32_t n_trials, uint32_t flags /* 0 or NDDM_WIENER_CENSORED */, double *out_loglik /* [R] or NULL */,
                                     double *out_grad /* [R, P] */, void *stream);
+
+/* nddm_wiener_log_likelihood_grad, nddm_wiener_hmc, nddm_wiener_hmc_joint: score basic_ddm_dc's censored timeouts in the gradient and
+ * in the samplers' posterior.  (4: the one value free in the flags of all three, whose 1, 2 and 3 are taken or refused by name.) */
+#define NDDM_WIENER_CENSORED 4u
 
 /* Batched Hamiltonian Monte Carlo over the basic_ddm_dc posterior of the reference's JAGS fit (basic_ddm_dc_pyjags.py:103-137), one wave per
  * chain, all the iterations of the call in one launch.  (ABI 4, additive)
@@ -318,14 +329,17 @@ int nddm_wiener_log_likelihood_grad(int32_t model, const float *params, int64_t 
  *                      chain's output is a pure function of (seed, global chain index, its data set, its incoming state, inv_mass,
  *                      free_mask, n_leapfrog, thin, n_adapt, the iteration range): a run continued from a returned state with iter_offset
  *                      advanced gives the bits of the uncut run, whatever else is in the launch
- *   flags              must be 0 (reserved)
+ *   flags              0 or NDDM_WIENER_CENSORED: a choice-0 trial (the simulator's timeout) is a trial, scored right-censored as
+ *                      log P(T > rt - tau) in the posterior and its gradient; tau's upper limit is then min(1.5, the smallest rt of the
+ *                      RESPONSES) (1.5 without one).  With no choice-0 trial in the data the flag changes no bit.  Other values: NDDM_ERR_PARAM
  *   outputs, each may be NULL, not all: out_draws f32 [C, K, 5] in theta and out_log_post f32 [C, K] (the log posterior in q, Jacobian
  *                      included, up to an additive constant), K = (iter_offset + n_iter) / thin - iter_offset / thin, global iteration g
  *                      kept when (g + 1) % thin == 0; out_accept f32 [C]: the mean acceptance probability of this call's non-adapting
  *                      iterations (NaN: none); out_divergent i32 [C]: rejections with a non-finite or > 1000 energy error;
  *                      out_flagged i32 [C]
  * Priors: drift N(0, 2^2); boundary N(1, .5^2) on (0, 10); beta Beta(2, 2); tau N(.5, .25^2) on (0, min(1.5, smallest rt)); dc N(1, .5^2)
- * on (0.05, 10) -- the floor is a deviation from JAGS's (0, 10).  A chain whose data set holds a choice-0 trial, a non-finite value or an
+ * on (0.05, 10) -- the floor is a deviation from JAGS's (0, 10).  A chain whose data set holds a choice-0 trial (without
+ * NDDM_WIENER_CENSORED), any other choice than 1 and -1, a non-finite value or an
  * rt <= 0, or whose incoming state (or inverse mass) is not finite, is FLAGGED: no iteration, NaN draws, out_flagged = 1, state unchanged,
  * the other chains unaffected.  Error checks, their order and their status codes are nddm_wiener_log_likelihood's (a chain is a row); C = 0
  * is NDDM_OK.  No scratch memory, no atomics.  The chain: csrc/nddm_wiener_hmc.h, DESIGN.md section 17. */
@@ -345,7 +359,8 @@ int nddm_wiener_hmc(int32_t model, const float *data /* [D, n_trials, 2] */, int
  *   extdata            device f64 [P]
  *   sigma              device f64 [S], in and out
  *   workspace          device f64 [P * S + S, 4], the caller's: the call's accept and divergence accumulators.  The entry allocates nothing
- *   flags              0 or NDDM_HMC_SIGMA_FIXED: sigma is held and no sigma kernel is launched
+ *   flags              0 or NDDM_HMC_SIGMA_FIXED: sigma is held and no sigma kernel is launched; either with NDDM_WIENER_CENSORED
+ *                      (flags 4, 5), which nddm_wiener_hmc's chains take as that entry does; 2 and 3 are NDDM_ERR_PARAM
  *   n_iter             <= 4096 per call (and nddm_wiener_hmc's n_iter * n_leapfrog * ceil(n_trials / 64) <= 2^19); P >= 2 when sigma is
  *                      sampled (NDDM_ERR_SHAPE); a run cut into calls gives the bits of the uncut run
  *   outputs, each may be NULL, not all: nddm_wiener_hmc's five, out_sigma f32 [S, K] (sigma after both parts of a kept iteration) and

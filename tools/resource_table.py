@@ -34,9 +34,10 @@ def pretty(name):
     m = re.match(r"_ZN4nddm22wiener_quantile_kernelILi(\d)ELb(\d)E", name)
     if m:                                                     # the quantile function's kernel, the same two layouts
         return f"wiener_quantile_kernel<{MODELS[int(m.group(1))]}, {'broadcast' if m.group(2) == '1' else 'paired'}>"
-    m = re.match(r"_ZN4nddm18wiener_grad_kernelILi(\d)ELb(\d)E", name)
-    if m:                                                     # the value-and-gradient kernel, the same two layouts
-        return f"wiener_grad_kernel<{MODELS[int(m.group(1))]}, {'broadcast' if m.group(2) == '1' else 'paired'}>"
+    m = re.match(r"_ZN4nddm18wiener_grad_kernelILi(\d)ELb(\d)ELb(\d)E", name)
+    if m:                                                     # the value-and-gradient kernel, the same two layouts; censored: NDDM_WIENER_CENSORED's
+        return (f"wiener_grad_kernel<{MODELS[int(m.group(1))]}, {'broadcast' if m.group(2) == '1' else 'paired'}"
+                f"{', censored' if m.group(3) == '1' else ''}>")
     m = re.match(r"_ZN4nddm22wiener_marginal_kernelILb(\d)E", name)
     if m:                                                     # the single-trial model's marginal likelihood, the same two layouts
         return f"wiener_marginal_kernel<{'broadcast' if m.group(1) == '1' else 'paired'}>"

@@ -12,6 +12,7 @@ run(exe, td, data [D, N, 2], state [C, 12], ...) -> dict with the C entry point'
 Usage: python tools/wiener_hmc_host.py [--sanitize] [--json OUT]      prints one JSON line: the energy error of short trajectories at
 eps = 1e-3 (the bar of the energy tests = 4 x the largest), and float32 against float64 over 3 iterations of 4 leapfrog steps (the
 tolerance of the device-against-host test = 4 x the largest difference, and the share of chains whose accept decision is within it).
+With --censored: the same comparison for NDDM_WIENER_CENSORED's chain on data with 10 % timeouts, per case (censored_survey).
 """
 import math
 import os
@@ -94,7 +95,7 @@ int main(int argc, char **argv) {
     fclose(f);
     std::vector<float2> tile(N);
     for (long long c = 0; c < C; ++c) {
-        const WhmcData dat = whmc_stage(tile.data(), data.data() + (c / S) * N * 2, (int)N, 0);
+        const WhmcData dat = whmc_stage<HOST_CENSORED>(tile.data(), data.data() + (c / S) * N * 2, (int)N, 0);
         double st[WHMC_STATE], m[5];
         for (int j = 0; j < WHMC_STATE; ++j) st[j] = state[c * WHMC_STATE + j];
         for (int j = 0; j < 5; ++j) m[j] = im[c * 5 + j];
@@ -104,7 +105,7 @@ int main(int argc, char **argv) {
             acc[c] = __builtin_nanf(""); dv[c] = 0; fl[c] = 1;
             continue;
         }
-        const WhmcTally t = whmc_chain(st, m, tile.data(), (int)N, dat.T, mask, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)(coff + c), ioff,
+        const WhmcTally t = whmc_chain<WhmcNoExt, HOST_CENSORED>(st, m, tile.data(), (int)N, dat.T, mask, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)(coff + c), ioff,
                                        (int)n_iter, (int)n_adapt, (int)L, (int)thin, draws.data() + c * K * 5, lpost.data() + c * K, 0, true);
         for (int j = 0; j < WHMC_STATE; ++j) state[c * WHMC_STATE + j] = st[j];
         acc[c] = t.n_sampling ? (float)(t.accept_sum / (double)t.n_sampling) : __builtin_nanf("");
@@ -119,11 +120,12 @@ int main(int argc, char **argv) {
 """
 
 
-def build(td, sanitize=False, f64=False):
-    """Compile the stand-alone program into a directory of its own under td -> its path."""
-    sub = os.path.join(td, "f64" if f64 else "f32")
+def build(td, sanitize=False, f64=False, censored=False):
+    """Compile the stand-alone program into a directory of its own under td -> its path.  censored: NDDM_WIENER_CENSORED's chain."""
+    sub = os.path.join(td, ("f64" if f64 else "f32") + ("_censored" if censored else ""))
     os.makedirs(sub)
-    return B.build(sub, MAIN % (RNG_SHIM + (F64_ON if f64 else "")), "wiener_hmc_host", sanitize)
+    switch = "#define HOST_CENSORED %s\n" % ("true" if censored else "false")
+    return B.build(sub, MAIN % (switch + RNG_SHIM + (F64_ON if f64 else "")), "wiener_hmc_host", sanitize)
 
 
 def kept(iter_offset, n_iter, thin):
@@ -147,11 +149,23 @@ def run(exe, td, data, state, chains_per_dataset=1, inv_mass=None, n_iter=1, n_a
                        ("divergent", np.int32, (C,)), ("flagged", np.int32, (C,)), ("state", np.float64, (C, STATE))))
 
 
-def init_state(theta, data, chains_per_dataset=1, eps0=0.05, free=31):
+def init_state(theta, data, chains_per_dataset=1, eps0=0.05, free=31, censored=False):
     """theta [C, 5] in the model's columns -> the state [C, 12] a chain starts from (adaptation at its beginning)."""
     sys.path.insert(0, ROOT)
     from bayesflow_nddms_amd import mcmc
-    return mcmc.make_state(theta, np.repeat(np.asarray(data), chains_per_dataset, 0), eps0=eps0, free=free)
+    return mcmc.make_state(theta, np.repeat(np.asarray(data), chains_per_dataset, 0), eps0=eps0, free=free, censored=censored)
+
+
+def censor(data, share=0.1, seed=0, t_censor=1.2):
+    """A copy of `data` [D, N, 2] with about `share` of each data set's trials (one at least) turned into timeouts (choice 0) at
+    rt = t_censor + 0.3: the censored tests' data.  Which trials: the data set's slowest responses, as a horizon would take them."""
+    d = np.array(data, np.float32)
+    k = max(1, int(round(share * d.shape[1])))
+    for i in range(d.shape[0]):
+        idx = np.argsort(-d[i, :, 0], kind="stable")[:k]
+        d[i, idx, 0] = np.float32(t_censor + 0.3)
+        d[i, idx, 1] = 0.0
+    return d
 
 
 ENERGY_SHAPES = (1, 20, 64, 65, 130)      # one lane, a partial first round, a full round, a second round of one lane, a third round
@@ -247,5 +261,51 @@ def survey(sanitize=False):
     return out
 
 
+CENSORED_PROFILE = os.path.join(ROOT, "profiles", "r22_wiener_censored_hmc_host.json")
+
+
+def censored_case(N, C=256, D=4):
+    """case(N) with about 10 % of every data set's trials timeouts (censor) -> (data [D, N, 2], theta [C, 5])."""
+    data, theta = case(N, C=C, D=D)
+    return censor(data), theta
+
+
+def compare_q(a, b, theta0):
+    """compare() with the final q (the float64 the state holds) in the draws' place: the float32 draws of two close runs often agree to
+    the last bit, which would set a tolerance of zero."""
+    same, dl, _ = compare(a, b, theta0)
+    dq = float(np.max(np.abs(a["state"][same, :5] - b["state"][same, :5]))) if same.any() else 0.0
+    return same, dl, dq
+
+
+def censored_survey(sanitize=False):
+    """NDDM_WIENER_CENSORED's chain: float32 against float64 over 3 iterations of 4 leapfrog steps for every case of the device-against-host
+    test (its tolerance = 4 x that case's difference, on log_post and on the final q), and the energy error at eps = 1e-3.  --sanitize runs
+    one small case through a build under AddressSanitizer and UndefinedBehaviorSanitizer first (a stand-alone program)."""
+    out = {"tool": "tools/wiener_hmc_host.py --censored", "sanitized": bool(sanitize), "cases": {}, "device_tolerance": {}}
+    with tempfile.TemporaryDirectory() as td:
+        if sanitize:
+            data, theta = censored_case(65, C=8, D=4)
+            r = run(build(os.path.join(td, "san"), True, censored=True), td, data, init_state(theta, data, 2, censored=True), 2, n_iter=6, n_adapt=3,
+                    n_leapfrog=4, seed=3)
+            assert not r["flagged"].any() and np.all(np.isfinite(r["draws"]))
+        e32, e64 = build(td, censored=True), build(td, f64=True, censored=True)
+        for N in ENERGY_SHAPES:
+            data, theta = censored_case(N)
+            r = run(e32, td, data, init_state(theta, data, 64, eps0=1e-3, censored=True), 64, **ENERGY)
+            assert not r["flagged"].any()
+            st = init_state(theta, data, 64, eps0=0.02, censored=True)
+            a, b = run(e32, td, data, st, 64, **COMPARE), run(e64, td, data, st, 64, **COMPARE)
+            same, dl, dq = compare_q(a, b, theta)
+            out["cases"][f"N{N}"] = dict(COMPARE, chains=256, eps=0.02, timeouts_per_set=int((data[0, :, 1] == 0).sum()), left_out=int((~same).sum()),
+                                         max_rel_log_post=dl, max_abs_q=dq, max_abs_energy_error_at_eps_1em3=float(np.max(r["state"][:, 11])))
+            out["device_tolerance"][f"N{N}"] = {"log_post_rel": 4.0 * dl, "q_abs": 4.0 * dq}
+    return out
+
+
 if __name__ == "__main__":
-    B.cli(survey)
+    if "--censored" in sys.argv:
+        sys.argv.remove("--censored")
+        B.cli(censored_survey)
+    else:
+        B.cli(survey)

@@ -61,7 +61,7 @@ int main(int argc, char **argv) {
     std::vector<double> T(P);
     bool any_bad = false;
     for (long long p = 0; p < P; ++p) {
-        const WhmcData d = whmc_stage(tiles[p].data(), data.data() + p * N * 2, (int)N, 0);
+        const WhmcData d = whmc_stage<HOST_CENSORED>(tiles[p].data(), data.data() + p * N * 2, (int)N, 0);
         T[p] = d.T; any_bad = any_bad || d.bad;
     }
     for (long long k = 0; k < S; ++k) {
@@ -93,7 +93,7 @@ int main(int argc, char **argv) {
                 const long long c = p * S + k;
                 double m[5];
                 for (int j = 0; j < 5; ++j) m[j] = im[c * 5 + j];
-                const WhmcTally t = whmcj_participant(&state[c * WHMC_STATE], m, tiles[p].data(), (int)N, T[p], mask, (unsigned)seed,
+                const WhmcTally t = whmcj_participant<HOST_CENSORED>(&state[c * WHMC_STATE], m, tiles[p].data(), (int)N, T[p], mask, (unsigned)seed,
                                                       (unsigned)(seed >> 32), (unsigned)(coff + c), gi, (int)n_adapt, (int)L, (int)thin,
                                                       kept ? &draws[(c * K + slot) * 5] : nullptr, kept ? &lpost[c * K + slot] : nullptr, 0, true,
                                                       ext[p], sigma[k]);
@@ -121,11 +121,12 @@ int main(int argc, char **argv) {
 """
 
 
-def build(td, sanitize=False, f64=False):
-    """Compile the stand-alone program into a directory of its own under td -> its path."""
-    sub = os.path.join(td, ("j64" if f64 else "j32") + ("s" if sanitize else ""))
+def build(td, sanitize=False, f64=False, censored=False):
+    """Compile the stand-alone program into a directory of its own under td -> its path.  censored: NDDM_WIENER_CENSORED's chains."""
+    sub = os.path.join(td, ("j64" if f64 else "j32") + ("s" if sanitize else "") + ("_censored" if censored else ""))
     os.makedirs(sub)
-    return B.build(sub, MAIN % (H.RNG_SHIM + (H.F64_ON if f64 else "")), "wiener_hmc_joint_host", sanitize)
+    switch = "#define HOST_CENSORED %s\n" % ("true" if censored else "false")
+    return B.build(sub, MAIN % (switch + H.RNG_SHIM + (H.F64_ON if f64 else "")), "wiener_hmc_joint_host", sanitize)
 
 
 kept = H.kept

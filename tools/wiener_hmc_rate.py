@@ -10,6 +10,11 @@ one chain), leapfrog x trials per second, the time of one full bounded launch (W
 reference's 2000 + 10 000 iterations cut into bounded launches.
 
 Usage: python tools/wiener_hmc_rate.py [--json OUT] [--iters 8000] [--baseline-iters 60]
+       python tools/wiener_hmc_rate.py --censored [--unflagged-only] [--json OUT] [--iters 4000]
+--censored: NDDM_WIENER_CENSORED's cost at the same shape -- seconds per iteration of the unflagged entry, of the flagged entry on the same
+data (0 % timeouts) and on data with 3 % timeouts, and the gradient kernel at 100 000 rows x 300 trials unflagged, flagged with 0 % and with
+10 % timeouts; every figure the median of three alternating runs.  --unflagged-only: the unflagged legs alone (what a library from before
+the flag can run: point NDDM_HIP_LIB at it to compare the two in one session).
 """
 import argparse
 import json
@@ -68,12 +73,92 @@ def torch_hmc(torch, engine, likelihood, data, q, T, n_iter, eps, gen):
     return q, acc / n_iter
 
 
+def censored_legs(a):
+    import torch
+    import wiener_hmc_host as H
+    from bayesflow_nddms_amd import engine, mcmc
+    engine.require_device()
+    dev = torch.device("cuda")
+    iters = min(a.iters, 4000)
+    data_np = H.example_data(D, N, 41)
+    with3 = H.censor(data_np, share=0.03)
+    legs = {"unflagged": (data_np, False)}
+    if not a.unflagged_only:
+        legs.update({"flagged_0pct_timeouts": (data_np, True), "flagged_3pct_timeouts": (with3, True)})
+    kw = dict(chains_per_dataset=CHAINS, n_leapfrog=LEAPFROG, seed=3)
+    runs = {}
+    for name, (d_np, cens) in legs.items():
+        ck = {"censored": True} if cens else {}
+        theta = mcmc.hmc_init(d_np, CHAINS, 1, **ck).reshape(-1, 5)
+        st = torch.as_tensor(mcmc.make_state(theta, np.repeat(d_np, CHAINS, 0), eps0=EPS, **ck)).to(dev)
+        d = torch.as_tensor(d_np).to(dev)
+        engine.wiener_hmc(engine.BASIC_DDM_DC, d, st, n_iter=300, n_adapt=300, want_draws=False, want_log_post=False, **kw, **ck)
+        torch.cuda.synchronize()
+
+        def loop(d=d, st=st, ck=ck):
+            r = engine.wiener_hmc(engine.BASIC_DDM_DC, d, st.clone(), n_iter=iters, n_adapt=0, iter_offset=300, thin=10, **kw, **ck)
+            return float(r["accept"].mean()), int(r["flagged"].sum())
+        runs[name] = loop
+    # the gradient kernel: 100 000 rows x 300 trials, paired layout
+    R_, N_ = 100_000, 300
+    rng = np.random.default_rng(7)
+    p = torch.as_tensor(np.stack([rng.uniform(-1, 1, R_), rng.uniform(1.2, 1.8, R_), rng.uniform(0.2, 0.8, R_), rng.uniform(0.2, 0.22, R_),
+                                  rng.uniform(0.9, 1.1, R_)], 1).astype(np.float32)).to(dev)
+    rt = torch.rand(R_, N_, device=dev) * 1.65 + 0.35
+    ch = torch.where(torch.rand(R_, N_, device=dev) < 0.5, 1.0, -1.0)
+    g0 = torch.stack([rt, ch], -1).contiguous()
+    to = torch.rand(R_, N_, device=dev) < 0.10
+    g10 = torch.stack([torch.where(to, torch.rand(R_, N_, device=dev) * 0.6 + 0.5, rt), torch.where(to, 0.0, ch)], -1).contiguous()
+    del rt, ch, to
+    glegs = {"grad_unflagged": (g0, False)}
+    if not a.unflagged_only:
+        glegs.update({"grad_flagged_0pct_timeouts": (g0, True), "grad_flagged_10pct_timeouts": (g10, True)})
+    REPS = 5
+    for name, (g, cens) in glegs.items():
+        def loop(g=g, ck=({"censored": True} if cens else {})):
+            for _ in range(REPS):
+                r = engine.wiener_log_likelihood_grad(engine.BASIC_DDM_DC, p, g, **ck)
+            return float(torch.isfinite(r["grad"]).all()), 0
+        runs[name] = loop
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        x = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, x
+    for fn in runs.values():
+        timed(fn)                                                       # warm-up of every shape the timed windows use
+    t = {k: [] for k in runs}
+    seen = {}
+    for _ in range(3):                                                  # alternating
+        for k, fn in runs.items():
+            dt, seen[k] = timed(fn)
+            t[k].append(dt / (REPS if k.startswith("grad") else iters))
+    out = {"tool": "tools/wiener_hmc_rate.py --censored", "device": torch.cuda.get_device_name(0), "library": os.environ.get("NDDM_HIP_LIB", "in-tree"),
+           "sampler": {"chains": D * CHAINS, "n_trials": N, "n_leapfrog": LEAPFROG, "timed_iterations": iters, "timeouts_per_set_at_3pct": 3},
+           "gradient": {"rows": R_, "n_trials": N_, "layout": "paired", "launches_per_run": REPS}, "runs": 3, "legs": {}}
+    for k in runs:
+        unit = "seconds_per_launch" if k.startswith("grad") else "seconds_per_iteration"
+        out["legs"][k] = {unit + "_runs": t[k], unit: float(np.median(t[k])), "spread_of_runs": float((max(t[k]) - min(t[k])) / np.median(t[k])),
+                          "mean_accept_or_all_finite": seen[k][0], "flagged_chains": seen[k][1]}
+    line = json.dumps(out)
+    print(line)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json")
     ap.add_argument("--iters", type=int, default=8000)
     ap.add_argument("--baseline-iters", type=int, default=60)
+    ap.add_argument("--censored", action="store_true")
+    ap.add_argument("--unflagged-only", action="store_true")
     a = ap.parse_args()
+    if a.censored:
+        return censored_legs(a)
     import torch
     import wiener_hmc_host as H
     from bayesflow_nddms_amd import engine, likelihood, mcmc
