@@ -648,12 +648,12 @@ class Trainer:
         self.scheduler = torch.optim.lr_scheduler.LambdaLR(
             self.optimizer, lambda step: 0.5 * (1.0 + math.cos(math.pi * min(step, total) / total)))
 
-    def _prefetcher(self, batch_size, total):
+    def _prefetcher(self, batch_size, total, prefetch=True):
         """Yields `total` configured batches, simulating batch i+1 on a side stream BEFORE batch i is trained on: the
         simulator launch (and a host-side prior) then overlaps the training step, whose loss read-back is the only
         synchronisation point of an iteration.  Batches come in the same order from the same random stream as without
-        prefetching; nothing is simulated beyond `total`."""
-        if self.device.type != "cuda" or total <= 0:
+        prefetching (prefetch=False, or no device: one after the other); nothing is simulated beyond `total`."""
+        if not prefetch or self.device.type != "cuda" or total <= 0:
             for _ in range(total):
                 yield self._simulate(batch_size)
             return
@@ -731,20 +731,30 @@ class Trainer:
         self._optimizer_spent = True
         return val
 
+    def _eager_loop(self, train_on, epochs, iterations_per_epoch, batch_size, validation_sims, save_checkpoint, prefetch,
+                    reuse_optimizer, optimizer, scheduler):
+        """The call as eager steps: this call's schedule, per epoch `iterations_per_epoch` steps -- each on train_on(fresh batch) --
+        then the validation loss (returned, one per epoch) and the checkpoint."""
+        self._setup_schedule(epochs * iterations_per_epoch, optimizer, scheduler)
+        val = []
+        for _ in range(epochs):
+            for conf in self._prefetcher(batch_size, iterations_per_epoch, prefetch):
+                self.loss_history.append(self._step(train_on(conf)))
+            if validation_sims is not None:
+                with torch.no_grad():
+                    val.append(float(self.amortizer.compute_loss(self.configurator(validation_sims))))
+            if save_checkpoint:
+                self.save_checkpoint()
+        self._optimizer_spent = not (reuse_optimizer or optimizer is not None)
+        return val
+
     def train_online(self, epochs, iterations_per_epoch, batch_size, save_checkpoint=True, prefetch=True, reuse_optimizer=False,
                      optimizer=None, scheduler=None, **_):
         if self.graph:
             self._graph_loop(False, epochs, iterations_per_epoch, batch_size, 0, None, save_checkpoint, optimizer)
-            return self.loss_history
-        self._setup_schedule(epochs * iterations_per_epoch, optimizer, scheduler)
-        for ep in range(epochs):
-            batches = (self._prefetcher(batch_size, iterations_per_epoch) if prefetch
-                       else (self._simulate(batch_size) for _ in range(iterations_per_epoch)))
-            for conf in batches:
-                self.loss_history.append(self._step(conf))
-            if save_checkpoint:
-                self.save_checkpoint()
-        self._optimizer_spent = not (reuse_optimizer or optimizer is not None)
+        else:
+            self._eager_loop(lambda conf: conf, epochs, iterations_per_epoch, batch_size, None, save_checkpoint, prefetch,
+                             reuse_optimizer, optimizer, scheduler)
         return self.loss_history
 
     def train_experience_replay(self, epochs, iterations_per_epoch, batch_size, capacity_in_batches=100,
@@ -757,24 +767,17 @@ class Trainer:
             val = self._graph_loop(True, epochs, iterations_per_epoch, batch_size, capacity_in_batches, validation_sims, save_checkpoint,
                                    optimizer)
             return {"train_losses": self.loss_history, "val_losses": val}
-        self._setup_schedule(epochs * iterations_per_epoch, optimizer, scheduler)
         rng = np.random.default_rng(0)
-        val = []
-        for ep in range(epochs):
-            batches = (self._prefetcher(batch_size, iterations_per_epoch) if prefetch
-                       else (self._simulate(batch_size) for _ in range(iterations_per_epoch)))
-            for conf in batches:
-                if len(self.replay) < capacity_in_batches:
-                    self.replay.append(conf)
-                else:
-                    self.replay[rng.integers(capacity_in_batches)] = conf
-                self.loss_history.append(self._step(self.replay[rng.integers(len(self.replay))]))
-            if validation_sims is not None:
-                with torch.no_grad():
-                    val.append(float(self.amortizer.compute_loss(self.configurator(validation_sims))))
-            if save_checkpoint:
-                self.save_checkpoint()
-        self._optimizer_spent = not (reuse_optimizer or optimizer is not None)
+
+        def stored(conf):
+            if len(self.replay) < capacity_in_batches:
+                self.replay.append(conf)
+            else:
+                self.replay[rng.integers(capacity_in_batches)] = conf
+            return self.replay[rng.integers(len(self.replay))]
+
+        val = self._eager_loop(stored, epochs, iterations_per_epoch, batch_size, validation_sims, save_checkpoint, prefetch,
+                               reuse_optimizer, optimizer, scheduler)
         return {"train_losses": self.loss_history, "val_losses": val}
 
     # ---- checkpoint / resume -----------------------------------------------------------------------

@@ -37,6 +37,7 @@ libnddm_train.so builds -- are the networks' forward / backward (amortizer.py) a
 (csrc/train_update.hip): 21 kernels and 0.31 ms per iteration of batch 32 on one MI355X.  Parity with BayesFlow's networks
 is unpinned as for amortizer.py.
 """
+import collections
 import math
 import os as _os
 
@@ -85,6 +86,12 @@ _TIMED_EVENTS = False
 class _Bucket:
     __slots__ = ("n_top", "shard", "params", "trials", "g_shard", "g_params", "g_trials", "t_params", "t_trials", "staged",
                  "r_params", "r_trials", "graphs", "n2", "free_ev")
+
+
+# How one train_* call runs its iterations (GraphTrainer._form): is there a collective, is it the all-gather, the mean over ranks the
+# update applies, the graph key of a simulate stretch of its own (None: fused in front of the training half) and the training half's
+# one or two graph keys.
+_Form = collections.namedtuple("_Form", "coll gather scale replay sim train")
 
 
 class GraphTrainer:
@@ -499,50 +506,57 @@ class GraphTrainer:
             bk.graphs[key] = g
         g.replay()
 
-    def _iteration(self, n, replay=None):
-        """simulate -> [all-gather] -> [experience replay: store, draw, stage] -> forward/backward -> [gradient all-reduce]
-        -> update.  Consecutive stretches with nothing eager between them are ONE graph: the whole iteration online at one
-        rank; simulate | forward/backward/update with an all-gather or the replay buffer in the middle; simulate +
-        forward/backward | update around a gradient all-reduce."""
+    def _form(self, replay, pipelined):
+        """The rule that maps a form -- collective or not, `parallel`, `split`, replay or not, sequential or pipelined -- to its
+        graphs; touches no device.  The training half is TWO graphs around a gradient all-reduce, or where `split` forces that shape
+        without one; an all-gather keeps it one.  Simulate is fused in front of it where nothing eager stands between the two: the
+        sequential loop, online, without an all-gather."""
         coll, ddp = self._has_collective(), self.parallel == "ddp"
         gather = coll and not ddp
+        two = (coll and ddp) or (self.split and not gather)          # forward/backward | [all-reduce] | update
+        fused = not (pipelined or replay or gather)
+        fb = ("sim+" if fused else "") + ("r:" if replay else "") + "fb"
+        return _Form(coll, gather, 1.0 / self.world if (coll and ddp) else 1.0, bool(replay), None if fused else "sim",
+                     (fb, "up") if two else (fb + "+up",))
+
+    def _train_half(self, bk, form, head=None):
+        """The consumer side of an iteration on bucket `bk`: [head +] forward/backward -> [gradient all-reduce] -> update, as
+        form.train's one graph or two (the all-reduce, eager, between them); experience replay trains on the bucket's staged
+        stored batch."""
+        p, t = (bk.r_params, bk.r_trials) if form.replay else (bk.t_params, bk.t_trials)
+        fb = lambda: self._forward_backward(p, t, bk.n2)
+        first = fb if head is None else lambda: (head(), fb())
+        up = lambda: self._update(form.scale)
+        if len(form.train) == 1:
+            self._run(bk, form.train[0], lambda: (first(), up()))
+            return
+        self._run(bk, form.train[0], first)
+        if form.coll:
+            self._all_reduce_gradients()                # (on the training stream itself: it never captures)
+        self._run(bk, form.train[1], up)
+
+    def _iteration(self, n, replay, form):
+        """simulate -> [all-gather] -> [experience replay: store, draw, stage] -> the training half.  Consecutive stretches with
+        nothing eager between them are ONE graph: the whole iteration online at one rank; simulate | forward/backward/update with
+        an all-gather or the replay buffer in the middle; simulate + forward/backward | update around a gradient all-reduce."""
         self._keep_loss_ring()
         bk = self._bucket(self.bucket_top(n))
         self._set_n(bk, n)
         sim = lambda: self._simulate(bk)
-        if replay is None:
-            fb = lambda: self._forward_backward(bk.t_params, bk.t_trials, bk.n2)
-            up = lambda: self._update(1.0 / self.world if (coll and ddp) else 1.0)
-            if not coll and not self.split:
-                self._run(bk, "sim+fb+up", lambda: (sim(), fb(), up()))
-            elif gather:
-                self._run(bk, "sim", sim)
-                self._on_comm_stream(lambda: self._gather(bk))
-                self._stage(bk)
-                self._run(bk, "fb+up", lambda: (fb(), up()))
-            else:                                   # ddp, or the two-graph form forced at one rank without a process group
-                self._run(bk, "sim+fb", lambda: (sim(), fb()))
-                if coll:
-                    self._all_reduce_gradients()                # (on the training stream itself: it never captures)
-                self._run(bk, "up", up)
-            return
-        # experience replay (basic_ddm_dc.py:199-202 calls trainer.train_experience_replay): the fresh batch goes into the
-        # buffer, the step trains on a stored one -- of ITS bucket, with ITS N
-        self._run(bk, "sim", sim)
-        if gather:
+        if form.sim is None:
+            return self._train_half(bk, form, head=sim)
+        self._run(bk, form.sim, sim)
+        if form.gather:
             self._on_comm_stream(lambda: self._gather(bk))
+        if replay is None:
             self._stage(bk)
-        bt = self._replay_stage((bk.t_params.clone(), bk.t_trials.clone(), n), replay)
-        fb = lambda: self._forward_backward(bt.r_params, bt.r_trials, bt.n2)
-        up = lambda: self._update(1.0 / self.world if (coll and ddp) else 1.0)
-        if coll and ddp:
-            self._run(bt, "r:fb", fb)
-            self._all_reduce_gradients()                # (on the training stream itself: it never captures)
-            self._run(bt, "up", up)
         else:
-            self._run(bt, "r:fb+up", lambda: (fb(), up()))
+            # experience replay (basic_ddm_dc.py:199-202 calls trainer.train_experience_replay): the fresh batch goes into the
+            # buffer, the step trains on a stored one -- of ITS bucket, with ITS N
+            bk = self._replay_stage(self._replay_entry(bk, n), replay)
+        self._train_half(bk, form)
 
-    def _train_overlapped(self, iterations, replay):
+    def _train_overlapped(self, ns, replay, form):
         """The pipelined loop (graphs, any world size): the PRODUCER of batch i + 1 -- its `sim` graph on the simulate stream
         and, in `gather` mode, the all-gather that reassembles it on the communication stream -- runs beside the training
         graph(s) of batch i on the training stream.  (A simulate launch of 32 sets is a few dozen waves for 30-200
@@ -550,15 +564,7 @@ class GraphTrainer:
         stays between its two graphs on the training side.  Within this call only: nothing is simulated beyond the last
         iteration, so the random stream's position after the call is what the sequential loop leaves."""
         T, S, C = self._stream, self._sim_stream, self._comm
-        coll, ddp = self._has_collective(), self.parallel == "ddp"
-        gather = coll and not ddp
-        two = (coll and ddp) or (self.split and not gather)          # forward/backward | [all-reduce] | update
-        cur = torch.cuda.current_stream(self.dev)
-        T.wait_stream(cur)
-        S.wait_stream(T)
-        C.wait_stream(T)
-        ns = [shared_prior_N(self.seed, self.n_base + self.iteration + k, self.n_min, self.n_max) for k in range(int(iterations))]
-        up = lambda: self._update(1.0 / self.world if (coll and ddp) else 1.0)
+        gather = form.gather
         stamps = self.stage_stamps = [] if _os.environ.get("NDDM_TRAIN_STAGE_STAMPS") else None     # developer aid (tools/train_stage_times.py)
         # Host order of an iteration.  The producer of batch i + 1 goes to its streams BEFORE the training graph of batch i goes
         # to its own: a cross-stream wait is resolved against what the other stream holds when the wait is ISSUED -- enqueued
@@ -611,59 +617,41 @@ class GraphTrainer:
             entry = None
             if replay is not None:                      # experience replay: the fresh batch is copied out for the buffer by its producer
                 with torch.cuda.stream(C if gather else S):
-                    src_p, src_t = self._produced(bk)
-                    entry = (torch.empty_like(bk.t_params), torch.empty_like(bk.t_trials), n)
-                    self._copy2(entry[0], src_p, entry[1], src_t)
+                    entry = self._replay_entry(bk, n)
                     ev = torch.cuda.Event(enable_timing=_TIMED_EVENTS)
                     ev.record(C if gather else S)
             if gather:
                 last_c[0] = ev
             return ev, bk, entry
 
-        with torch.cuda.device(self.dev):
-            nxt = produce(ns[0]) if ns else None
-            for k, n in enumerate(ns):
-                ev, bk, entry = nxt
-                with torch.cuda.stream(T):
-                    if stamps is not None:
-                        stamps.append([torch.cuda.Event(enable_timing=True) for _ in range(4)])
-                        stamps[-1][0].record(T)
-                    T.wait_event(ev)
-                    if stamps is not None:
-                        stamps[-1][1].record(T)
-                # (the producer's own buffers are read on the producer's streams only -- by the all-gather, the staging, the copy for
-                #  the replay buffer -- so the next producer, which follows on the same streams, needs no event from this one)
-                if produce_first and k + 1 < len(ns):
-                    nxt = produce(ns[k + 1])
-                with torch.cuda.stream(T):
-                    self._keep_loss_ring()
-                    if replay is None:
-                        b, pre = bk, ""
-                        fb = lambda: self._forward_backward(bk.t_params, bk.t_trials, bk.n2)
-                    else:
-                        bt = self._replay_stage(entry, replay)
-                        b, pre = bt, "r:"
-                        fb = lambda: self._forward_backward(bt.r_params, bt.r_trials, bt.n2)
-                    if two:
-                        self._run(b, pre + "fb", fb)
-                        if coll:
-                            self._all_reduce_gradients()                # (on the training stream itself: it never captures)
-                        self._run(b, "up", up)
-                    else:
-                        if stamps is not None:
-                            stamps[-1][2].record(T)
-                        self._run(b, pre + "fb+up", lambda: (fb(), up()))
-                        if stamps is not None:
-                            stamps[-1][3].record(T)
-                    if direct:
-                        bk.free_ev = torch.cuda.Event(enable_timing=_TIMED_EVENTS)
-                        bk.free_ev.record(T)
-                if not produce_first and k + 1 < len(ns):
-                    nxt = produce(ns[k + 1])
-                self.iteration += 1
-        cur.wait_stream(T)
-        cur.wait_stream(S)
-        cur.wait_stream(C)
+        nxt = produce(ns[0]) if ns else None
+        for k, n in enumerate(ns):
+            ev, bk, entry = nxt
+            with torch.cuda.stream(T):
+                if stamps is not None:
+                    stamps.append([torch.cuda.Event(enable_timing=True) for _ in range(4)])
+                    stamps[-1][0].record(T)
+                T.wait_event(ev)
+                if stamps is not None:
+                    stamps[-1][1].record(T)
+            # (the producer's own buffers are read on the producer's streams only -- by the all-gather, the staging, the copy for
+            #  the replay buffer -- so the next producer, which follows on the same streams, needs no event from this one)
+            if produce_first and k + 1 < len(ns):
+                nxt = produce(ns[k + 1])
+            with torch.cuda.stream(T):
+                self._keep_loss_ring()
+                marks = stamps[-1] if stamps is not None and len(form.train) == 1 else None      # (stamps 2, 3: around the one-graph form only)
+                if marks:
+                    marks[2].record(T)
+                self._train_half(bk if direct else self._replay_stage(entry, replay), form)
+                if marks:
+                    marks[3].record(T)
+                if direct:
+                    bk.free_ev = torch.cuda.Event(enable_timing=_TIMED_EVENTS)
+                    bk.free_ev.record(T)
+            if not produce_first and k + 1 < len(ns):
+                nxt = produce(ns[k + 1])
+            self.iteration += 1
 
     def _replay_stage(self, entry, replay):
         """Experience replay's host side: the fresh batch into the buffer (overwriting a random slot once it is full), a stored
@@ -682,17 +670,40 @@ class GraphTrainer:
         p_s.record_stream(cur); t_s.record_stream(cur)                  #  here: the allocator must not hand them out again before this copy)
         return bt
 
+    def _replay_entry(self, bk, n):
+        """A copy of the fresh batch bucket `bk` holds, for the replay buffer: (parameter rows, trials, N), made on the current
+        stream -- the training stream in the sequential loop, the producer's in the pipelined one."""
+        src_p, src_t = self._produced(bk)
+        entry = (torch.empty_like(bk.t_params), torch.empty_like(bk.t_trials), n)
+        self._copy2(entry[0], src_p, entry[1], src_t)
+        return entry
+
+    def _train(self, iterations, replay):
+        """`iterations` steps of one form: the pipelined loop, or the sequential one on the training stream; the caller's stream
+        waits for every stream used."""
+        self._note_schedule_end(iterations)
+        form = self._form(replay is not None, self.overlap)
+        ns = [shared_prior_N(self.seed, self.n_base + self.iteration + k, self.n_min, self.n_max)     # batch-shared N (basic_ddm_dc.py:50-52, 131)
+              for k in range(int(iterations))]
+        cur = torch.cuda.current_stream(self.dev)
+        side = [self._sim_stream, self._comm] if self.overlap else []
+        self._stream.wait_stream(cur)
+        for s_ in side:
+            s_.wait_stream(self._stream)
+        with torch.cuda.device(self.dev):
+            if self.overlap:
+                self._train_overlapped(ns, replay, form)
+            else:
+                with torch.cuda.stream(self._stream):
+                    for n in ns:
+                        self._iteration(n, replay, form)
+                        self.iteration += 1
+        for s_ in [self._stream] + side:
+            cur.wait_stream(s_)
+
     def train_online(self, iterations):
         """`iterations` training steps, every batch fresh; returns nothing -- losses stay on the device until loss_history()."""
-        self._note_schedule_end(iterations)
-        if self.overlap:
-            return self._train_overlapped(iterations, None)
-        self._stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.device(self.dev), torch.cuda.stream(self._stream):
-            for _ in range(int(iterations)):
-                self._iteration(shared_prior_N(self.seed, self.n_base + self.iteration, self.n_min, self.n_max))   # batch-shared N (basic_ddm_dc.py:50-52, 131)
-                self.iteration += 1
-        torch.cuda.current_stream(self.dev).wait_stream(self._stream)
+        self._train(iterations, None)
 
     def train_experience_replay(self, iterations, capacity_in_batches=100, replay_seed=0):
         """The reference's call (basic_ddm_dc.py:199-202): each iteration simulates one fresh batch into a buffer of
@@ -705,15 +716,7 @@ class GraphTrainer:
             ring, rng, _ = self._replay
             del ring[int(capacity_in_batches):]
             self._replay = (ring, rng, int(capacity_in_batches))
-        self._note_schedule_end(iterations)
-        if self.overlap:
-            return self._train_overlapped(iterations, self._replay)
-        self._stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.device(self.dev), torch.cuda.stream(self._stream):
-            for _ in range(int(iterations)):
-                self._iteration(shared_prior_N(self.seed, self.n_base + self.iteration, self.n_min, self.n_max), self._replay)
-                self.iteration += 1
-        torch.cuda.current_stream(self.dev).wait_stream(self._stream)
+        self._train(iterations, self._replay)
 
     # ---- the run's POSITION in the random stream, apart from its weights / optimizer / schedule: what a LATER run (the next
     # train_* call of amortizer.Trainer(graph=True), or a resumed one) needs to continue with fresh data instead of replaying this one's
@@ -721,25 +724,31 @@ class GraphTrainer:
         """{'offset': global index of the next batch's first parameter set (rank 0's row 0), 'n_key': key of the next batch-shared N,
         'replay': the experience-replay buffer and its generator, or None} -- one synchronisation of the training stream."""
         self._stream.synchronize()
-        pos = {"offset": int(self.offset.item()) - self.rank * self.B, "n_key": self.n_base + self.iteration, "replay": None}
-        if self._replay is not None:
-            ring, rng, cap = self._replay
-            pos["replay"] = {"ring": [(p.cpu(), t.cpu(), n) for p, t, n in ring], "rng": rng.bit_generator.state, "capacity": cap}
-        return pos
+        return {"offset": int(self.offset.item()) - self.rank * self.B, "n_key": self.n_base + self.iteration, "replay": self._replay_state()}
+
+    def _replay_state(self):
+        """The experience-replay buffer, its generator and its capacity as host data (None: no replay so far)."""
+        if self._replay is None:
+            return None
+        ring, rng, cap = self._replay
+        return {"ring": [(p.cpu(), t.cpu(), n) for p, t, n in ring], "rng": rng.bit_generator.state, "capacity": cap}
+
+    def _set_replay_state(self, st):
+        import numpy as np
+        self._replay = None
+        if st is not None:
+            rng = np.random.default_rng(0)
+            rng.bit_generator.state = st["rng"]
+            self._replay = ([(p.to(self.dev), t.to(self.dev), n) for p, t, n in st["ring"]], rng, int(st["capacity"]))
 
     def set_position(self, pos):
         """Continue the stream a previous run left at `pos` (position()): the next batch takes the next parameter sets and the next
         N, experience replay goes on with the stored batches.  Weights, Adam's state and the schedule are not touched."""
-        import numpy as np
         self._stream.synchronize()
         with torch.no_grad():
             self.offset.fill_(int(pos["offset"]) + self.rank * self.B)
         self.n_base = int(pos["n_key"]) - self.iteration
-        self._replay = None
-        if pos.get("replay") is not None:
-            rng = np.random.default_rng(0)
-            rng.bit_generator.state = pos["replay"]["rng"]
-            self._replay = ([(p.to(self.dev), t.to(self.dev), n) for p, t, n in pos["replay"]["ring"]], rng, int(pos["replay"]["capacity"]))
+        self._set_replay_state(pos.get("replay"))
         torch.cuda.synchronize(self.dev)
 
     def _note_schedule_end(self, iterations):
@@ -749,7 +758,7 @@ class GraphTrainer:
             import warnings
             self._warned_past_end = True
             warnings.warn(f"GraphTrainer: iteration {self.iteration} + {int(iterations)} goes past total_steps={self.T}; the cosine schedule "
-                          "holds its final learning rate (0) from there on", RuntimeWarning, stacklevel=3)
+                          "holds its final learning rate (0) from there on", RuntimeWarning, stacklevel=4)
 
     def _drain_losses(self):
         """Read the losses the host does not hold yet out of the device ring (one synchronisation of the training stream)."""
@@ -781,13 +790,9 @@ class GraphTrainer:
     # so that a resumed run continues the random stream and reproduces the uninterrupted one
     def state_dict(self):
         self._stream.synchronize()
-        st = {"model": self.amortizer.state_dict(), "optimizer": self._optimizer_state(), "iteration": self.iteration, "n_base": self.n_base,
-              "offset": self.offset.cpu(), "step_i": self.step_i.cpu(), "step_f": self.step_f.cpu(), "lr": self.lr_t.cpu(),
-              "loss_buf": self.loss_buf.cpu(), "loss_host": self.loss_history(), "replay": None}
-        if self._replay is not None:
-            ring, rng, cap = self._replay
-            st["replay"] = {"ring": [(p.cpu(), t.cpu(), n) for p, t, n in ring], "rng": rng.bit_generator.state, "capacity": cap}
-        return st
+        return {"model": self.amortizer.state_dict(), "optimizer": self._optimizer_state(), "iteration": self.iteration, "n_base": self.n_base,
+                "offset": self.offset.cpu(), "step_i": self.step_i.cpu(), "step_f": self.step_f.cpu(), "lr": self.lr_t.cpu(),
+                "loss_buf": self.loss_buf.cpu(), "loss_host": self.loss_history(), "replay": self._replay_state()}
 
     def _moments(self):
         if self.optimizer is None:
@@ -800,30 +805,16 @@ class GraphTrainer:
         return {"exp_avg": m.cpu(), "exp_avg_sq": v.cpu(), "layout": "flat, every parameter tensor padded to a multiple of 4 floats"}
 
     def load_state_dict(self, st):
-        import numpy as np
         self._stream.synchronize()
         with torch.no_grad():
             self.amortizer.load_state_dict(st["model"])
-            # Adam's state tensors are the ones the captured graphs hold: copy INTO them (Adam's step count is step_i)
-            m, v = self._moments()
-            m.copy_(st["optimizer"]["exp_avg"])
-            v.copy_(st["optimizer"]["exp_avg_sq"])
-            if self.optimizer is not None:
-                self.optimizer.state[self._flat_param]["step"].copy_(st["step_i"].to(torch.float32).view(()))
-            self.offset.copy_(st["offset"]); self.step_i.copy_(st["step_i"]); self.step_f.copy_(st["step_f"])
-            self.lr_t.copy_(st["lr"])
-            n = min(self.loss_buf.numel(), st["loss_buf"].numel())
-            self.loss_buf[:n].copy_(st["loss_buf"][:n])
-        self.iteration = int(st["iteration"])
+            self.offset.copy_(st["offset"])
         self.n_base = int(st.get("n_base", 0))
-        # (a checkpoint written before the ring existed holds the first min(iteration, capacity) losses in its buffer)
-        self._loss_host = list(st["loss_host"]) if "loss_host" in st else st["loss_buf"][:min(self.iteration, n)].tolist()
-        self._replay = None
-        if st.get("replay") is not None:
-            rng = np.random.default_rng(0)
-            rng.bit_generator.state = st["replay"]["rng"]
-            self._replay = ([(p.to(self.dev), t.to(self.dev), n) for p, t, n in st["replay"]["ring"]], rng, st["replay"]["capacity"])
-        self._sync_replicas()          # more than one rank: whatever each rank loaded, all continue from rank 0's state
+        self._set_replay_state(st.get("replay"))
+        if "loss_host" not in st:      # (a checkpoint written before the ring existed holds the first min(iteration, capacity) losses in its buffer)
+            n = min(int(st["iteration"]), self.loss_buf.numel(), st["loss_buf"].numel())
+            st = dict(st, loss_host=st["loss_buf"][:n].tolist())
+        self.load_optimizer_state(st)  # (ends with _sync_replicas: more than one rank: whatever each rank loaded, all continue from rank 0's state)
 
     def optimizer_state(self):
         """The part of state_dict() that is neither weights nor position: Adam's two moments, the step counters, the learning rate,
@@ -840,6 +831,7 @@ class GraphTrainer:
         BEFORE set_position (the key of the batch-shared N is counted from the iteration)."""
         self._stream.synchronize()
         with torch.no_grad():
+            # Adam's state tensors are the ones the captured graphs hold: copy INTO them (Adam's step count is step_i)
             m, v = self._moments()
             m.copy_(st["optimizer"]["exp_avg"])
             v.copy_(st["optimizer"]["exp_avg_sq"])

@@ -246,7 +246,13 @@ def test_graph_trainer_checkpoint_resume_reproduces_the_uninterrupted_run(tmp_pa
     with make() as gt:
         gt.train_experience_replay(25, capacity_in_batches=8)
         gt.save_checkpoint(str(tmp_path / "gt.pt"))
-    torch.manual_seed(123)                                   # other initial weights: everything must come from the file
+        # the dictionaries a run's state travels in (the checkpoint formats): their keys
+        st, pos = gt.state_dict(), gt.position()
+        assert set(st) == {"model", "optimizer", "iteration", "n_base", "offset", "step_i", "step_f", "lr", "loss_buf", "loss_host", "replay"}
+        assert set(gt.optimizer_state()) == {"optimizer", "iteration", "step_i", "step_f", "lr", "loss_buf", "loss_host", "total_steps"}
+        assert set(pos) == {"offset", "n_key", "replay"}
+        assert set(st["replay"]) == set(pos["replay"]) == {"ring", "rng", "capacity"}
+    torch.manual_seed(123)                                  # other initial weights: everything must come from the file
     with GraphTrainer(AmortizedPosterior(InvertibleNetwork(num_params=5), InvariantNetwork()), batch_size=32, total_steps=50,
                       seed=2023, learning_rate=1e-3) as gt:
         gt.load_checkpoint(str(tmp_path / "gt.pt"))

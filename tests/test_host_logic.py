@@ -355,6 +355,37 @@ def test_graph_trainer_buckets_and_masked_pooling_equal_the_unpadded_batch():
     assert torch.allclose(net(x_pad, mask, torch.tensor(1.0 / n)), net(x[:, :n]), atol=2e-5)
 
 
+def test_graph_trainer_form_rule_names_the_graphs_of_every_form():
+    """GraphTrainer._form, the device-free rule from a form -- collective or not, `parallel`, `split`, replay or not, sequential or
+    pipelined -- to its graph keys: the simulate stretch of its own (None: fused in front of the training half) and the training
+    half's one graph or two.  Two graphs go with a gradient all-reduce (ddp) or with `split` where no all-gather is in the way; the
+    sequential replay loop with `split` alone follows that rule too."""
+    from bayesflow_nddms_amd.graph_trainer import GraphTrainer
+
+    def keys(replay, pipelined, world=1, parallel="gather", split=False):
+        gt = GraphTrainer.__new__(GraphTrainer)
+        gt.world, gt.parallel, gt.split = world, parallel, split
+        f = gt._form(replay, pipelined)
+        assert f.replay == replay and f.coll == (world > 1) and f.gather == (world > 1 and parallel == "gather")
+        assert f.scale == (1.0 / world if parallel == "ddp" else 1.0)
+        return (f.sim,) + f.train
+
+    one_rank, gather, ddp, split = {}, dict(world=2, split=True), dict(world=2, parallel="ddp", split=True), dict(split=True)
+    # the sequential loop
+    assert keys(False, False, **one_rank) == (None, "sim+fb+up")
+    assert keys(False, False, **gather) == ("sim", "fb+up")
+    assert keys(False, False, **ddp) == keys(False, False, **split) == (None, "sim+fb", "up")
+    assert keys(True, False, **one_rank) == keys(True, False, **gather) == ("sim", "r:fb+up")
+    assert keys(True, False, **ddp) == keys(True, False, **split) == ("sim", "r:fb", "up")
+    # the pipelined loop
+    assert keys(False, True, **one_rank) == keys(False, True, **gather) == ("sim", "fb+up")
+    assert keys(False, True, **ddp) == keys(False, True, **split) == ("sim", "fb", "up")
+    assert keys(True, True, **one_rank) == keys(True, True, **gather) == ("sim", "r:fb+up")
+    assert keys(True, True, **ddp) == keys(True, True, **split) == ("sim", "r:fb", "up")
+    # (a process group without `split` at more than one rank: the collective decides, not the flag)
+    assert keys(False, False, world=2, parallel="ddp") == (None, "sim+fb", "up") and keys(True, True, world=2) == ("sim", "r:fb+up")
+
+
 def test_training_library_builds_and_exports_its_entry_points():
     """libnddm_train.so (the amortizer's flow, summary-network and optimizer kernels: csrc/train_*.hip) cross-compiles for
     gfx950 without a GPU, loads, and exports what _train_lib binds; the shape predicates answer on the host."""
