@@ -699,12 +699,14 @@ using namespace nddm_train;
 
 extern "C" {
 
-// 1 for the shapes the fused flow covers (the caller takes the PyTorch path otherwise)
+// 1 for the shapes the fused flow covers (the caller takes the PyTorch path otherwise).  At least ONE condition column: the
+// weight-gradient kernel loads its condition element from a clamped column, min(.., C - 1), whether it is used or not, and with
+// C == 0 that column is -1 of a [R, 0] tensor -- an unconditional flow (which nothing here trains) takes the PyTorch composition.
 int nddm_train_flow_supported(int hidden, int L, int D, int d1, int C)
 {
     const int d2 = D - d1;
     return (hidden == H && L >= 1 && L <= L_MAX && D >= 2 && D <= D_MAX && d1 >= 1 && d2 >= 1 && d1 + C <= DI_MAX && d2 + C <= DI_MAX
-            && C >= 0 && 2 * d1 <= M_MAX && 2 * d2 <= M_MAX) ? 1 : 0;
+            && C >= 1 && 2 * d1 <= M_MAX && 2 * d2 <= M_MAX) ? 1 : 0;
 }
 
 /* params: L x 14 device pointers per layer -- ActNorm log-scale [D] and bias [D], then W1 [H, Dh + C], b1 [H], W2 [H, H], b2 [H],

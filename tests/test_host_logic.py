@@ -404,6 +404,30 @@ def test_training_library_builds_and_exports_its_entry_points():
     assert build.train_source_hash() == open(build.TRAIN_SO_PATH + ".srchash").read().strip()
 
 
+def test_fused_flow_gate_refuses_an_unconditional_flow():
+    """A flow without condition columns is not the fused kernels': the weight-gradient kernel loads cond[row * C + min(.., C - 1)]
+    unconditionally, which for C == 0 is element -1 of an empty tensor.  The gate says no, the entry points return 1 BEFORE they
+    read an argument or launch (so they are called here with null pointers, on the host), and InvertibleNetwork(cond_dim=0) -- which
+    constructs and runs as a PyTorch composition -- is never handed the library."""
+    import torch
+    from bayesflow_nddms_amd import _train_lib
+    from bayesflow_nddms_amd.amortizer import InvertibleNetwork
+    L = _train_lib.lib()
+    assert L is not None, "libnddm_train.so did not build / load"
+    for D, d1 in ((5, 2), (2, 1), (8, 4)):
+        assert L.nddm_train_flow_supported(128, 6, D, d1, 0) == 0 and L.nddm_train_flow_supported(128, 6, D, d1, 1) == 1
+    assert L.nddm_train_flow_supported(128, 6, 5, 2, -1) == 0
+    assert L.nddm_train_flow_supported(128, 8, 8, 4, 28) == 1 and L.nddm_train_flow_supported(128, 8, 8, 4, 29) == 0     # d + C <= 32
+    assert L.nddm_train_flow_supported(128, 1, 2, 1, 31) == 1 and L.nddm_train_flow_supported(128, 1, 2, 1, 32) == 0
+    assert L.nddm_train_flow_fwd(6, 32, 5, 2, 0, 1.9, *([None] * 11)) == 1
+    assert L.nddm_train_flow_bwd(6, 32, 5, 2, 0, 1.9, *([None] * 17)) == 1
+    net = InvertibleNetwork(num_params=5, cond_dim=0)
+    theta, cond = torch.randn(8, 5), torch.zeros(8, 0)
+    assert net._fused_lib(theta, cond) is None
+    z, ld = net(theta, cond)
+    assert z.shape == (8, 5) and ld.shape == (8,) and bool(torch.isfinite(z).all())
+
+
 _RACE_WORKER = r"""
 import os, stat, sys, time
 sys.path.insert(0, sys.argv[1])
