@@ -169,7 +169,7 @@ __device__ __forceinline__ void finalize_summary(float *o, int n_up, int n_lo, i
     const double mz = ((double)sz / 4294967296.0) / Nd;
     const double vz = ((double)szz / 16777216.0) / Nd - mz * mz;
     o[7] = (float)mz;
-    o[8] = (float)vz;
+    o[8] = (float)(vz < 0 ? 0 : vz);      // the fixed-point sums truncate each term: a tiny variance can come out below 0
     o[9] = (float)(((double)n_up + 0.5 * (double)n_miss) / Nd);
 }
 

@@ -90,8 +90,15 @@ enum nddm_summary_col {
     NDDM_S_VAR_RT = 4,        /* population variance (ddof=0) of the same */
     NDDM_S_MEAN_RT_UPPER = 5, /* EZ-diffusion MRT: mean RT of upper-boundary trials; NaN if none */
     NDDM_S_VAR_RT_UPPER = 6,  /* EZ-diffusion VRT */
+    /* The two z columns come from fixed-point sums -- sum z in units of 2^-32, sum z^2 in units of 2^-24, every term truncated towards
+     * zero, z clamped at +-2^18 -- so that they are bit-reproducible whatever the launch geometry.  With ref the float64 value over the
+     * float32 z1 that are written:  |mean_z - ref| <= 2^-32 + ulp32(ref) / 2,  |var_z - ref| <= 2^-24 + 2 |mean_z| 2^-32 + ulp32(ref) / 2.
+     * A var_z below about 1e-5 is therefore only good to a few percent (and below 6e-8 to nothing).  Variances are never negative:
+     * var_z is clamped at 0 (the truncation can leave sum z^2 / N below mean^2: one trial, or sigma1 ~ 1e-5 and gamma = 0); the RT
+     * variances are formed in float64 from exact integer sums and are within 1 float32 ulp of the exact value of the trials written
+     * (tests/test_gpu_summary.py), an exact 0 included. */
     NDDM_S_MEAN_Z = 7,        /* mean external datum z1 over all trials (0 for models without z1) */
-    NDDM_S_VAR_Z = 8,         /* population variance of z1 */
+    NDDM_S_VAR_Z = 8,         /* population variance of z1, >= 0 */
     NDDM_S_CHOICE_MEAN = 9    /* mean(.5 + .5*sign(choicert)) over all trials */
 };
 
