@@ -7,7 +7,8 @@ from .build import SO_PATH
 
 NDDM_OK, NDDM_ERR_NULL, NDDM_ERR_SHAPE, NDDM_ERR_PARAM, NDDM_ERR_HIP, NDDM_ERR_NO_DEVICE = range(6)
 GAUSS_EXACT, GAUSS_FAST, BRIDGE, GAUSS_PACKED, STATE_F64 = 0, 1, 2, 4, 8
-QUANTILE_CONDITIONAL = 1             # nddm_wiener_quantile's flag (a namespace of its own)
+DEBUG_RAW, DEBUG_HOT, DEBUG_PACKED = 2, 4, 8      # nddm_debug_normals' flags (a namespace of its own, beside GAUSS_FAST)
+QUANTILE_CONDITIONAL = 1            # nddm_wiener_quantile's flag (a namespace of its own)
 HMC_SIGMA_FIXED = 1                  # nddm_wiener_hmc_joint's flag (a namespace of its own)
 WIENER_CENSORED = 4                  # nddm_wiener_log_likelihood_grad's flag: score basic_ddm_dc's timeouts in the gradient too
 ABI_VERSION = 4

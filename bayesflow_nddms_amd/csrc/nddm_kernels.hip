@@ -1404,11 +1404,25 @@ int nddm_debug_normals(const uint32_t *counters, int64_t n, uint32_t k0, uint32_
     if (n < 0) return nddm::fail(NDDM_ERR_SHAPE, "n < 0%s");
     if (n == 0) return NDDM_OK;
     if (!counters || !out) return nddm::fail(NDDM_ERR_NULL, "null pointer%s");
+    if (flags & ~(uint32_t)(NDDM_GAUSS_FAST | NDDM_DEBUG_RAW | NDDM_DEBUG_HOT | NDDM_DEBUG_PACKED))
+        return nddm::fail(NDDM_ERR_PARAM, "nddm_debug_normals: unknown flag bits%s");
+    if ((flags & (NDDM_DEBUG_HOT | NDDM_DEBUG_PACKED)) && !(flags & NDDM_DEBUG_RAW))
+        return nddm::fail(NDDM_ERR_PARAM, "nddm_debug_normals: NDDM_DEBUG_HOT and NDDM_DEBUG_PACKED select a form of the raw dump: set NDDM_DEBUG_RAW%s");
+    if ((flags & NDDM_DEBUG_HOT) && (flags & NDDM_DEBUG_PACKED))
+        return nddm::fail(NDDM_ERR_PARAM, "nddm_debug_normals: the packed layout has one form: NDDM_DEBUG_HOT cannot go with NDDM_DEBUG_PACKED%s");
     if (const int rc = nddm::check_stream(reinterpret_cast<hipStream_t>(stream))) return rc;
     const int threads = 256;
     const long long blocks = (n + threads - 1) / threads;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (flags & NDDM_GAUSS_FAST)
+    if (flags & NDDM_DEBUG_RAW) {
+        const bool fast = (flags & NDDM_GAUSS_FAST) != 0;
+        const int form = (flags & NDDM_DEBUG_PACKED) ? 2 : ((flags & NDDM_DEBUG_HOT) ? 1 : 0);
+#define NDDM_RAW(F, M) hipLaunchKernelGGL((nddm::debug_raw_kernel<F, M>), dim3((unsigned)blocks), dim3(threads), 0, st, counters, (long long)n, k0, k1, out)
+        if (fast) { if (form == 2) NDDM_RAW(true, 2); else if (form == 1) NDDM_RAW(true, 1); else NDDM_RAW(true, 0); }
+        else { if (form == 2) NDDM_RAW(false, 2); else if (form == 1) NDDM_RAW(false, 1); else NDDM_RAW(false, 0); }
+#undef NDDM_RAW
+    }
+    else if (flags & NDDM_GAUSS_FAST)
         hipLaunchKernelGGL(nddm::debug_normals_kernel<true>, dim3((unsigned)blocks), dim3(threads), 0, st, counters,
                            (long long)n, k0, k1, out);
     else

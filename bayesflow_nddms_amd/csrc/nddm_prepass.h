@@ -146,6 +146,29 @@ __global__ void debug_normals_kernel(const uint32_t *ctr, long long n, uint32_t 
     out[4 * i] = z[0]; out[4 * i + 1] = z[1]; out[4 * i + 2] = z[2]; out[4 * i + 3] = z[3];
 }
 
+// the transform's own factors (NDDM_DEBUG_RAW): per counter the (r, cos, sin) of the block's Box-Muller pairs, the radius in noise
+// units (no noise_unit multiply), exactly as the simulators' step loop and auxiliary stream receive them.
+// FORM 0: polar_pair<FAST> (AuxStream), 1: polar_pair<FAST, true> (the step loop) -- two pairs, 6 floats;
+// FORM 2: polar_pair_packed<FAST> -- four pairs, 12 floats
+template <bool FAST, int FORM>
+__global__ void debug_raw_kernel(const uint32_t *ctr, long long n, uint32_t k0, uint32_t k1, float *out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32x4 x = philox4x32_10(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], k0, k1);
+    if constexpr (FORM == 2) {
+        float *o = out + 12 * i;
+        polar_pair_packed<FAST>(x.x, o[0], o[1], o[2]);
+        polar_pair_packed<FAST>(x.y, o[3], o[4], o[5]);
+        polar_pair_packed<FAST>(x.z, o[6], o[7], o[8]);
+        polar_pair_packed<FAST>(x.w, o[9], o[10], o[11]);
+    } else {
+        float *o = out + 6 * i;
+        polar_pair<FAST, FORM == 1>(x.x, x.y, o[0], o[1], o[2]);
+        polar_pair<FAST, FORM == 1>(x.z, x.w, o[3], o[4], o[5]);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // on-device draw_prior(): basic_ddm_dc.py:62-80 / single_trial_alpha_not_scaled.py:78-102 (+ _alt :889-913,
 // _scale :1205-1232 share the marginals).  Stream 2 of the row; one thread per row.

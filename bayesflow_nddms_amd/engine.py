@@ -197,7 +197,8 @@ def simulate(model, params, n_trials, dt=0.01, max_steps=400.0, seed=None, set_o
 
     want_codes / out_codes: also (or, with want_trials=False, only) write the trials in the 2-byte wire format, int16 [B, n_trials]
     holding uint16 (step index | code << 14) -- basic_ddm_dc and alpha_not_scaled without the bridge, max_steps < 2^14;
-    decode_codes() gives the float pairs back (include/nddm.h: nddm_simulate_codes).
+    decode_codes() gives the float pairs back (include/nddm.h: nddm_simulate_codes).  That entry point has no output for
+    alpha_not_scaled's external datum: with want_ext it is written by a second, step-less launch (the same bits as any launch's).
 
     Returns a dict of torch tensors on the device: 'trials' f32 [B, n_trials, 2], 'summary' f32 [B, 10],
     'ext' f32 [B] (alpha_not_scaled only), plus 'seed' / 'set_offset' actually used.
@@ -249,6 +250,13 @@ def simulate(model, params, n_trials, dt=0.01, max_steps=400.0, seed=None, set_o
                                                    and set_offset_dev.dtype == torch.int64 and set_offset_dev.numel() >= 1):
                 raise ValueError("set_offset_dev must be a device int64 tensor")
             if out_codes is not None:
+                if out_ext is not None:
+                    # nddm_simulate_codes has no output for the external datum.  The datum is a function of (seed, set, Alpha, ext_sigma,
+                    # ext_mode) and the transform alone -- not of the trials -- so a launch of one step-less trial per set writes the
+                    # bits any launch would (first: last_launch() then describes the launch that simulates)
+                    _lib.check(L.nddm_simulate_indirect(model, _ptr(p_dev), None, B, 1, float(dt), 0, seed, set_offset, _ptr(set_offset_dev),
+                                                        _lib.GAUSS_FAST if fast else _lib.GAUSS_EXACT, float(ext_sigma), int(ext_mode),
+                                                        None, None, _ptr(out_ext), st))
                 rc = L.nddm_simulate_codes(model, _ptr(p_dev), *common[:-1], _ptr(set_offset_dev), flags, _ptr(out_codes), _ptr(out_trials),
                                            _ptr(out_summary), st)
             elif set_offset_dev is not None:
@@ -882,13 +890,31 @@ def simulate_to_host(model, params, n_trials, seed=None, set_offset=None, stream
     return res
 
 
-def debug_normals(counters, k0, k1, fast=False):
-    """4 normals per Philox counter row (tests compare these with the oracle's)."""
+def debug_normals(counters, k0, k1, fast=False, raw=False, form=None):
+    """4 normals per Philox counter row (tests compare these with the oracle's).
+    raw=True: the transform's own factors instead (include/nddm.h: NDDM_DEBUG_RAW) -- [n, 6] = r0, cos0, sin0, r1, cos1, sin1 with the
+    radius in noise units, in the form the auxiliary stream evaluates (form=None or "aux"), the step loop's (form="hot"), or [n, 12]
+    for the four pairs of the packed layout (form="packed").
+    counters: anything np.asarray takes, or an int32 device tensor [n, 4] holding the words' bits."""
     torch = require_device()
-    c = torch.as_tensor(np.asarray(counters, dtype=np.uint32).view(np.int32)).cuda().contiguous()
+    if form not in (None, "aux", "hot", "packed"):
+        raise ValueError(f"debug_normals: form={form!r} (None, 'aux', 'hot' or 'packed')")
+    if form is not None and not raw:
+        raise ValueError("debug_normals: form= selects a form of the raw dump (raw=True)")
+    if isinstance(counters, torch.Tensor):
+        if counters.dtype != torch.int32 or counters.dim() != 2 or counters.shape[1] != 4:
+            raise ValueError("debug_normals: a counter tensor is int32 [n, 4]")
+        c = counters.cuda().contiguous()
+    else:
+        c = torch.as_tensor(np.asarray(counters, dtype=np.uint32).view(np.int32)).cuda().contiguous()
     n = c.shape[0]
-    out = torch.empty((n, 4), dtype=torch.float32, device=c.device)
-    rc = _lib.lib().nddm_debug_normals(c.data_ptr(), n, int(k0), int(k1), 1 if fast else 0, out.data_ptr(),
+    flags = 1 if fast else 0
+    width = 4
+    if raw:
+        flags |= _lib.DEBUG_RAW | {"hot": _lib.DEBUG_HOT, "packed": _lib.DEBUG_PACKED}.get(form, 0)
+        width = 12 if form == "packed" else 6
+    out = torch.empty((n, width), dtype=torch.float32, device=c.device)
+    rc = _lib.lib().nddm_debug_normals(c.data_ptr(), n, int(k0), int(k1), flags, out.data_ptr(),
                                        torch.cuda.current_stream().cuda_stream)
     _lib.check(rc)
     return out.cpu().numpy()

@@ -527,9 +527,21 @@ const char *nddm_source_hash(void);
 /* "hipcc=<version>": the compiler that built this library, recorded at build time */
 const char *nddm_build_info(void);
 
-/* ---- debugging aid used by the parity tests: the 4 normals of Philox block (c0..c3) under key (k0,k1) --- */
+/* ---- debugging aid used by the parity tests: the 4 normals of Philox block (c0..c3) under key (k0,k1) ---
+ * flags: NDDM_GAUSS_EXACT / NDDM_GAUSS_FAST (bit 0) and the bits below, a namespace of this entry point.  With NDDM_DEBUG_RAW the
+ * output is the transform's own factors instead of the normals -- what the simulators' step loop and auxiliary stream consume: per
+ * counter r0, cos0, sin0, r1, cos1, sin1 of the block's two Box-Muller pairs, the radius in NOISE UNITS (exact: sqrt(-2 ln u); fast:
+ * sqrt(-log2 u), before any multiply by sqrt(2 ln 2)).  A normal of flags 0 / 1 is (r * unit) * cos|sin.  Fed to the CPU oracle in
+ * place of its exact transform (oracle/ddm_oracle.c: oracle_philox_simulate_tab) they hold the fast mode to it bit for bit.
+ * Any other bit, a form bit without NDDM_DEBUG_RAW, and NDDM_DEBUG_HOT together with NDDM_DEBUG_PACKED are NDDM_ERR_PARAM. */
+enum nddm_debug_normals_flags {
+    NDDM_DEBUG_RAW = 2,       /* out f32 [n,6]: (r, cos, sin) of the two pairs */
+    NDDM_DEBUG_HOT = 4,       /* with NDDM_DEBUG_RAW: the step loop's form of the pair (the angle spliced by v_bitop3_b32 with constants
+                                 held in registers) instead of the auxiliary stream's (shift + v_alignbit_b32) */
+    NDDM_DEBUG_PACKED = 8     /* with NDDM_DEBUG_RAW: the NDDM_GAUSS_PACKED layout, out f32 [n,12]: (r, cos, sin) of the four pairs */
+};
 int nddm_debug_normals(const uint32_t *counters /* device u32 [n,4] */, int64_t n, uint32_t k0, uint32_t k1,
-                       uint32_t flags, float *out /* device f32 [n,4] */, void *stream);
+                       uint32_t flags, float *out /* device f32 [n,4], [n,6] or [n,12] */, void *stream);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,14 @@ def lib():
         L.oracle_philox_ratcliff.argtypes = [fp, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_float, ctypes.c_int,
                                              fp, fp, fp, ctypes.c_int]
         L.oracle_philox_ratcliff.restype = ctypes.c_int
+        tab = [fp, ctypes.c_int, fp, ctypes.c_int, ctypes.c_float, ctypes.c_int]      # path, n_path, aux, n_aux, unit, fast
+        L.oracle_philox_simulate_tab.argtypes = L.oracle_philox_simulate.argtypes + tab + [ctypes.POINTER(ctypes.c_uint8)]
+        L.oracle_philox_simulate_tab.restype = ctypes.c_int
+        L.oracle_philox_simulate_f64_tab.argtypes = L.oracle_philox_simulate_f64.argtypes + tab
+        L.oracle_philox_simulate_f64_tab.restype = ctypes.c_int
+        L.oracle_philox_raw.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                        ctypes.c_int, fp, ctypes.c_int]
+        L.oracle_philox_raw.restype = None
         L.oracle_philox_normals4.argtypes = [ctypes.c_uint32] * 6 + [fp]
         L.oracle_philox_block.argtypes = [ctypes.c_uint32] * 6 + [ctypes.POINTER(ctypes.c_uint32)]
         _lib = L
@@ -142,10 +150,44 @@ def mt_ratcliff(N=100, Alpha=1, Tau=.4, Nu=1, Beta=.5, rangeTau=0, rangeBeta=0, 
 
 
 # ----------------------------------------------------------------------------- Philox mode
+FAST_UNIT = np.float32(1.1774100225154747)       # sqrt(2 ln 2): nddm_rng.h noise_unit<true>
+
+
+def _table_args(table, B, n_trials, packed):
+    """(path ptr, n_path, aux ptr, n_aux, unit, fast, keep-alive) of a transform table: dict(path f32[B,N,n_path,6|12],
+    aux f32[B,N+1,n_aux,6] or None, unit, fast) -- ddm_oracle.c: xform_tab."""
+    if table is None:
+        return (None, 0, None, 0, np.float32(1.0), 0), ()
+    path = np.ascontiguousarray(table["path"], dtype=np.float32)
+    assert path.ndim == 4 and path.shape[:2] == (B, n_trials) and path.shape[3] == (12 if packed else 6), path.shape
+    aux = table.get("aux")
+    n_aux = 0
+    if aux is not None:
+        aux = np.ascontiguousarray(aux, dtype=np.float32)
+        assert aux.ndim == 4 and aux.shape[:2] == (B, n_trials + 1) and aux.shape[3] == 6, aux.shape
+        n_aux = aux.shape[2]
+    return (_fptr(path), path.shape[2], _fptr(aux), n_aux, np.float32(table.get("unit", 1.0)), int(bool(table.get("fast", False)))), (path, aux)
+
+
+def philox_raw(counters, k0, k1, packed=False, standin=False, threads=8):
+    """(r, cos, sin) of the Box-Muller pairs of each Philox counter row, f32 [n, 6] (packed: [n, 12]) -- the CPU twin of
+    engine.debug_normals(raw=True).  standin=False: the exact transform's own factors; True: a float64 evaluation of the fast
+    transform's (radius sqrt(-log2 u))."""
+    c = np.ascontiguousarray(counters, dtype=np.uint32).reshape(-1, 4)
+    out = np.empty((c.shape[0], 12 if packed else 6), np.float32)
+    lib().oracle_philox_raw(c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), c.shape[0], int(k0), int(k1), int(bool(packed)),
+                            int(bool(standin)), _fptr(out), threads)
+    return out
+
+
 def philox_simulate(model, params, n_trials, dt=0.01, max_steps=400.0, seed=0, set_offset=0, bounds=None,
                     ext_sigma=0.0, ext_mode=0, bridge=False, packed=False, want_trials=True, want_k=False, want_summary=True,
-                    want_ext=False, threads=1):
+                    want_ext=False, threads=1, table=None):
     """The device stream on the CPU: element-wise checker of the HIP kernels.
+
+    table: an injected Gaussian transform (_table_args; ddm_oracle.c: xform_tab) read in place of the exact one -- the device's own
+    fast-mode factors hold the fast kernels to this function bit for bit.  With it the result has 'undecided' bool[B,N]: trials
+    with a bridge step whose crossing test lies within the error of the device's exp2 (none without bridge / table['fast']).
 
     Returns dict(trials f32[B,N,2], k i32[B,N], summary f32[B,10], ext f32[B]) (requested keys only)."""
     L = lib()
@@ -164,13 +206,17 @@ def philox_simulate(model, params, n_trials, dt=0.01, max_steps=400.0, seed=0, s
     k = np.empty((B, n_trials), np.int32) if want_k else None
     summ = np.empty((B, SUMMARY_K), np.float32) if want_summary else None
     ext = np.empty((B,), np.float32) if want_ext else None
-    rc = L.oracle_philox_simulate(
+    targs, _keep = _table_args(table, B, n_trials, packed)
+    und = np.zeros((B, n_trials), np.uint8) if table is not None else None
+    rc = L.oracle_philox_simulate_tab(
         model, int(bool(bridge)) | (2 if packed else 0), _fptr(p), _fptr(bnd), B, n_trials, np.float32(dt), max_k, seed, set_offset,
         np.float32(ext_sigma), ext_mode, _fptr(trials),
         None if k is None else k.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(summ), _fptr(ext),
-        threads)
+        threads, *targs, None if und is None else und.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
     if rc != 0:
-        raise ValueError(f"oracle_philox_simulate rc={rc}")
+        raise ValueError(f"oracle_philox_simulate rc={rc}" + (" (a trial ran beyond the transform table)" if rc == 4 else ""))
+    if und is not None:
+        res["undecided"] = und.astype(bool)
     if want_trials:
         res["trials"] = trials
     if want_k:
@@ -205,7 +251,7 @@ def philox_ratcliff(params, n_trials, seed=0, set_offset=0, ext_sigma=0.0, ext_m
     return res
 
 
-def philox_simulate_f64(model, params, n_trials, dt=0.01, max_steps=400.0, seed=0, set_offset=0, threads=1, want_outputs=False):
+def philox_simulate_f64(model, params, n_trials, dt=0.01, max_steps=400.0, seed=0, set_offset=0, threads=1, want_outputs=False, table=None):
     """The REFERENCE'S float64 recurrence (basic_ddm_dc.py:91-103; single_trial_alpha_not_scaled.py:113-128) on the device
     stream's normals: (k i32[B,N], choice i32[B,N]) -- compare with philox_simulate(want_k=True) trial by trial to state how
     often the float32 integrator of the product ends on another (step, choice) than the float64 one.
@@ -223,8 +269,9 @@ def philox_simulate_f64(model, params, n_trials, dt=0.01, max_steps=400.0, seed=
     ip = ctypes.POINTER(ctypes.c_int32)
     trials = np.empty((B, n_trials, 2), np.float32) if want_outputs else None
     summ = np.empty((B, SUMMARY_K), np.float32) if want_outputs else None
-    rc = L.oracle_philox_simulate_f64(model, _fptr(p), B, n_trials, np.float32(dt), int(np.ceil(max_steps)), seed, set_offset,
-                                      k.ctypes.data_as(ip), c.ctypes.data_as(ip), _fptr(trials), _fptr(summ), threads)
+    targs, _keep = _table_args(table, B, n_trials, False)
+    rc = L.oracle_philox_simulate_f64_tab(model, _fptr(p), B, n_trials, np.float32(dt), int(np.ceil(max_steps)), seed, set_offset,
+                                          k.ctypes.data_as(ip), c.ctypes.data_as(ip), _fptr(trials), _fptr(summ), threads, *targs)
     if rc != 0:
         raise ValueError(f"oracle_philox_simulate_f64 rc={rc}")
     if want_outputs:

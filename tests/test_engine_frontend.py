@@ -310,6 +310,39 @@ def test_caller_supplied_buffers_are_used_or_refused_untouched(name):
 
 
 @gpu
+@pytest.mark.parametrize("fast", [False, True])
+def test_the_wire_format_launch_returns_a_written_external_datum(fast):
+    """nddm_simulate_codes has no output for alpha_not_scaled's per-set external datum; simulate(want_codes=True, want_ext=True) fills it
+    with a launch of its own (one step-less trial per set).  The datum is the one a plain launch writes, bit for bit -- with and without
+    the float pairs, with a device-resident part of the set offset -- and, in exact mode, the oracle's; the launch that last_launch()
+    describes is the one that simulated."""
+    import oracle
+    p = np.concatenate([P_RATCLIFF] * 40)
+    nb, n = len(p), 70
+    kw = dict(dt=DT, max_steps=MAX_STEPS, seed=11, fast=fast, ext_sigma=0.25, ext_mode=0, want_ext=True)
+    plain = engine.simulate(engine.ALPHA_NOT_SCALED, p, n, set_offset=(1 << 34) + 5, **kw)
+    engine.simulate(engine.ALPHA_NOT_SCALED, p, n, set_offset=(1 << 34) + 5, want_codes=True, **dict(kw, want_ext=False))
+    geo = engine.last_launch()
+    both = engine.simulate(engine.ALPHA_NOT_SCALED, p, n, set_offset=(1 << 34) + 5, want_codes=True, **kw)
+    assert engine.last_launch() == geo
+    only = engine.simulate(engine.ALPHA_NOT_SCALED, p, n, set_offset=(1 << 34) + 5, want_codes=True, want_trials=False, want_summary=False, **kw)
+    off = torch.tensor([1 << 34], dtype=torch.int64, device="cuda")
+    ind = engine.simulate(engine.ALPHA_NOT_SCALED, p, n, set_offset=5, set_offset_dev=off, want_codes=True, **kw)
+    for r in (both, only, ind):
+        assert r["ext"].shape == (nb,) and torch.equal(r["ext"].view(torch.int32), plain["ext"].view(torch.int32))
+        assert torch.equal(r["codes"], both["codes"])
+    assert torch.equal(both["trials"], plain["trials"])
+    mode1 = engine.simulate(engine.ALPHA_NOT_SCALED, p, n, set_offset=3, want_codes=True, **dict(kw, ext_mode=1))
+    assert torch.equal(mode1["ext"], engine.simulate(engine.ALPHA_NOT_SCALED, p, n, set_offset=3, **dict(kw, ext_mode=1))["ext"])
+    if not fast:
+        o = oracle.philox_simulate(oracle.M_ALPHA_NS, p, n, dt=DT, max_steps=MAX_STEPS, seed=11, set_offset=(1 << 34) + 5, ext_sigma=0.25,
+                                   ext_mode=0, want_ext=True, want_trials=False, want_summary=False)
+        assert np.array_equal(both["ext"].cpu().numpy().view(np.uint32), o["ext"].view(np.uint32))
+    basic = engine.simulate(engine.BASIC_DDM_DC, P_BASIC, n, dt=DT, max_steps=MAX_STEPS, seed=1, set_offset=0, want_codes=True, want_ext=True)
+    assert "ext" not in basic                       # (a model without the datum: nothing to fill, nothing returned)
+
+
+@gpu
 def test_an_empty_batch_returns_empty_tensors_and_launches_nothing():
     engine.simulate(engine.BASIC_DDM_DC, P_BASIC, N_TRIALS, dt=DT, max_steps=MAX_STEPS, seed=1, set_offset=0)
     last = engine.last_launch()
