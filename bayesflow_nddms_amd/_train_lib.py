@@ -1,4 +1,5 @@
-"""ctypes binding of libnddm_train.so: the amortizer's flow as one kernel each way (csrc/train_kernels.hip) and the summary
+"""ctypes binding of libnddm_train.so: the amortizer's flow as one kernel each way (csrc/train_kernels.hip), its inverse -- the
+posterior sampler -- as one kernel (csrc/train_sample.hip), and the summary
 network's per-trial MLPs (csrc/train_deepset.hip), and the optimizer step on flat buffers (csrc/train_update.hip).
 Optional: `lib()` returns None when the library cannot be built or loaded, and the amortizer then runs its PyTorch path."""
 import ctypes
@@ -31,6 +32,11 @@ def lib():
     #                               ... params perm grads theta cond z_all out_all s_all h_all g_z g_ld g_nll gz_all gx gcond work stream
     L.nddm_train_flow_bwd.argtypes = [i32, i32, i32, i32, i32, f32, vp, vp, vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]
     L.nddm_train_flow_bwd.restype = i32
+    #                                  hidden L  B    S    D    d1   C    clamp params perm z cond theta lo hi sums n_outside work stream
+    L.nddm_train_flow_sample.argtypes = [i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, fp, fp, fp, fp, fp, fp, fp, fp, vp]   # csrc/train_sample.hip
+    L.nddm_train_flow_sample.restype = i32
+    L.nddm_train_flow_sample_work_bytes.argtypes = [i32, i32, i32]                                                             # B S D
+    L.nddm_train_flow_sample_work_bytes.restype = c.c_longlong
     L.nddm_deepset_supported.argtypes = [i32, i32]
     L.nddm_deepset_supported.restype = i32
     common = [fp, i32, i32, i32, i32, i32, fp, i32, fp, f32, fp, i32, fp, i32, fp, fp, fp, fp, fp, i32, fp, i32]   # x .. S_x (csrc/train_deepset.hip)

@@ -431,10 +431,11 @@ class InvertibleNetwork(nn.Module):
         self._refresh_host_perms()  # (host copies: reading the buffers back would synchronise, which a graph capture forbids)
         self.register_load_state_dict_post_hook(self._refresh_host_perms)
 
-    def _fused_lib(self, theta, cond):
-        """libnddm_train.so if the fused flow covers this network and these tensors, else None (the PyTorch composition)."""
+    def _fused_lib(self, theta, cond, rows_limit=True):
+        """libnddm_train.so if the fused flow covers this network and these tensors, else None (the PyTorch composition).
+        rows_limit=False: the sampler's gate (csrc/train_sample.hip takes any number of draws)."""
         if not (self.fused and len(self.layers) and theta.is_cuda and theta.dtype == torch.float32 and cond.dtype == torch.float32
-                and theta.shape[0] <= self.FUSED_MAX_ROWS):
+                and (theta.shape[0] <= self.FUSED_MAX_ROWS or not rows_limit)):
             return None
         l0 = self.layers[0]
         if any(len(n) != 5 or not isinstance(n[1], nn.ELU) for l in self.layers for n in (l.net1, l.net2)):
@@ -506,6 +507,53 @@ class InvertibleNetwork(nn.Module):
             x = (x - self.an_bias[i]) * torch.exp(-self.an_scale[i])
         return x
 
+    def _sample_lib(self, z, cond):
+        """libnddm_train.so if the fused sampler covers z [B, S, D] with one condition row per set, cond [B, C]; else None.  The
+        kernel is no autograd node: where a gradient could be asked for, the PyTorch composition serves."""
+        if z.dim() != 3 or cond.dim() != 2 or z.shape[0] != cond.shape[0] or z.numel() == 0 or z.device != cond.device:
+            return None
+        if torch.is_grad_enabled() and (z.requires_grad or cond.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return None
+        return self._fused_lib(z.reshape(-1, z.shape[-1]), cond, rows_limit=False)
+
+    def _fused_sample(self, L, z, cond, box=None, draws=True, moments=False, out=None, sums=None, n_outside=None):
+        """One launch of csrc/train_sample.hip on z [B, S, D], cond [B, C] -> (theta [B, S, D] or None, sums [B, 2 D] float64 or None,
+        n_outside [B] int64 or None): the draws (draws=True), and / or (moments=True) per set the float64 sums of theta and of
+        theta^2 over the draws INSIDE -- every component finite and, with box = (lo [D], hi [D]) float32 tensors, within it -- and
+        the number of draws outside.  out / sums / n_outside: contiguous tensors to write into (else allocated here)."""
+        import ctypes
+        (B, S, D), C, dev, nl = z.shape, cond.shape[1], z.device, len(self.layers)
+        params = self._flow_params()
+        ptrs = (ctypes.c_void_p * (14 * nl))(*[p.data_ptr() for p in params])
+        perm = (ctypes.c_int * (nl * D))(*[int(v) for p in self._perm_host for v in p])
+        z, cond = z.contiguous(), cond.contiguous()
+        if draws and out is None:
+            out = torch.empty(B, S, D, dtype=torch.float32, device=dev)
+        if moments:
+            sums = torch.empty(B, 2 * D, dtype=torch.float64, device=dev) if sums is None else sums
+            n_outside = torch.empty(B, dtype=torch.int64, device=dev) if n_outside is None else n_outside
+        lo, hi = (None, None) if box is None else (v.to(dev, torch.float32).contiguous() for v in box)
+        work = torch.empty(int(L.nddm_train_flow_sample_work_bytes(B, S, D)), dtype=torch.uint8, device=dev)
+        ptr = lambda v: None if v is None else v.data_ptr()       # noqa: E731
+        rc = L.nddm_train_flow_sample(params[4].shape[0], nl, B, S, D, self.layers[0].d1, C, float(self.layers[0].clamp), ptrs, perm,
+                                      z.data_ptr(), cond.data_ptr(), ptr(out) if draws else None, ptr(lo), ptr(hi),
+                                      ptr(sums) if moments else None, ptr(n_outside) if moments else None, work.data_ptr(),
+                                      torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"nddm_train_flow_sample failed ({rc})")
+        return (out if draws else None), (sums if moments else None), (n_outside if moments else None)
+
+    def inverse_per_set(self, z, cond):
+        """The inverse on draws grouped by data set: z [B, S, D] base normals, cond [B, C] ONE condition row per set -> [B, S, D].
+        Where the fused sampler applies (cuda, float32, the shapes of nddm_train_flow_supported, self.fused, no gradient asked for) it
+        is one kernel that never expands the condition (csrc/train_sample.hip); otherwise `inverse` on the condition repeated S
+        times -- the same map."""
+        B, S, D = z.shape
+        L = self._sample_lib(z, cond)
+        if L is not None:
+            return self._fused_sample(L, z, cond)[0]
+        return self.inverse(z.reshape(B * S, D), cond.repeat_interleave(S, dim=0)).reshape(B, S, D)
+
 
 class AmortizedPosterior(nn.Module):
     """bf.amortizers.AmortizedPosterior(inference_net, summary_net): maximum-likelihood training of q(theta | data)."""
@@ -546,7 +594,7 @@ class AmortizedPosterior(nn.Module):
         return (0.5 * (z ** 2).sum(-1) - log_det).mean()
 
     @torch.no_grad()
-    def sample(self, input_dict, n_samples, to_numpy=True, reject_outside=None, max_redraws=16):
+    def sample(self, input_dict, n_samples, to_numpy=True, reject_outside=None, max_redraws=16, fused=False):
         """amortizer.sample(dict, n_samples) (basic_ddm_dc.py:223): [n_samples, P] for a single data set,
         [B, n_samples, P] for a batch.
 
@@ -557,13 +605,23 @@ class AmortizedPosterior(nn.Module):
         section 8), and a posterior MEAN over 10 000 draws -- the statistic the reference's recovery plots use, basic_ddm_dc.py:
         230-236 -- is carried off by one such draw; `priors.prior_box(model)` is a generous box (the prior's support widened by
         its own width on each side) that removes them and nothing else.  The number of redrawn draws of the last call is kept in
-        `self.last_redrawn` (0 with the option off)."""
+        `self.last_redrawn` (0 with the option off).
+
+        fused=True: the same base normals (the generator is consumed identically) go through `inverse_per_set` -- on the device one
+        kernel for all draws, which reads each data set's condition row once instead of n_samples copies of it (csrc/
+        train_sample.hip) -- and the few redrawn rows through the PyTorch inverse.  The draws agree with the default's to float32
+        round-off (tests/test_gpu_flow_sample.py), not bit for bit; the default (False) is the PyTorch composition, unchanged."""
         cond = self._conditions(input_dict)
         B = cond.shape[0]
         P = self.inference_net.num_params
         z = torch.randn(B * n_samples, P, device=cond.device)
-        cond_rep = cond.repeat_interleave(n_samples, dim=0)
-        out = self.inference_net.inverse(z, cond_rep)
+        if fused and hasattr(self.inference_net, "inverse_per_set"):
+            out = self.inference_net.inverse_per_set(z.view(B, n_samples, P), cond).reshape(B * n_samples, P)
+            cond_rows = lambda idx: cond[torch.div(idx, n_samples, rounding_mode="floor")]      # noqa: E731
+        else:
+            cond_rep = cond.repeat_interleave(n_samples, dim=0)
+            out = self.inference_net.inverse(z, cond_rep)
+            cond_rows = lambda idx: cond_rep[idx]                                                 # noqa: E731
         self.last_redrawn = 0
         if reject_outside is not None:
             lo, hi = (torch.as_tensor(np.asarray(v, dtype=np.float32), device=out.device) for v in reject_outside)
@@ -575,12 +633,57 @@ class AmortizedPosterior(nn.Module):
                 if idx.numel() == 0:
                     break
                 self.last_redrawn += int(idx.numel())
-                out[idx] = self.inference_net.inverse(torch.randn(idx.numel(), P, device=out.device), cond_rep[idx])
+                out[idx] = self.inference_net.inverse(torch.randn(idx.numel(), P, device=out.device), cond_rows(idx))
             out = torch.minimum(torch.maximum(torch.nan_to_num(out, nan=0.0), lo), hi)      # (what max_redraws rounds did not cure: clipped)
         out = out.reshape(B, n_samples, -1)
         if B == 1:
             out = out[0]
         return out.cpu().numpy() if to_numpy else out
+
+    @torch.no_grad()
+    def posterior_moments(self, input_dict, n_samples, box=None, z_bytes=64 << 20):
+        """Posterior mean and standard deviation of every data set from n_samples draws each, WITHOUT keeping the draws:
+        {"mean" [B, P], "sd" [B, P] (population, ddof 0, as the reference's np.var), "n_outside" [B], "n_samples"}, float64 (numpy).
+
+        box: None or a (low, high) pair of length-P sequences.  A draw is INSIDE if every component is finite and, with a box,
+        within [low, high]; the moments are over the inside draws and `n_outside` counts the others.  With box=priors.prior_box(
+        model) this is the tail-safe posterior mean (see `sample`: one draw in 1e5-1e6 of a sharply trained flow lands far outside
+        the prior): leaving the outside draws out of the mean is the same law as redrawing them.  A set with no inside draw
+        has nan moments.
+
+        On the device the sums are accumulated in float64 by the sampler itself in a fixed order (csrc/train_sample.hip:
+        bit-reproducible), whole data sets per launch, as many as keep the base normals of a launch within z_bytes.  Elsewhere
+        (a CPU, a shape the kernel does not cover) the same numbers come from the PyTorch inverse's draws, summed in float64.  The
+        base normals are torch.randn(sets * n_samples, P) per launch: those of sample() whenever one launch holds all B sets."""
+        cond = self._conditions(input_dict)
+        B, P, dev, net = cond.shape[0], self.inference_net.num_params, cond.device, self.inference_net
+        if box is not None:
+            box = tuple(torch.as_tensor(np.asarray(v, dtype=np.float32), device=dev) for v in box)
+            if box[0].shape != (P,) or box[1].shape != (P,):
+                raise ValueError(f"box must be a (low, high) pair of length-{P} sequences")
+        sums = torch.empty(B, 2 * P, dtype=torch.float64, device=dev)
+        n_out = torch.empty(B, dtype=torch.int64, device=dev)
+        per = max(1, int(z_bytes) // max(1, 4 * n_samples * P))
+        for b0 in range(0, B, per):
+            c = cond[b0:b0 + per]
+            nb = c.shape[0]
+            z = torch.randn(nb * n_samples, P, device=dev)
+            L = net._sample_lib(z.view(nb, n_samples, P), c) if hasattr(net, "_sample_lib") else None
+            if L is not None:
+                net._fused_sample(L, z.view(nb, n_samples, P), c, box=box, draws=False, moments=True, sums=sums[b0:b0 + nb],
+                                  n_outside=n_out[b0:b0 + nb])
+                continue
+            th = net.inverse(z, c.repeat_interleave(n_samples, dim=0)).reshape(nb, n_samples, P)
+            inside = torch.isfinite(th).all(dim=-1)
+            if box is not None:
+                inside &= ((th >= box[0]) & (th <= box[1])).all(dim=-1)
+            th = torch.where(inside[..., None], th.double(), torch.zeros((), dtype=torch.float64, device=dev))
+            sums[b0:b0 + nb] = torch.cat([th.sum(dim=1), (th * th).sum(dim=1)], dim=-1)
+            n_out[b0:b0 + nb] = (~inside).sum(dim=1)
+        n_in = (n_samples - n_out).double()[:, None]
+        mean = sums[:, :P] / n_in
+        sd = (sums[:, P:] / n_in - mean * mean).clamp_min(0.0).sqrt()
+        return {"mean": mean.cpu().numpy(), "sd": sd.cpu().numpy(), "n_outside": n_out.cpu().numpy(), "n_samples": int(n_samples)}
 
 
 class Trainer:
@@ -814,13 +917,13 @@ class Trainer:
         return True
 
 
-def posterior_estimates(amortizer, generative_model, configurator, n_datasets=100, n_samples=1000):
+def posterior_estimates(amortizer, generative_model, configurator, n_datasets=100, n_samples=1000, fused=False):
     """n_datasets fresh data sets, one at a time as in the reference's loop (basic_ddm_dc.py:218-223): (true parameters [n, P],
-    posterior means [n, P], posterior medians [n, P]) from n_samples posterior draws each."""
+    posterior means [n, P], posterior medians [n, P]) from n_samples posterior draws each.  fused: `AmortizedPosterior.sample`'s."""
     true, means, meds = [], [], []
     for _ in range(n_datasets):
         conf = configurator(generative_model(1))
-        post = amortizer.sample(conf, n_samples)
+        post = amortizer.sample(conf, n_samples, fused=fused)
         p = conf["parameters"]
         true.append((p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p))[0])
         means.append(post.mean(axis=0))
@@ -828,16 +931,17 @@ def posterior_estimates(amortizer, generative_model, configurator, n_datasets=10
     return np.array(true), np.array(means), np.array(meds)
 
 
-def posterior_recovery(amortizer, generative_model, configurator, n_datasets=100, n_samples=1000, statistic="mean"):
+def posterior_recovery(amortizer, generative_model, configurator, n_datasets=100, n_samples=1000, statistic="mean", fused=False):
     """The recovery loop of basic_ddm_dc.py:218-223 in miniature: posterior means vs true parameters -> per-parameter
     Pearson correlation (the reference plots R^2 / rho, pyhddmjagsutils.py:609-623).  statistic="median": the posterior median
     instead.  A sharply trained flow carries ~5e-7 of its mass at |theta| up to 1e6 (regions maximum-likelihood training never
     visits: once the inverse's intermediate vector leaves the trained range, the conditioners' log-scales flip sign and every
     remaining half-layer multiplies by e^1.9; the inverse is exact there -- DESIGN.md section 8, tools/locate_tail_draws.py), and ONE
     such draw among a data set's ten thousand moves its mean (and one such data set among hundreds the correlation) while the
-    posterior's bulk sits on the truth.  The mean is the reference's statistic and the default here."""
+    posterior's bulk sits on the truth.  The mean is the reference's statistic and the default here.  fused: `AmortizedPosterior.
+    sample`'s (`AmortizedPosterior.posterior_moments` with a box is the tail-safe mean without the draws)."""
     if statistic not in ("mean", "median"):
         raise ValueError("statistic must be 'mean' or 'median'")
-    true, means, meds = posterior_estimates(amortizer, generative_model, configurator, n_datasets, n_samples)
+    true, means, meds = posterior_estimates(amortizer, generative_model, configurator, n_datasets, n_samples, fused=fused)
     est = means if statistic == "mean" else meds
     return np.array([np.corrcoef(true[:, j], est[:, j])[0, 1] for j in range(true.shape[1])])

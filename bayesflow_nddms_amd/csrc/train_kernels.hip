@@ -17,10 +17,10 @@
 // gfx950 only.  tests/test_gpu_training.py compares with the PyTorch composition.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "train_flow.h"      // H, elu, f32x4 / f32x16, lds_barrier, RowBuf, HalfP / LayerP / FlowP, fill: shared with train_sample.hip
 
 namespace nddm_train {
 
-constexpr int H = 128;        // hidden width
 constexpr int TR = 32;        // rows per tile
 constexpr int DI_MAX = 32;    // inputs of the sub-network (x_h columns + condition columns)
 constexpr int M_MAX = 16;     // outputs (2 * transformed columns)
@@ -36,7 +36,6 @@ __device__ int g_nstamps;
 #define STAMP(id) do { } while (0)
 #endif
 
-__device__ __forceinline__ float elu(float v) { return v > 0.0f ? v : expm1f(v); }
 // ELU' from the saved PRE-activation: exp(a) itself.  (Until round 5 the forward saved the OUTPUT h and the backward took h + 1: an
 // absolute 2^-24 on a factor that can be far below 1 -- PyTorch keeps the input -- which left the activation-gradient chain at ~2 x
 // PyTorch's error against float64, tools/fused_accuracy.py.  The saved tensors h_all now hold a = W in + b; the weight-gradient kernel
@@ -55,30 +54,8 @@ __device__ __forceinline__ float elu_grad_from_pre(float a) { return a > 0.0f ? 
 // operand so that the lanes an LDS instruction serves together fall on different banks.  The NEXT half-layer's weights are
 // fetched into registers at the top of a half-layer and written to LDS once their buffers' last readers are done: a half-layer
 // is a chain of short phases, and a cold load at the head of each was 3.3 of its 8.4 microseconds (now 5.2 in all).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int LDR = H + 4;      // row stride of the [row][unit] tiles and of W2 in LDS: 16-byte aligned rows whose operand reads
                                 // (16 rows x 4 column groups per wave instruction) spread evenly over the banks
-// A barrier that orders LDS traffic only.  __syncthreads() also waits for every global load and store the thread has in flight
-// -- which is exactly what the forward's weight prefetch must not do: its loads are issued a half-layer ahead and nothing in
-// this kernel reads global memory that the kernel wrote.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// The rows [r0, r0 + rows) of a row-major global array as a RAW BUFFER of just their size: a store to a row beyond them (the rows of
-// a tile past R) is dropped by the hardware's range check -- the `if (r0 + r < R)` around every one of a phase's stores compiled
-// to a branch, an exec save / restore and a 64-bit address each.
-struct RowBuf {
-    __amdgpu_buffer_rsrc_t r;
-    __device__ __forceinline__ RowBuf(float *first_row, int rows, int ld)
-        : r(__builtin_amdgcn_make_buffer_rsrc(first_row, 0, (rows > 0 ? rows : 0) * ld * 4, 0x00020000)) {}
-    __device__ __forceinline__ void put(int off_floats, float v) const
-    { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, off_floats * 4, 0, 0); }
-};
-
-constexpr int L_MAX = 8, D_MAX = 8;
-struct HalfP { const float *W1, *b1, *W2, *b2, *W3, *b3; };
-struct LayerP { const float *scale, *bias; HalfP a, b; };
-struct FlowP { LayerP layer[L_MAX]; unsigned char perm[L_MAX][D_MAX]; };
 struct FlowDims { int L, R, D, d1, C; float clamp; };
 struct FlowSaved { float *z_all, *out_all, *s_all, *h_all; };    // [L, R, D] permuted ActNorm outputs, layer outputs, clamped
                                                                   // log-scales; [L, 4, R, H] activations of the sub-networks
@@ -707,17 +684,6 @@ int nddm_train_flow_supported(int hidden, int L, int D, int d1, int C)
     const int d2 = D - d1;
     return (hidden == H && L >= 1 && L <= L_MAX && D >= 2 && D <= D_MAX && d1 >= 1 && d2 >= 1 && d1 + C <= DI_MAX && d2 + C <= DI_MAX
             && C >= 1 && 2 * d1 <= M_MAX && 2 * d2 <= M_MAX) ? 1 : 0;
-}
-
-/* params: L x 14 device pointers per layer -- ActNorm log-scale [D] and bias [D], then W1 [H, Dh + C], b1 [H], W2 [H, H], b2 [H],
- * W3 [2 Dt, H], b3 [2 Dt] of sub-network 1 (conditioned on the first d1 columns) and of sub-network 2; perm: L x D host ints. */
-static void fill(FlowP &P, int L, int D, const void *const *params, const int *perm)
-{
-    for (int l = 0; l < L; ++l) {
-        const float *const *q = reinterpret_cast<const float *const *>(params) + 14 * l;
-        P.layer[l] = {q[0], q[1], {q[2], q[3], q[4], q[5], q[6], q[7]}, {q[8], q[9], q[10], q[11], q[12], q[13]}};
-        for (int d = 0; d < D; ++d) P.perm[l][d] = (unsigned char)perm[l * D + d];
-    }
 }
 
 /* -> z = out_all[L - 1] and ld [R] (log|det|, ActNorm terms included); z_all / out_all / s_all [L, R, D] and h_all [L, 4, R, H] (the PRE-activations of the coupling nets' two hidden layers)
