@@ -11,6 +11,9 @@
 // ~150 launches per training iteration.  Here the [rows, 64] x [64, 64] products are v_mfma_f32_32x32x2_f32 (exact f32: a k-ordered
 // fmaf chain) on LDS tiles of 64 rows; a workgroup owns up to `rows_per_wg` consecutive trials of ONE set, so pooling and context
 // never cross a workgroup inside a kernel -- they cross KERNELS as [set, workgroup-of-the-set, 64] partial sums.
+// Every step of a layer is written ONCE ("the forward steps", "the backward steps"); the four kernels are sequences of those calls, so the
+// kernels that run two MLPs in one launch write what two launches of the single kernels write, bit for bit
+// (tests/test_gpu_deepset_pairs.py).
 // gfx950 only.  tests/test_gpu_training.py compares with the PyTorch composition.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +25,8 @@ constexpr int LD = HS + 4;    // LDS row stride: 16-byte aligned rows, and the o
 constexpr int TM = 64;        // rows per tile
 constexpr int NT = 256;       // threads per workgroup: wave w owns the 32 x 32 tile (w >> 1, w & 1) of every 64 x 64 product
 constexpr int DS_MAX = 4;     // a "small" input (the raw trials: rt, choice) goes through layer 1 as plain FMAs
+constexpr int NQ = HS * HS / 4 / NT;      // 16-byte pieces per thread of a [64][64] tile (of weights, or of TM == HS rows)
+static_assert(TM == HS, "a row tile and a weight matrix are staged by the same pair of functions");
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));      // (register arrays of HIP's float4 STRUCT were seen kept in memory; of this type not)
 
@@ -50,6 +55,22 @@ struct Common {
     int d_out;                              // rows of W3 / b3 (<= 64): 64 for the per-trial MLPs, the summary width for the last MLP
     const float *x_part; int S_x;           // not null (d_in == 64): row r of x IS inv_n * sum over s of x_part[r][s][.] -- the MLP
 };                                          // after the pooling runs on the pooled means, one row per set (launched as ONE "set" of B rows)
+
+// What a thread is in the workgroup.  Of a 64 x 64 product: wave w owns the 32 x 32 tile (rb, ub), the lane holds row / column m of
+// the operands for the 32 k's of half kk, and column u of every result tile.  Of a per-column pass: unit uu, rows 16 rg ...
+struct Lane {
+    int t, lane, wave, m, kk, rb, ub, u, uu, rg;
+    __device__ __forceinline__ Lane()
+        : t(threadIdx.x), lane(t & 63), wave(t >> 6), m(lane & 31), kk(lane >> 5), rb(wave >> 1), ub(wave & 1), u(32 * ub + m), uu(t & 63), rg(t >> 6) {}
+};
+// What the workgroup owns: trials [n_begin, n_end) of set b, as the set's workgroup sp (wg: its row of every [B, S, .] array)
+struct Span {
+    int b, sp, n_begin, n_end, wg;
+    long long row0;                         // the set's first row of every [B * N, .] array
+    __device__ __forceinline__ Span(const Common &C)
+        : b(blockIdx.x / C.S), sp(blockIdx.x - b * C.S), n_begin(sp * C.rows_per_wg), n_end(min(C.N, n_begin + C.rows_per_wg)), wg(blockIdx.x),
+          row0((long long)b * C.N) {}
+};
 
 // acc += A B over 64 k's.  Lane l holds A[i = l & 31][k] and B[k][j = l & 31] for the 32 k's of its half (l >> 5): the order of
 // the sum is free, so step s of the instruction stream takes k = 32 (l >> 5) + s from both.  SA / SB: distance in floats between
@@ -93,42 +114,36 @@ __device__ __forceinline__ f32x16 zero16()
     return z;
 }
 
-// [rows <= 64] x 64 row-major weights -> LDS [64][LD] (rows beyond: zero), 16-byte loads (ldw: the source's row stride in floats,
-// a multiple of 4)
-__device__ __forceinline__ void stage64(float (*dst)[LD], const float *src, int ldw, int t, int rows = HS)
-{
-    float4 v[HS * HS / 4 / NT];
-#pragma unroll                                       // all loads first (from a clamped row: no branch), then the stores
-    for (int k = 0; k < HS * HS / 4 / NT; ++k) {
-        const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-        v[k] = *reinterpret_cast<const float4 *>(src + (long long)min(r, rows - 1) * ldw + 4 * c4);
-    }
-#pragma unroll
-    for (int k = 0; k < HS * HS / 4 / NT; ++k) {
-        const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-        *reinterpret_cast<float4 *>(&dst[r][4 * c4]) = r < rows ? v[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-}
-
-// the same in two halves: the loads into registers now, the stores to LDS when the buffer's last readers are done / its first reader
-// is about to run -- a kernel that issues EVERY load up front and stores each operand just before the phase that needs it exposes
-// one load latency instead of one per operand
-__device__ __forceinline__ void fetch64(f32x4 (&v)[HS * HS / 4 / NT], const float *src, int ldw, int t, int rows = HS)
+// [rows <= 64] x 64 of a row-major array (ldw: its row stride in floats, a multiple of 4) -> LDS [64][LD] (rows beyond: zero),
+// 16-byte loads, in two halves: the loads into registers now (from a clamped row: no branch), the stores to LDS when the buffer's
+// last readers are done / its first reader is about to run -- a kernel that issues EVERY load up front and stores each operand just
+// before the phase that needs it exposes one load latency instead of one per operand
+__device__ __forceinline__ void fetch64(f32x4 (&v)[NQ], const float *src, int ldw, int t, int rows = HS)
 {
 #pragma unroll
-    for (int k = 0; k < HS * HS / 4 / NT; ++k) {
+    for (int k = 0; k < NQ; ++k) {
         const int p = t + NT * k, r = p >> 4, c4 = p & 15;
         v[k] = *reinterpret_cast<const f32x4 *>(src + (long long)min(r, rows - 1) * ldw + 4 * c4);
     }
 }
-__device__ __forceinline__ void store64(float (*dst)[LD], const f32x4 (&v)[HS * HS / 4 / NT], int t, int rows = HS)
+__device__ __forceinline__ void store64(float (*dst)[LD], const f32x4 (&v)[NQ], int t, int rows = HS)
 {
     const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int k = 0; k < HS * HS / 4 / NT; ++k) {
+    for (int k = 0; k < NQ; ++k) {
         const int p = t + NT * k, r = p >> 4, c4 = p & 15;
         *reinterpret_cast<f32x4 *>(&dst[r][4 * c4]) = r < rows ? v[k] : z;
     }
+}
+// the same pair for the tile of rows n0 .. n0 + 63 of the workgroup's set in a [B * N, 64] array (saved activations, an input, a
+// gradient): rows beyond the workgroup's range are fetched from its last row and zeroed at the store
+__device__ __forceinline__ void fetch_tile(f32x4 (&v)[NQ], const float *src, const Span &W, int n0, int t)
+{
+    fetch64(v, src + (W.row0 + n0) * HS, HS, t, W.n_end - n0);
+}
+__device__ __forceinline__ void store_tile(float (*dst)[LD], const f32x4 (&v)[NQ], const Span &W, int n0, int t)
+{
+    store64(dst, v, t, W.n_end - n0);
 }
 
 // sum over s = 0 .. S - 1 of p[s * stride], added in that order -- with the loads of eight terms in flight at a time: as a plain loop
@@ -163,6 +178,28 @@ __device__ __forceinline__ float4 x_row4(const Common &C, long long row, int c4,
     }
     a.x *= inv_n; a.y *= inv_n; a.z *= inv_n; a.w *= inv_n;
     return a;
+}
+// fetch_tile of a 64-wide input (store_tile stores it)
+__device__ __forceinline__ void fetch_x_tile(f32x4 (&v)[NQ], const Common &C, const Span &W, int n0, float inv_n, int t)
+{
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+        const int p = t + NT * k, r = p >> 4, c4 = p & 15;
+        const float4 xv = x_row4(C, W.row0 + min(n0 + r, W.n_end - 1), c4, inv_n);       // (clamped: rows beyond the range are zeroed at the store)
+        v[k] = f32x4{xv.x, xv.y, xv.z, xv.w};
+    }
+}
+// the tile of a small input, and the columns of W1 that act on it, straight to LDS (rows beyond the workgroup's range: zero)
+__device__ __forceinline__ void fill_xsmall(float (*xsmall)[DS_MAX], const Common &C, const Span &W, int n0, int t)
+{
+    for (int p = t; p < TM * C.d_in; p += NT) {
+        const int r = p / C.d_in, c = p - r * C.d_in, n = n0 + r;
+        xsmall[r][c] = n < W.n_end ? C.x[(W.row0 + n) * C.d_in + c] : 0.0f;
+    }
+}
+__device__ __forceinline__ void fill_w1small(float (*w1small)[DS_MAX], const Common &C, int t)
+{
+    for (int p = t; p < HS * C.d_in; p += NT) { const int r = p / C.d_in, c = p - r * C.d_in; w1small[r][c] = C.P.W1[(long long)r * C.P.ldw1 + c]; }
 }
 
 __device__ __forceinline__ float inv_count(const Common &C)
@@ -244,6 +281,55 @@ __device__ __forceinline__ void context(const Common &C, int b, float *pooled, f
     context_product(C, pooled, cs, t, L);
 }
 
+// ---- the forward steps
+// this wave's 32 x 32 tile of in W^T: a tile of rows against a weight matrix [unit out][unit in], both in LDS
+__device__ __forceinline__ f32x16 fwd_product(const float (*in)[LD], const float (*w)[LD], const Lane &L)
+{
+    return mma64<1, 1>(&in[32 * L.rb + L.m][32 * L.kk], &w[L.u][32 * L.kk], zero16());
+}
+// a hidden layer: out = ReLU(in W^T + bias), to LDS (the next layer's input) and to global memory (saved for the backward; rows
+// beyond the tile's valid ones are dropped by g's range check)
+__device__ __forceinline__ void relu_layer(const float (*in)[LD], const float (*w)[LD], float bias, float (*out)[LD], const RowTile &g, const Lane &L)
+{
+    const f32x16 acc = fwd_product(in, w, L);
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const int r = 32 * L.rb + drow(v, L.kk);
+        const float val = fmaxf(acc[v] + bias, 0.0f);
+        out[r][L.u] = val;
+        g.put(r, L.u, val);
+    }
+}
+// the first hidden layer of a small input as plain FMAs (cs: bias and context): thread (unit t & 63, rows 16 (t >> 6) ...)
+__device__ __forceinline__ void small_layer1(const float (*xsmall)[DS_MAX], const float (*w1small)[DS_MAX], const float *cs, int d_in,
+                                             float (*out)[LD], const RowTile &g, const Lane &L)
+{
+    float w[DS_MAX];
+#pragma unroll
+    for (int c = 0; c < DS_MAX; ++c) w[c] = c < d_in ? w1small[L.uu][c] : 0.0f;
+    const float c0 = cs[L.uu];
+#pragma unroll 4
+    for (int q = 0; q < 16; ++q) {
+        const int r = 16 * L.rg + q;
+        float a = c0;
+#pragma unroll
+        for (int c = 0; c < DS_MAX; ++c) if (c < d_in) a = fmaf(w[c], xsmall[r][c], a);
+        const float val = fmaxf(a, 0.0f);
+        out[r][L.uu] = val;
+        g.put(r, L.uu, val);
+    }
+}
+// the masked sums of an output over the workgroup's trials: the fixed-order sum of the four lanes that share a column
+__device__ __forceinline__ void pooled_sum(float (*red)[64], float pacc, float *pool_row, const Lane &L)
+{
+    red[L.wave][L.lane] = pacc;
+    __syncthreads();
+    if (L.t < HS) {
+        const int cb = L.t >> 5, n = L.t & 31;
+        pool_row[L.t] = (red[cb][n] + red[cb][n + 32]) + (red[2 + cb][n] + red[2 + cb][n + 32]);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ forward
 struct FwdOut {
     float *h1, *h2;        // [B * N, 64] the two hidden activations (after their ReLU): saved for the backward
@@ -265,136 +351,70 @@ __global__ __launch_bounds__(NT) void mlp_fwd_kernel(Common C, FwdOut O)
     __shared__ __attribute__((aligned(16))) float h2s[TM][LD];
     __shared__ float w1small[BIG ? 1 : HS][DS_MAX], xsmall[BIG ? 1 : TM][DS_MAX];
     __shared__ float cs[HS], pooled[HS], red[4][64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, m = lane & 31, kk = lane >> 5, rb = wave >> 1, ub = wave & 1;
-    const int b = blockIdx.x / C.S, sp = blockIdx.x - b * C.S;
-    const int n_begin = sp * C.rows_per_wg, n_end = min(C.N, n_begin + C.rows_per_wg);
-    const long long row0 = (long long)b * C.N;
+    const Lane L;
+    const Span W(C);
+    const int t = L.t, u = L.u, n_begin = W.n_begin, n_end = W.n_end;
     STAMP(100);
     const float inv_n = inv_count(C);
-    auto load_x_tile = [&](const int n0) {           // rows beyond the workgroup's range: zero
-        if (BIG) {
-#pragma unroll
-            for (int k = 0; k < TM * HS / 4 / NT; ++k) {
-                const int p = t + NT * k, r = p >> 4, c4 = p & 15, n = n0 + r;
-                float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (n < n_end) v = x_row4(C, row0 + n, c4, inv_n);
-                *reinterpret_cast<float4 *>(&xs[r][4 * c4]) = v;
-            }
-        } else {
-            for (int p = t; p < TM * C.d_in; p += NT) {
-                const int r = p / C.d_in, c = p - r * C.d_in, n = n0 + r;
-                xsmall[r][c] = n < n_end ? C.x[(row0 + n) * C.d_in + c] : 0.0f;
-            }
-        }
-    };
     // every global load first: W1 (needed first), W2, W3 into registers; W2 and W3 go to LDS behind layers 1 and 2 (the barriers
     // that are there anyway), so their latency runs beside the input tile's, the context's and layer 1
     // (the loads complete in issue order: the input tile and W1 first, they are stored first)
-    f32x4 r1[HS * HS / 4 / NT], r2[HS * HS / 4 / NT], r3[HS * HS / 4 / NT];
-    float4 rx[TM * HS / 4 / NT];
-    if (BIG) {
-#pragma unroll
-        for (int k = 0; k < TM * HS / 4 / NT; ++k) {
-            const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-            rx[k] = x_row4(C, row0 + min(n_begin + r, n_end - 1), c4, inv_n);       // (clamped: rows beyond the range are zeroed at the store)
-        }
-    } else load_x_tile(n_begin);
+    f32x4 r1[NQ], r2[NQ], r3[NQ], rx[NQ];
+    if (BIG) fetch_x_tile(rx, C, W, n_begin, inv_n, t);
+    else fill_xsmall(xsmall, C, W, n_begin, t);
     fetch64(r1, BIG ? C.P.W1 : C.P.W2, BIG ? C.P.ldw1 : HS, t);
     fetch64(r2, C.P.W2, HS, t);
     fetch64(r3, C.P.W3, HS, t, C.d_out);
     if (BIG) {
-#pragma unroll
-        for (int k = 0; k < TM * HS / 4 / NT; ++k) {
-            const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-            *reinterpret_cast<float4 *>(&xs[r][4 * c4]) = n_begin + r < n_end ? rx[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
+        store_tile(xs, rx, W, n_begin, t);
         store64(w1s, r1, t);
-    } else
-        for (int p = t; p < HS * C.d_in; p += NT) { const int r = p / C.d_in, c = p - r * C.d_in; w1small[r][c] = C.P.W1[(long long)r * C.P.ldw1 + c]; }
-    context(C, b, pooled, cs, t);
+    } else fill_w1small(w1small, C, t);
+    context(C, W.b, pooled, cs, t);
     __syncthreads();
-    const int u = 32 * ub + m;                       // this lane's column of every result tile
     const float bias2 = C.P.b2[u], bias3 = u < C.d_out ? C.P.b3[u] : 0.0f, bias1 = cs[u];
     float pacc = 0.0f;
     STAMP(101);
     for (int n0 = n_begin; n0 < n_end; n0 += TM) {
         if (n0 != n_begin) {
-            load_x_tile(n0);
+            if (BIG) {
+                fetch_x_tile(rx, C, W, n0, inv_n, t);
+                store_tile(xs, rx, W, n0, t);
+            } else fill_xsmall(xsmall, C, W, n0, t);
             __syncthreads();
         }
         STAMP(102);
-        const RowTile th1(O.h1 + (row0 + n0) * HS, n_end - n0), th2(O.h2 + (row0 + n0) * HS, n_end - n0);
-        if (BIG) {                                   // layer 1
-            const f32x16 acc = mma64<1, 1>(&xs[32 * rb + m][32 * kk], &w1s[u][32 * kk], zero16());
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int r = 32 * rb + drow(v, kk);
-                const float val = fmaxf(acc[v] + bias1, 0.0f);
-                h1s[r][u] = val;
-                th1.put(r, u, val);
-            }
-        } else {                                     // thread (unit t & 63, rows 16 (t >> 6) ...)
-            const int uu = t & 63, rg = t >> 6;
-            float w[DS_MAX];
-#pragma unroll
-            for (int c = 0; c < DS_MAX; ++c) w[c] = c < C.d_in ? w1small[uu][c] : 0.0f;
-            const float c0 = cs[uu];
-#pragma unroll 4
-            for (int q = 0; q < 16; ++q) {
-                const int r = 16 * rg + q;
-                float a = c0;
-#pragma unroll
-                for (int c = 0; c < DS_MAX; ++c) if (c < C.d_in) a = fmaf(w[c], xsmall[r][c], a);
-                const float val = fmaxf(a, 0.0f);
-                h1s[r][uu] = val;
-                th1.put(r, uu, val);
-            }
-        }
+        const RowTile th1(O.h1 + (W.row0 + n0) * HS, n_end - n0), th2(O.h2 + (W.row0 + n0) * HS, n_end - n0);
+        if (BIG) relu_layer(xs, w1s, bias1, h1s, th1, L);                   // layer 1
+        else small_layer1(xsmall, w1small, cs, C.d_in, h1s, th1, L);
         if (n0 == n_begin) store64(w2s, r2, t);      // (its first reader is layer 2, behind the barrier)
         __syncthreads();
         STAMP(103);
-        {                                            // layer 2
-            const f32x16 acc = mma64<1, 1>(&h1s[32 * rb + m][32 * kk], &w2s[u][32 * kk], zero16());
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int r = 32 * rb + drow(v, kk);
-                const float val = fmaxf(acc[v] + bias2, 0.0f);
-                h2s[r][u] = val;
-                th2.put(r, u, val);
-            }
-        }
+        relu_layer(h1s, w2s, bias2, h2s, th2, L);    // layer 2
         if (n0 == n_begin) store64(w3s, r3, t, C.d_out);
         __syncthreads();
         STAMP(104);
         {                                            // layer 3 (no activation), and the masked sums of its output
-            const f32x16 acc = mma64<1, 1>(&h2s[32 * rb + m][32 * kk], &w3s[u][32 * kk], zero16());
+            const f32x16 acc = fwd_product(h2s, w3s, L);
             // (branch-free: y as a raw buffer of the tile's valid rows -- of NO rows if y is not wanted -- whose range check drops the
             //  stores of the other rows; a lane whose column is not written aims past the buffer; the pooled sum takes a zero mask)
-            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(O.y ? O.y + (row0 + n0) * O.ldy : O.h1, 0,
+            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(O.y ? O.y + (W.row0 + n0) * O.ldy : O.h1, 0,
                                                                                   O.y ? (n_end - n0) * O.ldy * 4 : 0, 0x00020000);
             const bool colv = u < C.d_out, cole = O.extra && !colv && u < C.d_out + O.n_extra;
             const int ue = min(max(u - C.d_out, 0), max(O.n_extra - 1, 0));
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int r = 32 * rb + drow(v, kk), n = n0 + r;
+                const int r = 32 * L.rb + drow(v, L.kk), n = n0 + r;
                 const float val = acc[v] + bias3;
                 if (O.pool_part) pacc = fmaf(colv ? mask_or_zero(C, n, n_end) : 0.0f, val, pacc);
                 float outv = val;
-                if (O.extra) { const float e = O.extra[(row0 + min(n, n_end - 1)) * O.extra_stride + ue]; outv = cole ? e : val; }
+                if (O.extra) { const float e = O.extra[(W.row0 + min(n, n_end - 1)) * O.extra_stride + ue]; outv = cole ? e : val; }
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, outv), ry, (colv || cole) ? (r * O.ldy + u) * 4 : 0x7ffffff0, 0, 0);
             }
         }
         STAMP(105);
         // (the next tile's writes to xs / h1s / h2s are each behind a barrier every reader of this tile has passed)
     }
-    if (O.pool_part) {                               // fixed-order sum of the four lanes that share a column
-        red[wave][lane] = pacc;
-        __syncthreads();
-        if (t < HS) {
-            const int cb = t >> 5, n = t & 31;
-            O.pool_part[((long long)b * C.S + sp) * HS + t] = (red[cb][n] + red[cb][n + 32]) + (red[2 + cb][n] + red[2 + cb][n + 32]);
-        }
-    }
+    if (O.pool_part) pooled_sum(red, pacc, O.pool_part + (long long)W.wg * HS, L);
 }
 
 // ---- two MLPs in one launch --------------------------------------------------------------------------------------------------
@@ -414,97 +434,46 @@ __global__ __launch_bounds__(NT) void mlp2_fwd_kernel(Common C, FwdOut O, Mlp P2
     __shared__ __attribute__((aligned(16))) float h2s[TM][LD];
     __shared__ float w1small[BIG ? 1 : HS][DS_MAX], xsmall[BIG ? 1 : TM][DS_MAX];
     __shared__ float cs[HS], pooled[HS], red[4][64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, m = lane & 31, kk = lane >> 5, rb = wave >> 1, ub = wave & 1;
-    const int b = blockIdx.x / C.S, sp = blockIdx.x - b * C.S;
-    const int n0 = sp * C.rows_per_wg, n_end = min(C.N, n0 + C.rows_per_wg);
-    const long long row0 = (long long)b * C.N;
+    const Lane L;
+    const Span W(C);
+    const int t = L.t, u = L.u, n0 = W.n_begin, n_end = W.n_end;
     const float inv_n = inv_count(C);
     // ---- every global load up front, in the order of need: A's input tile and W1 (stored at once), A's W2 and W3 (stored behind
     //      A's layers 1 and 2), B's three matrices (stored when A is done)
-    f32x4 r1[HS * HS / 4 / NT], r2[HS * HS / 4 / NT], r3[HS * HS / 4 / NT];
-    float4 rx[TM * HS / 4 / NT];
-    if (BIG) {
-#pragma unroll
-        for (int k = 0; k < TM * HS / 4 / NT; ++k) {
-            const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-            rx[k] = x_row4(C, row0 + min(n0 + r, n_end - 1), c4, inv_n);
-        }
-    } else {
-        for (int p = t; p < TM * C.d_in; p += NT) {
-            const int r = p / C.d_in, c = p - r * C.d_in, n = n0 + r;
-            xsmall[r][c] = n < n_end ? C.x[(row0 + n) * C.d_in + c] : 0.0f;
-        }
-    }
+    f32x4 r1[NQ], r2[NQ], r3[NQ], rx[NQ];
+    if (BIG) fetch_x_tile(rx, C, W, n0, inv_n, t);
+    else fill_xsmall(xsmall, C, W, n0, t);
     fetch64(r1, BIG ? C.P.W1 : C.P.W2, BIG ? C.P.ldw1 : HS, t);
     fetch64(r2, C.P.W2, HS, t);
     fetch64(r3, C.P.W3, HS, t);
-    f32x4 q1[HS * HS / 4 / NT], q2[HS * HS / 4 / NT], q3[HS * HS / 4 / NT];
+    f32x4 q1[NQ], q2[NQ], q3[NQ];
     fetch64(q1, P2.W1, HS, t);
     fetch64(q2, P2.W2, HS, t);
     fetch64(q3, P2.W3, HS, t);
     if (BIG) {
-#pragma unroll
-        for (int k = 0; k < TM * HS / 4 / NT; ++k) {
-            const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-            *reinterpret_cast<float4 *>(&xs[r][4 * c4]) = n0 + r < n_end ? rx[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
+        store_tile(xs, rx, W, n0, t);
         store64(w1s, r1, t);
-    } else
-        for (int p = t; p < HS * C.d_in; p += NT) { const int r = p / C.d_in, c = p - r * C.d_in; w1small[r][c] = C.P.W1[(long long)r * C.P.ldw1 + c]; }
-    context(C, b, pooled, cs, t);
+    } else fill_w1small(w1small, C, t);
+    context(C, W.b, pooled, cs, t);
     __syncthreads();
-    const int u = 32 * ub + m;                       // this lane's column of every result tile
     const float bias2 = C.P.b2[u], bias3 = C.P.b3[u], bias1 = cs[u];
     const float c1 = P2.b1[u], c2 = P2.b2[u], c3 = P2.b3[u];
     const int nv = n_end - n0;                       // the tile's valid rows: stores beyond them are dropped by the buffers' range check
-    const RowTile th1(O.h1 + (row0 + n0) * HS, nv), th2(O.h2 + (row0 + n0) * HS, nv), ty(O.y + (row0 + n0) * HS, nv);
-    const RowTile tg1(O2.h1 + (row0 + n0) * HS, nv), tg2(O2.h2 + (row0 + n0) * HS, nv);
+    const RowTile th1(O.h1 + (W.row0 + n0) * HS, nv), th2(O.h2 + (W.row0 + n0) * HS, nv), ty(O.y + (W.row0 + n0) * HS, nv);
+    const RowTile tg1(O2.h1 + (W.row0 + n0) * HS, nv), tg2(O2.h2 + (W.row0 + n0) * HS, nv);
     // ---- MLP A
-    if (BIG) {
-        const f32x16 acc = mma64<1, 1>(&xs[32 * rb + m][32 * kk], &w1s[u][32 * kk], zero16());
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int r = 32 * rb + drow(v, kk);
-            const float val = fmaxf(acc[v] + bias1, 0.0f);
-            h1s[r][u] = val;
-            th1.put(r, u, val);
-        }
-    } else {
-        const int uu = t & 63, rg = t >> 6;
-        float w[DS_MAX];
-#pragma unroll
-        for (int c = 0; c < DS_MAX; ++c) w[c] = c < C.d_in ? w1small[uu][c] : 0.0f;
-        const float c0 = cs[uu];
-#pragma unroll 4
-        for (int q = 0; q < 16; ++q) {
-            const int r = 16 * rg + q;
-            float a = c0;
-#pragma unroll
-            for (int c = 0; c < DS_MAX; ++c) if (c < C.d_in) a = fmaf(w[c], xsmall[r][c], a);
-            const float val = fmaxf(a, 0.0f);
-            h1s[r][uu] = val;
-            th1.put(r, uu, val);
-        }
-    }
+    if (BIG) relu_layer(xs, w1s, bias1, h1s, th1, L);
+    else small_layer1(xsmall, w1small, cs, C.d_in, h1s, th1, L);
     store64(w2s, r2, t);
     __syncthreads();
-    {
-        const f32x16 acc = mma64<1, 1>(&h1s[32 * rb + m][32 * kk], &w2s[u][32 * kk], zero16());
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int r = 32 * rb + drow(v, kk);
-            const float val = fmaxf(acc[v] + bias2, 0.0f);
-            h2s[r][u] = val;
-            th2.put(r, u, val);
-        }
-    }
+    relu_layer(h1s, w2s, bias2, h2s, th2, L);
     store64(w3s, r3, t);
     __syncthreads();
     {   // A's output: to global memory (the next equivariant MLP and the backward read it) and into xs as B's input
-        const f32x16 acc = mma64<1, 1>(&h2s[32 * rb + m][32 * kk], &w3s[u][32 * kk], zero16());
+        const f32x16 acc = fwd_product(h2s, w3s, L);
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const int r = 32 * rb + drow(v, kk), n = n0 + r;
+            const int r = 32 * L.rb + drow(v, L.kk), n = n0 + r;
             const float val = n < n_end ? acc[v] + bias3 : 0.0f;          // (rows beyond the set: zero, as a loaded tile has them)
             xs[r][u] = val;                                               // (xs: A's layer 1 finished reading it two barriers ago)
             ty.put(r, u, val);
@@ -516,43 +485,20 @@ __global__ __launch_bounds__(NT) void mlp2_fwd_kernel(Common C, FwdOut O, Mlp P2
     store64(w3s, q3, t);
     __syncthreads();
     // ---- MLP B
-    {
-        const f32x16 acc = mma64<1, 1>(&xs[32 * rb + m][32 * kk], &w1s[u][32 * kk], zero16());
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int r = 32 * rb + drow(v, kk);
-            const float val = fmaxf(acc[v] + c1, 0.0f);
-            h1s[r][u] = val;
-            tg1.put(r, u, val);
-        }
-    }
+    relu_layer(xs, w1s, c1, h1s, tg1, L);
     __syncthreads();
-    {
-        const f32x16 acc = mma64<1, 1>(&h1s[32 * rb + m][32 * kk], &w2s[u][32 * kk], zero16());
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int r = 32 * rb + drow(v, kk);
-            const float val = fmaxf(acc[v] + c2, 0.0f);
-            h2s[r][u] = val;
-            tg2.put(r, u, val);
-        }
-    }
+    relu_layer(h1s, w2s, c2, h2s, tg2, L);
     __syncthreads();
     float pacc = 0.0f;
     {
-        const f32x16 acc = mma64<1, 1>(&h2s[32 * rb + m][32 * kk], &w3s[u][32 * kk], zero16());
+        const f32x16 acc = fwd_product(h2s, w3s, L);
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const int n = n0 + 32 * rb + drow(v, kk);
+            const int n = n0 + 32 * L.rb + drow(v, L.kk);
             pacc = fmaf(mask_or_zero(C, n, n_end), acc[v] + c3, pacc);
         }
     }
-    red[wave][lane] = pacc;                          // fixed-order sum of the four lanes that share a column (as mlp_fwd_kernel)
-    __syncthreads();
-    if (t < HS) {
-        const int cb = t >> 5, n = t & 31;
-        O2.pool_part[((long long)b * C.S + sp) * HS + t] = (red[cb][n] + red[cb][n + 32]) + (red[2 + cb][n] + red[2 + cb][n + 32]);
-    }
+    pooled_sum(red, pacc, O2.pool_part + (long long)W.wg * HS, L);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -577,6 +523,98 @@ __device__ __forceinline__ void gp_product(const float *dsum, float *gp, float i
     if (q == 0) gp[k] = a * inv_n;
 }
 
+// ---- the backward steps.  g: d(pre-activation) of a layer's output, h: the layer's input, both tiles in LDS
+// what a thread accumulates of one MLP's weight gradients: its registers of the three products g^T h (tile (rb, ub): row = unit out,
+// column = unit in), and as thread (unit t & 63, rows 16 (t >> 6) ..) the column sums of d(pre-activation 1..3) and (a small
+// input) row t & 63 of dW1 over the same rows
+struct Grads {
+    f32x16 aW1, aW2, aW3;
+    float db[3], dw1[DS_MAX];
+    __device__ __forceinline__ Grads() : aW1(zero16()), aW2(zero16()), aW3(zero16()), db{0.0f, 0.0f, 0.0f}, dw1{0.0f, 0.0f, 0.0f, 0.0f} {}
+};
+// dW [unit out, unit in] += g^T h (the k's are the tile's rows)
+__device__ __forceinline__ f32x16 wgrad(const float (*g)[LD], const float (*h)[LD], f32x16 aW, const Lane &L)
+{
+    return mma64<LD, LD>(&g[32 * L.kk][32 * L.rb + L.m], &h[32 * L.kk][L.u], aW);
+}
+// db += the column sums of g
+__device__ __forceinline__ void bias_grad(const float (*g)[LD], float &db, const Lane &L)
+{
+#pragma unroll 8
+    for (int q = 0; q < 16; ++q) db += g[16 * L.rg + q][L.uu];
+}
+// d h = g W (w [unit out][unit in])
+__device__ __forceinline__ f32x16 dgrad(const float (*g)[LD], const float (*w)[LD], const Lane &L)
+{
+    return mma64<1, LD>(&g[32 * L.rb + L.m][32 * L.kk], &w[32 * L.kk][L.u], zero16());
+}
+// a hidden layer, whose input h is the ReLU output of the layer before: dW, db, and out = that layer's d(pre-activation).
+// (out is never a tile this step reads: every reader of its old content finished before the barrier in front of the step)
+__device__ __forceinline__ void bwd_layer(const float (*g)[LD], const float (*h)[LD], const float (*w)[LD], float (*out)[LD], f32x16 &aW, float &db,
+                                          const Lane &L)
+{
+    aW = wgrad(g, h, aW, L);
+    bias_grad(g, db, L);
+    const f32x16 acc = dgrad(g, w, L);
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const int r = 32 * L.rb + drow(v, L.kk);
+        out[r][L.u] = h[r][L.u] > 0.0f ? acc[v] : 0.0f;
+    }
+}
+// dW1 of a small input as plain FMAs, g = d(pre-activation 1)
+__device__ __forceinline__ void small_dw1(const float (*g)[LD], const float (*xsmall)[DS_MAX], int d_in, float (&dw1)[DS_MAX], const Lane &L)
+{
+#pragma unroll 4
+    for (int q = 0; q < 16; ++q) {
+        const float d = g[16 * L.rg + q][L.uu];
+#pragma unroll
+        for (int c = 0; c < DS_MAX; ++c) if (c < d_in) dw1[c] = fmaf(d, xsmall[16 * L.rg + q][c], dw1[c]);
+    }
+}
+// this workgroup's partial sums of one MLP's weight gradients -> wp (its row of wpart: W1 [64, ld1], b1, W2, b2, W3 [d_out, 64], b3).
+// dctx_part: not null: the column sums of d(pre-activation 1) also go to this workgroup's row of it; ctx_cols: W1 has context columns
+// [d_in, d_in + 64), whose gradient is those sums x pooled.  (Behind its first barrier every reader of the MLP's tiles is done.)
+template <bool BIG>
+__device__ __forceinline__ void wgrad_epilogue(float *wp, int ld1, int d_in, int d_out, const Grads &G, float (*red)[3][HS], float (*redw)[HS][DS_MAX],
+                                               float *db1s, float *dctx_part, bool ctx_cols, const float *pooled, const Span &W, const Lane &L)
+{
+    const int t = L.t, oW1 = 0, ob1 = HS * ld1, oW2 = ob1 + HS, ob2 = oW2 + HS * HS, oW3 = ob2 + HS, ob3 = oW3 + d_out * HS;
+    const RowTile tw3(wp + oW3, d_out);
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {                   // tile (rb, ub): row = unit out, column = unit in
+        const int r = 32 * L.rb + drow(v, L.kk);
+        wp[oW2 + r * HS + L.u] = G.aW2[v];
+        tw3.put(r, L.u, G.aW3[v]);                   // (rows >= d_out: dropped)
+        if (BIG) wp[oW1 + r * ld1 + L.u] = G.aW1[v];
+    }
+#pragma unroll
+    for (int l = 0; l < 3; ++l) red[L.rg][l][L.uu] = G.db[l];
+    if (!BIG) {
+#pragma unroll
+        for (int c = 0; c < DS_MAX; ++c) redw[L.rg][L.uu][c] = G.dw1[c];
+    }
+    __syncthreads();
+    if (t < 3 * HS) {
+        const int l = t >> 6, c = t & 63;
+        const float v = (red[0][l][c] + red[1][l][c]) + (red[2][l][c] + red[3][l][c]);
+        if (l < 2 || c < d_out) wp[l == 0 ? ob1 + c : (l == 1 ? ob2 + c : ob3 + c)] = v;
+        if (l == 0) {
+            db1s[c] = v;
+            if (dctx_part) dctx_part[(long long)W.wg * HS + c] = v;
+        }
+    }
+    if (!BIG && t < HS)
+        for (int c = 0; c < d_in; ++c) wp[oW1 + t * ld1 + c] = (redw[0][t][c] + redw[1][t][c]) + (redw[2][t][c] + redw[3][t][c]);
+    if (ctx_cols) {                                  // context columns of W1: (sum of d pre-activation 1) x pooled
+        __syncthreads();
+        for (int p = t; p < HS * HS; p += NT) {
+            const int r = p >> 6, k = p & 63;
+            wp[oW1 + r * ld1 + d_in + k] = db1s[r] * pooled[k];
+        }
+    }
+}
+
 struct BwdIO {
     const float *h1, *h2;            // saved by the forward
     const float *gy; int ldgy;       // [B * N, ldgy] gradient of the output (columns [0, d_out)), or null
@@ -589,6 +627,24 @@ struct BwdIO {
     float *wpart; int ld_part;       // row blockIdx.x (stride ld_part floats) takes this workgroup's weight gradients:
                                      // W1 [64, ldw1], b1, W2, b2, W3, b3
 };
+
+// fetch_tile of the output's gradient (null: zeros; store_tile stores it)
+__device__ __forceinline__ void fetch_gy_tile(f32x4 (&v)[NQ], const float *gy, int ldgy, int d_out, const Span &W, int n0, int t)
+{
+    if (!gy) {
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) v[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    } else if (d_out == HS && ldgy == HS) fetch_tile(v, gy, W, n0, t);
+    else {                                           // a narrow output (the summary): columns < d_out, rows ldgy floats apart
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) {
+            const int p = t + NT * k, r = p >> 4, c4 = p & 15, cl = d_out - 1;
+            const float *gr = gy + (W.row0 + min(n0 + r, W.n_end - 1)) * ldgy;
+            const float a0 = gr[min(4 * c4, cl)], a1 = gr[min(4 * c4 + 1, cl)], a2 = gr[min(4 * c4 + 2, cl)], a3 = gr[min(4 * c4 + 3, cl)];
+            v[k] = f32x4{4 * c4 < d_out ? a0 : 0.0f, 4 * c4 + 1 < d_out ? a1 : 0.0f, 4 * c4 + 2 < d_out ? a2 : 0.0f, 4 * c4 + 3 < d_out ? a3 : 0.0f};
+        }
+    }
+}
 
 template <bool BIG>
 __global__ __launch_bounds__(NT) void mlp_bwd_kernel(Common C, BwdIO Q)
@@ -603,53 +659,24 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(Common C, BwdIO Q)
     __shared__ __attribute__((aligned(16))) float d2s[TM][LD];       // d(pre-activation 2)
     __shared__ float xsmall[BIG ? 1 : TM][DS_MAX];
     __shared__ float pooled[HS], cs[HS], gp[HS], dsum[HS], red[4][3][HS], redw[BIG ? 1 : 4][HS][DS_MAX], db1s[HS];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, m = lane & 31, kk = lane >> 5, rb = wave >> 1, ub = wave & 1;
-    const int b = blockIdx.x / C.S, sp = blockIdx.x - b * C.S;
-    const int n_begin = sp * C.rows_per_wg, n_end = min(C.N, n_begin + C.rows_per_wg);
-    const long long row0 = (long long)b * C.N;
+    const Lane L;
+    const Span W(C);
+    const int t = L.t, u = L.u, b = W.b, n_begin = W.n_begin, n_end = W.n_end;
     const float inv_n = inv_count(C);
     STAMP(200);
     auto load_tile = [&](const int n0) {             // saved activations, input and output gradient (the pooled part: added below)
         // every load unconditional, from a clamped row (rows beyond the set are zeroed at the store), and ALL of them issued before
         // the first store: inside `if (n < n_end)` each of the four passes was a branch and a round trip to L2 of its own
-        // (f32x4, the compiler's own vector type: arrays of HIP's float4 struct are kept in memory)
-        f32x4 v1[TM * HS / 4 / NT], v2[TM * HS / 4 / NT], vg[TM * HS / 4 / NT], vx[TM * HS / 4 / NT];
-        const bool gy_dense = C.d_out == HS && Q.ldgy == HS;
-        const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int k = 0; k < TM * HS / 4 / NT; ++k) {
-            const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-            const long long row = row0 + min(n0 + r, n_end - 1), o = row * HS + 4 * c4;
-            v1[k] = *reinterpret_cast<const f32x4 *>(Q.h1 + o);
-            v2[k] = *reinterpret_cast<const f32x4 *>(Q.h2 + o);
-            vg[k] = z;
-            vx[k] = z;
-            if (Q.gy) {
-                if (gy_dense) vg[k] = *reinterpret_cast<const f32x4 *>(Q.gy + o);
-                else {                               // a narrow output (the summary): columns < d_out, rows ldgy floats apart
-                    const float *gr = Q.gy + row * Q.ldgy;
-                    const int cl = C.d_out - 1;
-                    const float a0 = gr[min(4 * c4, cl)], a1 = gr[min(4 * c4 + 1, cl)], a2 = gr[min(4 * c4 + 2, cl)], a3 = gr[min(4 * c4 + 3, cl)];
-                    vg[k] = f32x4{4 * c4 < C.d_out ? a0 : 0.0f, 4 * c4 + 1 < C.d_out ? a1 : 0.0f, 4 * c4 + 2 < C.d_out ? a2 : 0.0f,
-                                  4 * c4 + 3 < C.d_out ? a3 : 0.0f};
-                }
-            }
-            if (BIG) { const float4 xv = x_row4(C, row, c4, inv_n); vx[k] = f32x4{xv.x, xv.y, xv.z, xv.w}; }
-        }
-#pragma unroll
-        for (int k = 0; k < TM * HS / 4 / NT; ++k) {
-            const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-            const bool ok = n0 + r < n_end;
-            *reinterpret_cast<f32x4 *>(&h1s[r][4 * c4]) = ok ? v1[k] : z;
-            *reinterpret_cast<f32x4 *>(&h2s[r][4 * c4]) = ok ? v2[k] : z;
-            *reinterpret_cast<f32x4 *>(&gs[r][4 * c4]) = ok ? vg[k] : z;
-            if (BIG) *reinterpret_cast<f32x4 *>(&xs[r][4 * c4]) = ok ? vx[k] : z;
-        }
-        if (!BIG)
-            for (int p = t; p < TM * C.d_in; p += NT) {
-                const int r = p / C.d_in, c = p - r * C.d_in, n = n0 + r;
-                xsmall[r][c] = n < n_end ? C.x[(row0 + n) * C.d_in + c] : 0.0f;
-            }
+        f32x4 v1[NQ], v2[NQ], vg[NQ], vx[NQ];
+        fetch_tile(v1, Q.h1, W, n0, t);
+        fetch_tile(v2, Q.h2, W, n0, t);
+        fetch_gy_tile(vg, Q.gy, Q.ldgy, C.d_out, W, n0, t);
+        if (BIG) fetch_x_tile(vx, C, W, n0, inv_n, t);
+        store_tile(h1s, v1, W, n0, t);
+        store_tile(h2s, v2, W, n0, t);
+        store_tile(gs, vg, W, n0, t);
+        if (BIG) store_tile(xs, vx, W, n0, t);
+        else fill_xsmall(xsmall, C, W, n0, t);
     };
     // the small loads that feed the context and the pooled gradient go FIRST (loads return in issue order): they are back while the
     // tiles and the weights are still on their way
@@ -658,8 +685,8 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(Common C, BwdIO Q)
     const bool gpw = Q.gpool && Q.gp_W;
     context_issue(C, b, t, Lc);
     if (gpw) gp_issue(Q.gpool, Q.gp_S, Q.gp_W, Q.gp_ldw, b, t, Lg);
-    {   // every weight load in flight before the first store (three stage64 calls in a row waited for three load latencies in turn)
-        f32x4 r1[HS * HS / 4 / NT], r2[HS * HS / 4 / NT], r3[HS * HS / 4 / NT];
+    {   // every weight load in flight before the first store (fetch, store, fetch, store ... waited for three load latencies in turn)
+        f32x4 r1[NQ], r2[NQ], r3[NQ];
         fetch64(r3, C.P.W3, HS, t, C.d_out);
         fetch64(r2, C.P.W2, HS, t);
         fetch64(r1, BIG ? C.P.W1 : C.P.W2, BIG ? C.P.ldw1 : HS, t);
@@ -675,11 +702,7 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(Common C, BwdIO Q)
     if (gpw) gp_product(dsum, gp, inv_n, t, Lg);     // gradient of the pooled output, per unit of this set
     else if (Q.gpool && t < HS) gp[t] = Q.gpool[(long long)b * HS + t] * inv_n;
     __syncthreads();
-    const int u = 32 * ub + m;
-    f32x16 aW1 = zero16(), aW2 = zero16(), aW3 = zero16();
-    float db[3] = {0.0f, 0.0f, 0.0f};                // thread (unit t & 63, rows 16 (t >> 6) ..): column sums of d(pre-activation 1..3)
-    float dw1[DS_MAX] = {0.0f, 0.0f, 0.0f, 0.0f};    // (!BIG) row t & 63 of dW1 over the same rows
-    const int uu = t & 63, rg = t >> 6;
+    Grads G;
     for (int n0 = n_begin; n0 < n_end; n0 += TM) {
         if (n0 != n_begin) {
             __syncthreads();                         // the previous tile's readers are done
@@ -689,7 +712,7 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(Common C, BwdIO Q)
         if (Q.gpool) {                               // the pooled output's gradient, spread over the set's real trials
             if (n0 != n_begin) __syncthreads();
 #pragma unroll
-            for (int k = 0; k < TM * HS / 4 / NT; ++k) {
+            for (int k = 0; k < NQ; ++k) {
                 const int p = t + NT * k, r = p >> 4, c4 = p & 15, n = n0 + r;
                 if (n < n_end) {
                     const float mk = mask_of(C, n);
@@ -702,94 +725,29 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(Common C, BwdIO Q)
         }
         __syncthreads();
         STAMP(202);
-        // layer 3: dW3 [unit out, unit in] += g^T h2 (the k's are the tile's rows); d h2 = g W3 -> d(pre-activation 2)
-        aW3 = mma64<LD, LD>(&gs[32 * kk][32 * rb + m], &h2s[32 * kk][u], aW3);
-#pragma unroll 8
-        for (int q = 0; q < 16; ++q) db[2] += gs[16 * rg + q][uu];
-        {
-            const f32x16 acc = mma64<1, LD>(&gs[32 * rb + m][32 * kk], &w3s[32 * kk][u], zero16());
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int r = 32 * rb + drow(v, kk);
-                d2s[r][u] = h2s[r][u] > 0.0f ? acc[v] : 0.0f;
-            }
-        }
+        bwd_layer(gs, h2s, w3s, d2s, G.aW3, G.db[2], L);             // layer 3: gs -> d(pre-activation 2) in d2s
         __syncthreads();
         STAMP(203);
-        // layer 2
-        aW2 = mma64<LD, LD>(&d2s[32 * kk][32 * rb + m], &h1s[32 * kk][u], aW2);
-#pragma unroll 8
-        for (int q = 0; q < 16; ++q) db[1] += d2s[16 * rg + q][uu];
-        {
-            const f32x16 acc = mma64<1, LD>(&d2s[32 * rb + m][32 * kk], &w2s[32 * kk][u], zero16());
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {           // (gs: its readers -- dW3, d h2 -- finished before the barrier above)
-                const int r = 32 * rb + drow(v, kk);
-                gs[r][u] = h1s[r][u] > 0.0f ? acc[v] : 0.0f;
-            }
-        }
+        bwd_layer(d2s, h1s, w2s, gs, G.aW2, G.db[1], L);             // layer 2: d2s -> d(pre-activation 1) in gs
         __syncthreads();
         STAMP(204);
-        // layer 1
-#pragma unroll 8
-        for (int q = 0; q < 16; ++q) db[0] += gs[16 * rg + q][uu];
+        bias_grad(gs, G.db[0], L);                                   // layer 1
         if (BIG) {
-            aW1 = mma64<LD, LD>(&gs[32 * kk][32 * rb + m], &xs[32 * kk][u], aW1);
+            G.aW1 = wgrad(gs, xs, G.aW1, L);
             if (Q.gx) {
-                const f32x16 acc = mma64<1, LD>(&gs[32 * rb + m][32 * kk], &w1s[32 * kk][u], zero16());
-                const RowTile tgx(Q.gx + (row0 + n0) * HS, n_end - n0);      // (rows beyond the set: the range check drops them)
+                const f32x16 acc = dgrad(gs, w1s, L);
+                const RowTile tgx(Q.gx + (W.row0 + n0) * HS, n_end - n0);    // (rows beyond the set: the range check drops them)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
-                    const int r = 32 * rb + drow(v, kk);
+                    const int r = 32 * L.rb + drow(v, L.kk);
                     tgx.put(r, u, Q.gx_acc ? tgx.get(r, u) + acc[v] : acc[v]);
                 }
             }
-        } else {
-#pragma unroll 4
-            for (int q = 0; q < 16; ++q) {
-                const float d = gs[16 * rg + q][uu];
-#pragma unroll
-                for (int c = 0; c < DS_MAX; ++c) if (c < C.d_in) dw1[c] = fmaf(d, xsmall[16 * rg + q][c], dw1[c]);
-            }
-        }
+        } else small_dw1(gs, xsmall, C.d_in, G.dw1, L);
     }
     STAMP(205);
-    // ---- this workgroup's partial sums
-    float *wp = Q.wpart + (long long)blockIdx.x * Q.ld_part;
-    const int ld1 = C.P.ldw1, oW1 = 0, ob1 = HS * ld1, oW2 = ob1 + HS, ob2 = oW2 + HS * HS, oW3 = ob2 + HS, ob3 = oW3 + C.d_out * HS;
-    const RowTile tw3(wp + oW3, C.d_out);
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {                   // tile (rb, ub): row = unit out, column = unit in
-        const int r = 32 * rb + drow(v, kk);
-        wp[oW2 + r * HS + u] = aW2[v];
-        tw3.put(r, u, aW3[v]);                       // (rows >= d_out: dropped)
-        if (BIG) wp[oW1 + r * ld1 + u] = aW1[v];
-    }
-#pragma unroll
-    for (int l = 0; l < 3; ++l) red[rg][l][uu] = db[l];
-    if (!BIG) {
-#pragma unroll
-        for (int c = 0; c < DS_MAX; ++c) redw[rg][uu][c] = dw1[c];
-    }
-    __syncthreads();
-    if (t < 3 * HS) {
-        const int l = t >> 6, c = t & 63;
-        const float v = (red[0][l][c] + red[1][l][c]) + (red[2][l][c] + red[3][l][c]);
-        if (l < 2 || c < C.d_out) wp[l == 0 ? ob1 + c : (l == 1 ? ob2 + c : ob3 + c)] = v;
-        if (l == 0) {
-            db1s[c] = v;
-            if (Q.dctx_part) Q.dctx_part[((long long)b * C.S + sp) * HS + c] = v;
-        }
-    }
-    if (!BIG && t < HS)
-        for (int c = 0; c < C.d_in; ++c) wp[oW1 + t * ld1 + c] = (redw[0][t][c] + redw[1][t][c]) + (redw[2][t][c] + redw[3][t][c]);
-    if (C.ctx_part) {                                // context columns of W1: (sum of d pre-activation 1) x pooled
-        __syncthreads();
-        for (int p = t; p < HS * HS; p += NT) {
-            const int r = p >> 6, k = p & 63;
-            wp[oW1 + r * ld1 + C.d_in + k] = db1s[r] * pooled[k];
-        }
-    }
+    wgrad_epilogue<BIG>(Q.wpart + (long long)W.wg * Q.ld_part, C.P.ldw1, C.d_in, C.d_out, G, red, redw, db1s, Q.dctx_part, C.ctx_part != nullptr, pooled,
+                        W, L);
     STAMP(206);
 }
 
@@ -828,12 +786,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     __shared__ __attribute__((aligned(16))) float d2s[TM][LD];
     __shared__ float xsmall[BIG ? 1 : TM][DS_MAX];
     __shared__ float pooled[HS], cs[HS], gp[HS], dsum[HS], red[4][3][HS], redw[BIG ? 1 : 4][HS][DS_MAX], db1s[HS];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, m = lane & 31, kk = lane >> 5, rb = wave >> 1, ub = wave & 1;
-    const int b = blockIdx.x / C.S, sp = blockIdx.x - b * C.S;
-    const int n0 = sp * C.rows_per_wg, n_end = min(C.N, n0 + C.rows_per_wg);
-    const long long row0 = (long long)b * C.N;
+    const Lane L;
+    const Span W(C);
+    const int t = L.t, u = L.u, b = W.b, n0 = W.n_begin, n_end = W.n_end;
     const float inv_n = inv_count(C);
-    const int u = 32 * ub + m, uu = t & 63, rg = t >> 6;
     // ---- Y's pooled context and the gradient of X's pooled output, per unit of this set: their loads go out FIRST and are consumed
     //      before the operand fetches below are issued (this kernel has no registers left to hold both) -- behind those fetches,
     //      in issue order, they cost four round trips at the head of the kernel
@@ -852,51 +808,32 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     // ---- every global load up front, in the order of need.  X: h2 and W3 (layer 3 runs first), then h1 and W2, then the input tile
     //      and W1; they are stored to LDS just before the phase that reads them (behind the barriers that are there anyway), so
     //      one load latency is exposed instead of one per operand.  Y's operands follow and stay in registers until X is done.
-    f32x4 xh2[TM * HS / 4 / NT], xw3[HS * HS / 4 / NT], xh1[TM * HS / 4 / NT], xw2[HS * HS / 4 / NT], xx[TM * HS / 4 / NT], xw1[HS * HS / 4 / NT];
-    auto fetch_tile = [&](f32x4 (&v)[TM * HS / 4 / NT], const float *src) {
-#pragma unroll
-        for (int k = 0; k < TM * HS / 4 / NT; ++k) {
-            const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-            v[k] = *reinterpret_cast<const f32x4 *>(src + (row0 + min(n0 + r, n_end - 1)) * HS + 4 * c4);     // (clamped; zeroed at the store)
-        }
-    };
-    auto store_tile = [&](float (*dst)[LD], const f32x4 (&v)[TM * HS / 4 / NT]) {
-        const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int k = 0; k < TM * HS / 4 / NT; ++k) {
-            const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-            *reinterpret_cast<f32x4 *>(&dst[r][4 * c4]) = n0 + r < n_end ? v[k] : z;
-        }
-    };
-    fetch_tile(xh2, Q.h2x);
+    f32x4 xh2[NQ], xw3[NQ], xh1[NQ], xw2[NQ], xx[NQ], xw1[NQ];
+    fetch_tile(xh2, Q.h2x, W, n0, t);
     fetch64(xw3, Q.PX.W3, HS, t);
-    fetch_tile(xh1, Q.h1x);
+    fetch_tile(xh1, Q.h1x, W, n0, t);
     fetch64(xw2, Q.PX.W2, HS, t);
-    fetch_tile(xx, Q.x1);
+    fetch_tile(xx, Q.x1, W, n0, t);
     fetch64(xw1, Q.PX.W1, HS, t);
     // ---- Y's operands -> registers (stored to LDS when X's readers are done)
-    f32x4 q1[HS * HS / 4 / NT], q2[HS * HS / 4 / NT], q3[HS * HS / 4 / NT], th1[TM * HS / 4 / NT], th2[TM * HS / 4 / NT], tx[TM * HS / 4 / NT];
+    f32x4 q1[NQ], q2[NQ], q3[NQ], th1[NQ], th2[NQ], tx[NQ];
     fetch64(q2, C.P.W2, HS, t);
     fetch64(q3, C.P.W3, HS, t);
     fetch64(q1, BIG ? C.P.W1 : C.P.W2, BIG ? C.P.ldw1 : HS, t);          // (unconditional: a guarded fetch is a branch around every load)
-    fetch_tile(th1, Q.h1y);
-    fetch_tile(th2, Q.h2y);
-    if (BIG) fetch_tile(tx, C.x);
+    fetch_tile(th1, Q.h1y, W, n0, t);
+    fetch_tile(th2, Q.h2y, W, n0, t);
+    if (BIG) fetch_tile(tx, C.x, W, n0, t);
     else {
 #pragma unroll
-        for (int k = 0; k < TM * HS / 4 / NT; ++k) tx[k] = th1[k];
+        for (int k = 0; k < NQ; ++k) tx[k] = th1[k];
+        fill_xsmall(xsmall, C, W, n0, t);
     }
-    if (!BIG)
-        for (int p = t; p < TM * C.d_in; p += NT) {
-            const int r = p / C.d_in, c = p - r * C.d_in, n = n0 + r;
-            xsmall[r][c] = n < n_end ? C.x[(row0 + n) * C.d_in + c] : 0.0f;
-        }
     // (Y's pooled context and the gradient of X's pooled output were computed at the head of the kernel: see there)
-    store_tile(h2s, xh2);
+    store_tile(h2s, xh2, W, n0, t);
     store64(w3s, xw3, t);
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < TM * HS / 4 / NT; ++k) {     // the pooled output's gradient, spread over the set's real trials (rows beyond: zero)
+    for (int k = 0; k < NQ; ++k) {                   // the pooled output's gradient, spread over the set's real trials (rows beyond: zero)
         const int p = t + NT * k, r = p >> 4, c4 = p & 15, n = n0 + r;
         const float mk = n < n_end ? mask_of(C, n) : 0.0f;
         *reinterpret_cast<float4 *>(&gs[r][4 * c4]) = make_float4(mk * gp[4 * c4], mk * gp[4 * c4 + 1], mk * gp[4 * c4 + 2], mk * gp[4 * c4 + 3]);
@@ -904,155 +841,56 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     __syncthreads();
     // ================================================================================ X
     {
-        f32x16 aW1, aW2, aW3;
-        float db[3] = {0.0f, 0.0f, 0.0f};
-        aW3 = mma64<LD, LD>(&gs[32 * kk][32 * rb + m], &h2s[32 * kk][u], zero16());
-#pragma unroll 8
-        for (int q = 0; q < 16; ++q) db[2] += gs[16 * rg + q][uu];
-        {
-            const f32x16 acc = mma64<1, LD>(&gs[32 * rb + m][32 * kk], &w3s[32 * kk][u], zero16());
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int r = 32 * rb + drow(v, kk);
-                d2s[r][u] = h2s[r][u] > 0.0f ? acc[v] : 0.0f;
-            }
-        }
-        store_tile(h1s, xh1);                        // (layer 2's operands: first read behind the barrier)
+        Grads G;
+        bwd_layer(gs, h2s, w3s, d2s, G.aW3, G.db[2], L);
+        store_tile(h1s, xh1, W, n0, t);              // (layer 2's operands: first read behind the barrier)
         store64(w2s, xw2, t);
         __syncthreads();
-        aW2 = mma64<LD, LD>(&d2s[32 * kk][32 * rb + m], &h1s[32 * kk][u], zero16());
-#pragma unroll 8
-        for (int q = 0; q < 16; ++q) db[1] += d2s[16 * rg + q][uu];
-        {
-            const f32x16 acc = mma64<1, LD>(&d2s[32 * rb + m][32 * kk], &w2s[32 * kk][u], zero16());
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int r = 32 * rb + drow(v, kk);
-                gs[r][u] = h1s[r][u] > 0.0f ? acc[v] : 0.0f;
-            }
-        }
-        store_tile(xs, xx);                          // (layer 1's)
+        bwd_layer(d2s, h1s, w2s, gs, G.aW2, G.db[1], L);
+        store_tile(xs, xx, W, n0, t);                // (layer 1's)
         store64(w1s, xw1, t);
         __syncthreads();
-#pragma unroll 8
-        for (int q = 0; q < 16; ++q) db[0] += gs[16 * rg + q][uu];
-        aW1 = mma64<LD, LD>(&gs[32 * kk][32 * rb + m], &xs[32 * kk][u], zero16());
+        bias_grad(gs, G.db[0], L);
+        G.aW1 = wgrad(gs, xs, G.aW1, L);
         {   // X's input gradient (+ the other consumer's) = Y's output gradient: into d2s (its readers finished before the barrier above)
-            const f32x16 acc = mma64<1, LD>(&gs[32 * rb + m][32 * kk], &w1s[32 * kk][u], zero16());
-            const RowTile tprev(Q.gx_prev ? Q.gx_prev + (row0 + n0) * HS : Q.h1y, Q.gx_prev ? n_end - n0 : 0);   // (no such gradient: a buffer of no rows reads zeros)
+            const f32x16 acc = dgrad(gs, w1s, L);
+            const RowTile tprev(Q.gx_prev ? Q.gx_prev + (W.row0 + n0) * HS : Q.h1y, Q.gx_prev ? n_end - n0 : 0);   // (no such gradient: a buffer of no rows reads zeros)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int r = 32 * rb + drow(v, kk), n = n0 + r;
+                const int r = 32 * L.rb + drow(v, L.kk), n = n0 + r;
                 const float g = tprev.get(r, u) + acc[v];
                 d2s[r][u] = n < n_end ? g : 0.0f;
             }
         }
-        float *wp = Q.wpart_x + (long long)blockIdx.x * Q.ld_part;
-        const int oW1 = 0, ob1 = HS * HS, oW2 = ob1 + HS, ob2 = oW2 + HS * HS, oW3 = ob2 + HS, ob3 = oW3 + HS * HS;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int r = 32 * rb + drow(v, kk);
-            wp[oW1 + r * HS + u] = aW1[v];
-            wp[oW2 + r * HS + u] = aW2[v];
-            wp[oW3 + r * HS + u] = aW3[v];
-        }
-#pragma unroll
-        for (int l = 0; l < 3; ++l) red[rg][l][uu] = db[l];
-        __syncthreads();                             // (also: every reader of X's tiles and weights is done, d2s is complete)
-        if (t < 3 * HS) {
-            const int l = t >> 6, c = t & 63;
-            wp[l == 0 ? ob1 + c : (l == 1 ? ob2 + c : ob3 + c)] = (red[0][l][c] + red[1][l][c]) + (red[2][l][c] + red[3][l][c]);
-        }
+        // (no context, W1 [64, 64]; behind the epilogue's barrier every reader of X's tiles and weights is done and d2s is complete)
+        wgrad_epilogue<true>(Q.wpart_x + (long long)W.wg * Q.ld_part, HS, HS, HS, G, red, redw, db1s, nullptr, false, pooled, W, L);
     }
     // ================================================================================ Y
     store64(w2s, q2, t);
     store64(w3s, q3, t);
     if (BIG) store64(w1s, q1, t);
-    store_tile(h1s, th1);
-    store_tile(h2s, th2);
-    if (BIG) store_tile(xs, tx);
+    store_tile(h1s, th1, W, n0, t);
+    store_tile(h2s, th2, W, n0, t);
+    if (BIG) store_tile(xs, tx, W, n0, t);
     __syncthreads();                                 // (and the readers of red[] above are done before Y's epilogue writes it)
     {
-        f32x16 aW1 = zero16(), aW2, aW3;
-        float db[3] = {0.0f, 0.0f, 0.0f};
-        float dw1[DS_MAX] = {0.0f, 0.0f, 0.0f, 0.0f};
+        Grads G;
         // the output gradient is in d2s; gs takes d(pre-activation 2), then d2s d(pre-activation 1): the single kernel's roles, swapped
-        aW3 = mma64<LD, LD>(&d2s[32 * kk][32 * rb + m], &h2s[32 * kk][u], zero16());
-#pragma unroll 8
-        for (int q = 0; q < 16; ++q) db[2] += d2s[16 * rg + q][uu];
-        {
-            const f32x16 acc = mma64<1, LD>(&d2s[32 * rb + m][32 * kk], &w3s[32 * kk][u], zero16());
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int r = 32 * rb + drow(v, kk);
-                gs[r][u] = h2s[r][u] > 0.0f ? acc[v] : 0.0f;
-            }
-        }
+        bwd_layer(d2s, h2s, w3s, gs, G.aW3, G.db[2], L);
         __syncthreads();
-        aW2 = mma64<LD, LD>(&gs[32 * kk][32 * rb + m], &h1s[32 * kk][u], zero16());
-#pragma unroll 8
-        for (int q = 0; q < 16; ++q) db[1] += gs[16 * rg + q][uu];
-        {
-            const f32x16 acc = mma64<1, LD>(&gs[32 * rb + m][32 * kk], &w2s[32 * kk][u], zero16());
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int r = 32 * rb + drow(v, kk);
-                d2s[r][u] = h1s[r][u] > 0.0f ? acc[v] : 0.0f;
-            }
-        }
+        bwd_layer(gs, h1s, w2s, d2s, G.aW2, G.db[1], L);
         __syncthreads();
-#pragma unroll 8
-        for (int q = 0; q < 16; ++q) db[0] += d2s[16 * rg + q][uu];
+        bias_grad(d2s, G.db[0], L);
         if (BIG) {
-            aW1 = mma64<LD, LD>(&d2s[32 * kk][32 * rb + m], &xs[32 * kk][u], zero16());
+            G.aW1 = wgrad(d2s, xs, G.aW1, L);
             if (Q.gx) {
-                const f32x16 acc = mma64<1, LD>(&d2s[32 * rb + m][32 * kk], &w1s[32 * kk][u], zero16());
-                const RowTile tgx(Q.gx + (row0 + n0) * HS, n_end - n0);
+                const f32x16 acc = dgrad(d2s, w1s, L);
+                const RowTile tgx(Q.gx + (W.row0 + n0) * HS, n_end - n0);
 #pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    tgx.put(32 * rb + drow(v, kk), u, acc[v]);
-                }
+                for (int v = 0; v < 16; ++v) tgx.put(32 * L.rb + drow(v, L.kk), u, acc[v]);
             }
-        } else {
-#pragma unroll 4
-            for (int q = 0; q < 16; ++q) {
-                const float d = d2s[16 * rg + q][uu];
-#pragma unroll
-                for (int c = 0; c < DS_MAX; ++c) if (c < C.d_in) dw1[c] = fmaf(d, xsmall[16 * rg + q][c], dw1[c]);
-            }
-        }
-        float *wp = Q.wpart_y + (long long)blockIdx.x * Q.ld_part;
-        const int ld1 = C.P.ldw1, oW1 = 0, ob1 = HS * ld1, oW2 = ob1 + HS, ob2 = oW2 + HS * HS, oW3 = ob2 + HS, ob3 = oW3 + HS * HS;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int r = 32 * rb + drow(v, kk);
-            wp[oW2 + r * HS + u] = aW2[v];
-            wp[oW3 + r * HS + u] = aW3[v];
-            if (BIG) wp[oW1 + r * ld1 + u] = aW1[v];
-        }
-#pragma unroll
-        for (int l = 0; l < 3; ++l) red[rg][l][uu] = db[l];
-        if (!BIG) {
-#pragma unroll
-            for (int c = 0; c < DS_MAX; ++c) redw[rg][uu][c] = dw1[c];
-        }
-        __syncthreads();
-        if (t < 3 * HS) {
-            const int l = t >> 6, c = t & 63;
-            const float v = (red[0][l][c] + red[1][l][c]) + (red[2][l][c] + red[3][l][c]);
-            wp[l == 0 ? ob1 + c : (l == 1 ? ob2 + c : ob3 + c)] = v;
-            if (l == 0) {
-                db1s[c] = v;
-                Q.dctx_part[((long long)b * C.S + sp) * HS + c] = v;
-            }
-        }
-        if (!BIG && t < HS)
-            for (int c = 0; c < C.d_in; ++c) wp[oW1 + t * ld1 + c] = (redw[0][t][c] + redw[1][t][c]) + (redw[2][t][c] + redw[3][t][c]);
-        __syncthreads();                             // context columns of W1: (sum of d pre-activation 1) x pooled
-        for (int p = t; p < HS * HS; p += NT) {
-            const int r = p >> 6, k = p & 63;
-            wp[oW1 + r * ld1 + C.d_in + k] = db1s[r] * pooled[k];
-        }
+        } else small_dw1(d2s, xsmall, C.d_in, G.dw1, L);
+        wgrad_epilogue<BIG>(Q.wpart_y + (long long)W.wg * Q.ld_part, C.P.ldw1, C.d_in, HS, G, red, redw, db1s, Q.dctx_part, true, pooled, W, L);
     }
 }
 
@@ -1087,6 +925,24 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float *part,
 
 using namespace nddm_deepset;
 
+// the 22 leading arguments of the four MLP entry points, in their order
+static Common make_common(const float *x, int d_in, int B, int N, int S, int rows_per_wg, const float *mask, int mask_is_count, const float *inv_n,
+                          float inv_n_host, const float *ctx_part, int S_ctx, const float *W1, int ldw1, const float *b1, const float *W2,
+                          const float *b2, const float *W3, const float *b3, int d_out, const float *x_part, int S_x)
+{
+    return {x, d_in, B, N, S, rows_per_wg, mask, mask && mask_is_count, inv_n, inv_n_host, ctx_part, S_ctx, {W1, ldw1, b1, W2, b2, W3, b3}, d_out, x_part, S_x};
+}
+
+// one workgroup per (set, workgroup of the set): the kernel for a 64-wide input or the one for a small input.  0, or 2: the launch failed
+template <typename K, typename... A>
+static int launch_by_d_in(K big, K small, const Common &C, void *stream, const A &...args)
+{
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (C.d_in == HS) hipLaunchKernelGGL(big, dim3(C.B * C.S), dim3(NT), 0, st, C, args...);
+    else hipLaunchKernelGGL(small, dim3(C.B * C.S), dim3(NT), 0, st, C, args...);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
 extern "C" {
 
 int nddm_deepset_supported(int hidden, int d_in) { return (hidden == HS && (d_in == HS || (d_in >= 1 && d_in <= DS_MAX))) ? 1 : 0; }
@@ -1108,15 +964,12 @@ int nddm_deepset_mlp_fwd(const float *x, int d_in, int B, int N, int S, int rows
                          const float *b2, const float *W3, const float *b3, int d_out, const float *x_part, int S_x, float *h1, float *h2,
                          float *y, float *pool_part, int ldy, const float *extra, int n_extra, int extra_stride, void *stream)
 {
-    const Common C = {x, d_in, B, N, S, rows_per_wg, mask, mask && mask_is_count, inv_n, inv_n_host, ctx_part, S_ctx, {W1, ldw1, b1, W2, b2, W3, b3}, d_out, x_part, S_x};
+    const Common C = make_common(x, d_in, B, N, S, rows_per_wg, mask, mask_is_count, inv_n, inv_n_host, ctx_part, S_ctx, W1, ldw1, b1, W2, b2, W3, b3, d_out, x_part, S_x);
     if (ldy <= 0) ldy = d_out;
     if (!common_ok(C) || !h1 || !h2 || (pool_part && d_out != HS) || n_extra < 0 || (extra && (!y || d_out + n_extra > HS)) || ldy < d_out + (extra ? n_extra : 0))
         return 1;
     const FwdOut O = {h1, h2, y, pool_part, ldy, extra, extra ? n_extra : 0, extra_stride};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d_in == HS) hipLaunchKernelGGL(mlp_fwd_kernel<true>, dim3(B * S), dim3(NT), 0, st, C, O);
-    else hipLaunchKernelGGL(mlp_fwd_kernel<false>, dim3(B * S), dim3(NT), 0, st, C, O);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    return launch_by_d_in(mlp_fwd_kernel<true>, mlp_fwd_kernel<false>, C, stream, O);
 }
 
 /* The backward of nddm_deepset_mlp_fwd (same first arguments).  gy [B * N, 64] or NULL; gpool / gp_S / gp_W / gp_ldw: see BwdIO;
@@ -1129,15 +982,12 @@ int nddm_deepset_mlp_bwd(const float *x, int d_in, int B, int N, int S, int rows
                          int gx_acc, float *dctx_part, float *wpart, int ld_part, void *stream)
 {
     if (ldgy <= 0) ldgy = d_out;
-    const Common C = {x, d_in, B, N, S, rows_per_wg, mask, mask && mask_is_count, inv_n, inv_n_host, ctx_part, S_ctx, {W1, ldw1, b1, W2, b2, W3, b3}, d_out, x_part, S_x};
+    const Common C = make_common(x, d_in, B, N, S, rows_per_wg, mask, mask_is_count, inv_n, inv_n_host, ctx_part, S_ctx, W1, ldw1, b1, W2, b2, W3, b3, d_out, x_part, S_x);
     if (!common_ok(C) || !h1 || !h2 || !wpart || ld_part < HS * ldw1 + HS + HS * HS + HS + d_out * HS + d_out || (gx && d_in != HS)
         || (!gy && !gpool) || (gpool && d_out != HS) || ldgy < d_out)
         return 1;
     const BwdIO Q = {h1, h2, gy, ldgy, gpool, gp_S, gp_W, gp_ldw, gx, gx_acc, dctx_part, wpart, ld_part};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d_in == HS) hipLaunchKernelGGL(mlp_bwd_kernel<true>, dim3(B * S), dim3(NT), 0, st, C, Q);
-    else hipLaunchKernelGGL(mlp_bwd_kernel<false>, dim3(B * S), dim3(NT), 0, st, C, Q);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    return launch_by_d_in(mlp_bwd_kernel<true>, mlp_bwd_kernel<false>, C, stream, Q);
 }
 
 /* nddm_deepset_mlp_fwd for an equivariant MLP A (same first arguments; d_out 64, y required) FOLLOWED IN THE SAME LAUNCH by the
@@ -1150,16 +1000,13 @@ int nddm_deepset_mlp2_fwd(const float *x, int d_in, int B, int N, int S, int row
                           float *y, const float *W1b, const float *b1b, const float *W2b, const float *b2b, const float *W3b, const float *b3b,
                           float *h1b, float *h2b, float *pool_part_b, void *stream)
 {
-    const Common C = {x, d_in, B, N, S, rows_per_wg, mask, mask && mask_is_count, inv_n, inv_n_host, ctx_part, S_ctx, {W1, ldw1, b1, W2, b2, W3, b3}, d_out, x_part, S_x};
+    const Common C = make_common(x, d_in, B, N, S, rows_per_wg, mask, mask_is_count, inv_n, inv_n_host, ctx_part, S_ctx, W1, ldw1, b1, W2, b2, W3, b3, d_out, x_part, S_x);
     if (!common_ok(C) || rows_per_wg != TM || d_out != HS || x_part || !h1 || !h2 || !y || !W1b || !b1b || !W2b || !b2b || !W3b || !b3b || !h1b || !h2b
         || !pool_part_b)
         return 1;
     const FwdOut O = {h1, h2, y, nullptr, HS, nullptr, 0, 0}, O2 = {h1b, h2b, nullptr, pool_part_b, HS, nullptr, 0, 0};
     const Mlp P2 = {W1b, HS, b1b, W2b, b2b, W3b, b3b};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d_in == HS) hipLaunchKernelGGL(mlp2_fwd_kernel<true>, dim3(B * S), dim3(NT), 0, st, C, O, P2, O2);
-    else hipLaunchKernelGGL(mlp2_fwd_kernel<false>, dim3(B * S), dim3(NT), 0, st, C, O, P2, O2);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    return launch_by_d_in(mlp2_fwd_kernel<true>, mlp2_fwd_kernel<false>, C, stream, O, P2, O2);
 }
 
 /* The backward of nddm_deepset_mlp2_fwd's pair, in the backward's order: first the pooling MLP X (input x1 [B * N, 64] = Y's output;
@@ -1177,15 +1024,12 @@ int nddm_deepset_mlp2_bwd(const float *x, int d_in, int B, int N, int S, int row
                           const float *gpool, int gp_S, const float *gp_W, int gp_ldw, const float *gx_prev, float *wpart_x, int ld_part,
                           void *stream)
 {
-    const Common C = {x, d_in, B, N, S, rows_per_wg, mask, mask && mask_is_count, inv_n, inv_n_host, ctx_part, S_ctx, {W1, ldw1, b1, W2, b2, W3, b3}, d_out, x_part, S_x};
+    const Common C = make_common(x, d_in, B, N, S, rows_per_wg, mask, mask_is_count, inv_n, inv_n_host, ctx_part, S_ctx, W1, ldw1, b1, W2, b2, W3, b3, d_out, x_part, S_x);
     if (!common_ok(C) || rows_per_wg != TM || d_out != HS || x_part || !ctx_part || !h1y || !h2y || !dctx_part || !wpart_y || !x1 || !W1x || !W2x || !W3x
         || !h1x || !h2x || !gpool || !wpart_x || (gx && d_in != HS) || ld_part < HS * ldw1 + HS + 2 * (HS * HS + HS))
         return 1;
     const Bwd2 Q = {x1, {W1x, HS, b1x, W2x, b2x, W3x, b3x}, h1x, h2x, gpool, gp_S, gp_W, gp_ldw, gx_prev, wpart_x, h1y, h2y, gx, dctx_part, wpart_y, ld_part};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d_in == HS) hipLaunchKernelGGL(mlp2_bwd_kernel<true>, dim3(B * S), dim3(NT), 0, st, C, Q);
-    else hipLaunchKernelGGL(mlp2_bwd_kernel<false>, dim3(B * S), dim3(NT), 0, st, C, Q);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    return launch_by_d_in(mlp2_bwd_kernel<true>, mlp2_bwd_kernel<false>, C, stream, Q);
 }
 
 int nddm_deepset_reduce(const float *part, int G, int P, int P_main, int G_tail, float *out, void *stream)

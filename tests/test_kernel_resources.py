@@ -52,7 +52,8 @@ def test_training_kernels_have_no_scratch_and_fit_their_lds():
     import resource_table as rt
     rows = {rt.pretty(r["name"]): r for r in rt.collect(train=True)}
     for k in ("flow_fwd_kernel", "flow_dgrad_kernel", "flow_wgrad_kernel", "mlp_fwd_kernel<true>", "mlp_fwd_kernel<false>",
-              "mlp_bwd_kernel<true>", "mlp_bwd_kernel<false>", "reduce_partials_kernel", "sqnorm_partial_kernel", "adam_kernel"):
+              "mlp_bwd_kernel<true>", "mlp_bwd_kernel<false>", "mlp2_fwd_kernel<true>", "mlp2_fwd_kernel<false>", "mlp2_bwd_kernel<true>",
+              "mlp2_bwd_kernel<false>", "flow_sample_kernel", "reduce_partials_kernel", "sqnorm_partial_kernel", "adam_kernel"):
         assert k in rows, (k, sorted(rows))
     for name, r in rows.items():
         assert r.get("ScratchSize [bytes/lane]", 0) == 0, name

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Compiler resource table of every kernel in nddm_kernels.hip -- and, with --train, of the amortizer's kernels
-(train_kernels.hip, train_deepset.hip, train_update.hip) -- from hipcc -Rpass-analysis=kernel-resource-usage:
+(build.TRAIN_SOURCES: every source of libnddm_train.so) -- from hipcc -Rpass-analysis=kernel-resource-usage:
 VGPRs, SGPRs, scratch, LDS, and the waves/SIMD the register files allow on gfx950.
 
 The SGPR limit is the one measured with tools/ubench_residency.hip (profiles/r1_ubench_residency.txt): 800 SGPRs per
@@ -62,16 +62,14 @@ def waves_by_vgpr(v):
     return min(8, 512 // (((v + 7) // 8) * 8))
 
 
-TRAIN_SRCS = [os.path.join(ROOT, "bayesflow_nddms_amd", "csrc", f) for f in ("train_kernels.hip", "train_deepset.hip", "train_update.hip")]
-
-
 def collect(train=False):
-    """One dict per kernel.  train=True: the amortizer's kernels (compiled as build.build_train does: -O3, contraction on)."""
+    """One dict per kernel.  train=True: the amortizer's kernels, every source of libnddm_train.so (compiled as build.build_train
+    does: -O3, contraction on)."""
     text = ""
     with tempfile.TemporaryDirectory() as td:
         sys.path.insert(0, ROOT)
-        from bayesflow_nddms_amd.build import _hipcc
-        for src in (TRAIN_SRCS if train else [SRC]):
+        from bayesflow_nddms_amd.build import _hipcc, TRAIN_SOURCES
+        for src in (TRAIN_SOURCES if train else [SRC]):
             flags = ["-O3", "--offload-arch=gfx950", "-std=c++17"] + ([] if train else ["-ffp-contract=off"])
             r = subprocess.run([_hipcc()] + flags + ["-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o",
                                 os.path.join(td, "k.o"), src], capture_output=True, text=True, check=True)
