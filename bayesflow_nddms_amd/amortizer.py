@@ -446,7 +446,7 @@ class InvertibleNetwork(nn.Module):
                                                            cond.shape[1])
         return L if ok else None
 
-    # (the fused kernels take 8 / 32 rows per workgroup, and one workgroup per half-layer sums the weight gradients over all rows:
+    # (the fused kernels take 16 rows per workgroup, and one workgroup per half-layer sums the weight gradients over all rows:
     # made for the training loop's batches of 32 ... a few hundred rows)
     FUSED_MAX_ROWS = 4096
     # a GraphTrainer may set {"grads": {parameter data_ptr: its slot in the trainer's flat gradient buffer}, "loss": the loss's slot}:

@@ -17,13 +17,13 @@
 // gfx950 only.  tests/test_gpu_training.py compares with the PyTorch composition.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "train_flow.h"      // H, elu, f32x4 / f32x16, lds_barrier, RowBuf, HalfP / LayerP / FlowP, fill: shared with train_sample.hip
+#include "train_flow.h"      // the flow's vocabulary: the parameter block, a half-layer's shape and the steps shared with train_sample.hip
 
 namespace nddm_train {
 
-constexpr int TR = 32;        // rows per tile
-constexpr int DI_MAX = 32;    // inputs of the sub-network (x_h columns + condition columns)
-constexpr int M_MAX = 16;     // outputs (2 * transformed columns)
+constexpr int TR = 32;        // rows per tile of the weight-gradient kernel
+constexpr int TC = 16;        // rows per workgroup of the two chain kernels (forward, activation gradients): one 16-row MFMA tile
+constexpr int NC = 512;       // ... and their threads: eight waves, two per SIMD
 
 #ifdef NDDM_TRAIN_STAMPS      // development only: phase time stamps of one workgroup (tools/train_stamps.py)
 __device__ unsigned long long g_stamps[8192];
@@ -35,12 +35,6 @@ __device__ int g_nstamps;
 #else
 #define STAMP(id) do { } while (0)
 #endif
-
-// ELU' from the saved PRE-activation: exp(a) itself.  (Until round 5 the forward saved the OUTPUT h and the backward took h + 1: an
-// absolute 2^-24 on a factor that can be far below 1 -- PyTorch keeps the input -- which left the activation-gradient chain at ~2 x
-// PyTorch's error against float64, tools/fused_accuracy.py.  The saved tensors h_all now hold a = W in + b; the weight-gradient kernel
-// re-derives h = elu(a) when it stages its tiles.)
-__device__ __forceinline__ float elu_grad_from_pre(float a) { return a > 0.0f ? 1.0f : expf(a); }   // alpha = 1
 
 // ------------------------------------------------------------------------------------------------ forward
 // grid = ceil(R / 16) workgroups of 512 threads over tiles of 16 rows (two workgroups at batch 32: every product then fills the
@@ -54,59 +48,61 @@ __device__ __forceinline__ float elu_grad_from_pre(float a) { return a > 0.0f ? 
 // operand so that the lanes an LDS instruction serves together fall on different banks.  The NEXT half-layer's weights are
 // fetched into registers at the top of a half-layer and written to LDS once their buffers' last readers are done: a half-layer
 // is a chain of short phases, and a cold load at the head of each was 3.3 of its 8.4 microseconds (now 5.2 in all).
-constexpr int LDR = H + 4;      // row stride of the [row][unit] tiles and of W2 in LDS: 16-byte aligned rows whose operand reads
-                                // (16 rows x 4 column groups per wave instruction) spread evenly over the banks
 struct FlowDims { int L, R, D, d1, C; float clamp; };
 struct FlowSaved { float *z_all, *out_all, *s_all, *h_all; };    // [L, R, D] permuted ActNorm outputs, layer outputs, clamped
                                                                   // log-scales; [L, 4, R, H] activations of the sub-networks
-template <int TF, int NT>        // rows per workgroup, threads: 8 x 256 (four CUs at batch 32) or 16 x 512 (two CUs, full 16-row MFMA tiles)
-__global__ __launch_bounds__(NT) void flow_fwd_kernel(FlowDims Q, FlowP P, const float *theta, const float *cond, FlowSaved S, float *ld)
+__global__ __launch_bounds__(NC) void flow_fwd_kernel(FlowDims Q, FlowP P, const float *theta, const float *cond, FlowSaved S, float *ld)
 {
-    constexpr int UW = H / (NT / 64);          // units per wave in layer 2: 32 (two 16 x 16 tiles) or 16 (one)
-    static_assert(TF % 4 == 0 && TF <= 16 && (UW == 32 || UW == 16) && M_MAX == 16 && TF * D_MAX <= NT && DI_MAX == 32, "tile shape");
-    __shared__ float in_s[16 * (DI_MAX + 2)];   // the sub-network's input rows, an MFMA operand read a dword at a time down 16 rows: row stride 33 or 34 by
-                                                // the parity of DI (see layer 1); columns >= DI zero; rows TF.. stay zero
-    __shared__ __attribute__((aligned(16))) float h1r[16][LDR];        // rows TF..15 stay zero (the MFMA tile has 16 rows)
-    __shared__ __attribute__((aligned(16))) float h2r[TF][LDR];
-    __shared__ float o_s[TF][M_MAX];
+    static_assert(TC == 16 && NC / 64 == H / 16 && M_MAX == 16 && DI_MAX == 32, "one 16 x 16 tile of layers 1 and 2 per wave");
+    __shared__ float in_s[TC * (DI_MAX + 2)];   // the sub-network's input rows, an MFMA operand read a dword at a time down 16 rows: row stride 33 or 34 by
+                                                // the parity of DI (see layer 1); columns >= DI zero
+    __shared__ __attribute__((aligned(16))) float h1r[TC][LDR];
+    __shared__ __attribute__((aligned(16))) float h2r[TC][LDR];
+    __shared__ float o_s[TC][M_MAX];
     __shared__ float w3s[16][H + 2];          // W3 [output][unit], rows >= M zero: an MFMA operand read a dword at a time down its 16 rows (+ 2: banks 2 n + k)
-    __shared__ float part3[NT / 64][16][16];  // layer 3's partial tiles, one per wave
+    __shared__ float part3[NC / 64][16][16];  // layer 3's partial tiles, one per wave
     __shared__ __attribute__((aligned(16))) float w2s[H][LDR];
-    __shared__ float xs[2][TF][D_MAX];       // the layer's input / output rows (alternating), zs: its permuted ActNorm output
-    __shared__ float zs[TF][D_MAX], cs[TF][DI_MAX];
+    __shared__ float xs[2][TC][D_MAX];       // the layer's input / output rows (alternating), zs: its permuted ActNorm output
+    __shared__ float zs[TC][D_MAX], cs[TC][DI_MAX];
     __shared__ float w1f[H * DI_MAX + DI_MAX];  // W1 as it lies in memory, [unit][DI]: the other MFMA operand of layer 1 (+ DI_MAX: the last unit's reads past its row)
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int r0 = blockIdx.x * TF, D = Q.D, d1 = Q.d1, d2 = D - d1;
+    const int r0 = blockIdx.x * TC, D = Q.D, d1 = Q.d1, d2 = D - d1;
     const long long RD = (long long)Q.R * D, RH = (long long)Q.R * H;
-    float ld_acc = 0.0f;                                     // threads t < TF: log|det| of row r0 + t, summed as the layers go
+    float ld_acc = 0.0f;                                     // threads t < TC: log|det| of row r0 + t, summed as the layers go
     STAMP(0);
-    // one thread's share of the next half-layer's weights (plain local arrays indexed by unrolled constants: registers)
-    f32x4 nw2[H * H / 4 / NT];           // (the compiler's own vector type: HIP's float4 struct kept the array in memory)
-    float nw1[H * DI_MAX / NT], nw3[M_MAX * H / NT], nb10, nb11, nb20, nb21, nb3s, nb3t, nsc = 0.0f, nbi = 0.0f;
-#define NDDM_FETCH_WEIGHTS(Wn, DIn, Mn) do {                                                                                  \
-        const f32x4 *src_ = reinterpret_cast<const f32x4 *>((Wn).W2);                                                         \
-        _Pragma("unroll") for (int k = 0; k < H * H / 4 / NT; ++k) nw2[k] = src_[t + NT * k];                                \
-        /* (coalesced; every load unconditional, from a clamped address: a guarded load is a branch and a block of its own) */     \
-        _Pragma("unroll") for (int k = 0; k < H * DI_MAX / NT; ++k) nw1[k] = (Wn).W1[min(t + NT * k, H * (DIn) - 1)];          \
-        _Pragma("unroll") for (int k = 0; k < M_MAX * H / NT; ++k) {                                                          \
-            const int p_ = t + NT * k; const float v_ = (Wn).W3[min(p_, (Mn) * H - 1)]; nw3[k] = p_ < (Mn) * H ? v_ : 0.0f; } \
-        nb10 = (Wn).b1[UW * w + (lane & 15)]; nb11 = (Wn).b1[min(UW * w + 16, H - 16) + (lane & 15)];                                \
-        nb20 = (Wn).b2[UW * w + (lane & 15)]; nb21 = (Wn).b2[min(UW * w + 16, H - 16) + (lane & 15)];                     \
-        {   const int Dt_ = (Mn) / 2, d_ = t % Dt_; nb3s = (Wn).b3[d_]; nb3t = (Wn).b3[Dt_ + d_]; }    /* thread (row t / Dt, column t % Dt) of the affine phase */ \
+    // one thread's share of the next half-layer's weights and biases: its unit's (16 w + (lane & 15)) of layers 1 and 2, its column's
+    // of the affine phase, thread (row t / Dt, column t % Dt)
+    // (plain local arrays indexed by unrolled constants: registers; f32x4 is the compiler's own vector type -- HIP's float4 struct kept
+    //  the array in memory.  Every load unconditional, from a clamped address: a guarded load is a branch and a block of its own.)
+    // The prefetch stays a literal macro, here and in the two other kernels that have one: as member functions of small structs,
+    // as free functions over the arrays and as an always_inline lambda it was measured and each form cost this kernel code --
+    // 1583 instructions as a macro, 1603 with the loops in helpers, 1642 with the helpers in a by-reference lambda, two SGPRs
+    // spilled to VGPR lanes either way, and 0.9 % of the kernel's time (profiles/r29_flow_refactor_ab.txt).
+    f32x4 nw2[H * H / 4 / NC];
+    float nw1[H * DI_MAX / NC], nw3[M_MAX * H / NC], nb1, nb2, nb3s, nb3t, nsc = 0.0f, nbi = 0.0f;
+#define NDDM_FETCH_FWD(Wn_, Gn_) do {                                                                                         \
+        const HalfP &Wn = (Wn_); const HalfShape Gn = (Gn_);                                                                  \
+        const f32x4 *src_ = reinterpret_cast<const f32x4 *>(Wn.W2);                                                           \
+        _Pragma("unroll") for (int k = 0; k < H * H / 4 / NC; ++k) nw2[k] = src_[t + NC * k];      /* (coalesced) */           \
+        _Pragma("unroll") for (int k = 0; k < H * DI_MAX / NC; ++k) nw1[k] = Wn.W1[min(t + NC * k, H * Gn.DI - 1)];            \
+        _Pragma("unroll") for (int k = 0; k < M_MAX * H / NC; ++k) {                                                          \
+            const int p_ = t + NC * k; const float v_ = Wn.W3[min(p_, Gn.M * H - 1)]; nw3[k] = p_ < Gn.M * H ? v_ : 0.0f; }   \
+        nb1 = Wn.b1[16 * w + (lane & 15)];                                                                                    \
+        nb2 = Wn.b2[16 * w + (lane & 15)];                                                                                    \
+        nb3s = Wn.b3[t % Gn.Dt]; nb3t = Wn.b3[Gn.Dt + t % Gn.Dt];                                                             \
     } while (0)
-    NDDM_FETCH_WEIGHTS(P.layer[0].a, d1 + Q.C, 2 * d2);
-    if (t < TF * D) { const int p = P.perm[0][t % D]; nsc = P.layer[0].scale[p]; nbi = P.layer[0].bias[p]; }
-    for (int p = t; p < (16 - TF) * H; p += NT) h1r[TF + (p >> 7)][p & (H - 1)] = 0.0f;
-    for (int p = t; p < 16 * (DI_MAX + 2); p += NT) in_s[p] = 0.0f;
-    for (int p = H * DI_MAX + t; p < H * DI_MAX + DI_MAX; p += NT) w1f[p] = 0.0f;
-    if (t < TF * D) { const int r = t / D, c = t - r * D; xs[0][r][c] = r0 + r < Q.R ? theta[(long long)(r0 + r) * D + c] : 0.0f; }
-    if (t < TF * Q.C) { const int r = t / Q.C, c = t - r * Q.C; cs[r][c] = r0 + r < Q.R ? cond[(long long)(r0 + r) * Q.C + c] : 0.0f; }
+    NDDM_FETCH_FWD(P.layer[0].a, half_shape(d1, d2, Q.C, false));
+    if (t < TC * D) { const int p = P.perm[0][t % D]; nsc = P.layer[0].scale[p]; nbi = P.layer[0].bias[p]; }
+    for (int p = t; p < TC * (DI_MAX + 2); p += NC) in_s[p] = 0.0f;
+    for (int p = H * DI_MAX + t; p < H * DI_MAX + DI_MAX; p += NC) w1f[p] = 0.0f;
+    if (t < TC * D) { const int r = t / D, c = t - r * D; xs[0][r][c] = r0 + r < Q.R ? theta[(long long)(r0 + r) * D + c] : 0.0f; }
+    if (t < TC * Q.C) { const int r = t / Q.C, c = t - r * Q.C; cs[r][c] = r0 + r < Q.R ? cond[(long long)(r0 + r) * Q.C + c] : 0.0f; }
     for (int hl = 0; hl < 2 * Q.L; ++hl) {
         const int l = hl >> 1;
         const bool second = hl & 1;
         const LayerP &Y = P.layer[l];
-        const HalfP &W = second ? Y.b : Y.a;
-        const int Dh = second ? d2 : d1, Dt = second ? d1 : d2, DI = Dh + Q.C, M = 2 * Dt;
+        const HalfShape G = half_shape(d1, d2, Q.C, second);
+        const int Dh = G.Dh, Dt = G.Dt, DI = G.DI;
         float *z_g = S.z_all + l * RD, *out_g = S.out_all + l * RD, *sl = S.s_all + l * RD + (second ? d2 : 0), *h = S.h_all + 4 * l * RH;
         float *h1_out = h + (second ? 2 : 0) * RH, *h2_out = h + (second ? 3 : 1) * RH;
         float (*xin)[D_MAX] = xs[l & 1], (*xout)[D_MAX] = xs[(l & 1) ^ 1];
@@ -115,27 +111,26 @@ __global__ __launch_bounds__(NT) void flow_fwd_kernel(FlowDims Q, FlowP P, const
         // this half-layer's weights: out of the registers (fetched a half-layer ago) into LDS / this thread's W1 row
         lds_barrier();                                     // (the previous half-layer's readers of w2s, w3s, xs are done)
 #pragma unroll
-        for (int k = 0; k < H * H / 4 / NT; ++k) { const int p4 = t + NT * k; *reinterpret_cast<f32x4 *>(&w2s[p4 >> 5][4 * (p4 & 31)]) = nw2[k]; }
+        for (int k = 0; k < H * H / 4 / NC; ++k) { const int p4 = t + NC * k; *reinterpret_cast<f32x4 *>(&w2s[p4 >> 5][4 * (p4 & 31)]) = nw2[k]; }
 #pragma unroll
-        for (int k = 0; k < M_MAX * H / NT; ++k) { const int p = t + NT * k; w3s[p >> 7][p & (H - 1)] = nw3[k]; }
+        for (int k = 0; k < M_MAX * H / NC; ++k) { const int p = t + NC * k; w3s[p >> 7][p & (H - 1)] = nw3[k]; }
 #pragma unroll
-        for (int k = 0; k < H * DI_MAX / NT; ++k) w1f[t + NT * k] = nw1[k];    // (entries beyond H * DI: copies of the last one, finite)
-        const float b10 = nb10, b11 = nb11, b20 = nb20, b21 = nb21, b3s = nb3s, b3t = nb3t, scv = nsc, biv = nbi;
+        for (int k = 0; k < H * DI_MAX / NC; ++k) w1f[t + NC * k] = nw1[k];    // (entries beyond H * DI: copies of the last one, finite)
+        const float b1 = nb1, b2 = nb2, b3s = nb3s, b3t = nb3t, scv = nsc, biv = nbi;
         STAMP(7);
         if (hl + 1 < 2 * Q.L) {                              // ... and the next one's into the registers
-            const HalfP &Wn = second ? P.layer[l + 1].a : Y.b;
-            NDDM_FETCH_WEIGHTS(Wn, (second ? d1 : d2) + Q.C, 2 * (second ? d2 : d1));
-            if (second && t < TF * D) { const int p = P.perm[l + 1][t % D]; nsc = P.layer[l + 1].scale[p]; nbi = P.layer[l + 1].bias[p]; }
+            NDDM_FETCH_FWD(second ? P.layer[l + 1].a : Y.b, half_shape(d1, d2, Q.C, !second));
+            if (second && t < TC * D) { const int p = P.perm[l + 1][t % D]; nsc = P.layer[l + 1].scale[p]; nbi = P.layer[l + 1].bias[p]; }
         }
         STAMP(8);
         if (!second) {
-            if (t < TF * D) {                               // ActNorm, then the permutation: z[:, c] = u[:, perm[c]]
+            if (t < TC * D) {                             // ActNorm, then the permutation: z[:, c] = u[:, perm[c]]
                 const int r = t / D, c = t - r * D, p = P.perm[l][c];
                 const float v = fmaf(xin[r][p], expf(scv), biv);
                 zs[r][c] = v;
                 bz.put(r * D + c, v);
             }
-            if (t < TF) {
+            if (t < TC) {
 #pragma unroll
                 for (int d = 0; d < D_MAX; ++d) if (d < D) ld_acc += Y.scale[d];
             }
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(NT) void flow_fwd_kernel(FlowDims Q, FlowP P, const
         // first:  conditioned on z[:, :d1], transforms z[:, d1:] -> out[:, d1:], log-scales -> s[:, :d2]
         // second: conditioned on out[:, d1:], transforms z[:, :d1] -> out[:, :d1], log-scales -> s[:, d2:]
         const int ild = DI_MAX + 1 + (~DI & 1);           // in_s row stride: 33 (DI odd) or 34 (DI even)
-        for (int p = t; p < TF * DI_MAX; p += NT) {        // (every column: those >= DI are zeros -- they meet the next unit's weights in layer 1)
+        for (int p = t; p < TC * DI_MAX; p += NC) {        // (every column: those >= DI are zeros -- they meet the next unit's weights in layer 1)
             const int r = p >> 5, c = p & (DI_MAX - 1);
             in_s[r * ild + c] = c < Dh ? (second ? xout[r][d1 + c] : zs[r][c]) : c < DI ? cs[r][c - Dh] : 0.0f;
         }
@@ -157,103 +152,31 @@ __global__ __launch_bounds__(NT) void flow_fwd_kernel(FlowDims Q, FlowP P, const
             // 15 each): DI odd -- group kk takes 8 kb + i (kb = 0, 2, 1, 3): W1 banks DI n + 16 kk + i, inputs (stride 33) n + 16 kk + i, all
             // 32 distinct; DI even -- group kk takes 4 i + kk: W1 banks DI n + kk + 4 i, inputs (stride 34) 2 n + kk + 4 i, all distinct
             const int n = lane & 15, kk = lane >> 4, odd = DI & 1;
-            const int k0 = odd ? 8 * (((kk & 1) << 1) | (kk >> 1)) : kk;
-            const float *ap = &in_s[n * ild + k0], *bp0 = &w1f[(UW * w + n) * DI + k0], *bp1 = &w1f[(min(UW * w + 16, H - 16) + n) * DI + k0];
-            f32x4 acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = acc0;
+            const int k0 = odd ? 8 * kblock(kk) : kk;
+            const float *ap = &in_s[n * ild + k0], *bp = &w1f[(16 * w + n) * DI + k0];
+            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
             if (odd) {                                       // (two copies: the reads' offsets are then immediates)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float a = ap[i];
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp0[i], acc0, 0, 0, 0);
-                    if constexpr (UW == 32) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp1[i], acc1, 0, 0, 0);
-                }
+                for (int i = 0; i < 8; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[i], bp[i], acc, 0, 0, 0);
             } else {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float a = ap[4 * i];
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp0[4 * i], acc0, 0, 0, 0);
-                    if constexpr (UW == 32) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp1[4 * i], acc1, 0, 0, 0);
-                }
+                for (int i = 0; i < 8; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[4 * i], bp[4 * i], acc, 0, 0, 0);
             }
-            if (kk < TF / 4) {                               // D: unit = tile base + (l & 15), row = 4 (l >> 4) + register
-                const int u0 = UW * w + n, u1 = u0 + 16;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int r = 4 * kk + q;
-                    const float a0 = acc0[q] + b10, v0 = elu(a0);
-                    h1r[r][u0] = v0;
-                    bh1.put(r * H + u0, a0);
-                    if constexpr (UW == 32) {
-                        const float a1 = acc1[q] + b11, v1 = elu(a1);
-                        h1r[r][u1] = v1;
-                        bh1.put(r * H + u1, a1);
-                    }
-                }
-            }
+            mfma_epilogue_elu(acc, b1, kk, 16 * w + n, h1r, bh1);
         }
         lds_barrier();
         STAMP(2);
-        {   // layer 2: wave w owns units [32 w, 32 w + 32) as two 16 x 16 tiles (two independent accumulators);
-            // lane l: A[row l & 15][k] = h1[row][k], B[k][unit l & 15] = W2[unit][k] for the k's 32 (l >> 4) + s, s = 0 .. 31
-            // (which 32 k's a lane group takes is free -- the MFMA sums over all four groups -- and it decides the LDS banks: ds_read_b128
-            //  serves lanes {0-3, 12-15, 20-27} together, i.e. rows n of group 0 with rows n' of group 1, on 64 banks = 16 slots of 16
-            //  bytes; with a row stride of 33 slots, groups 0 and 1 must start a multiple of 16 slots = 64 floats apart, not 32, or
-            //  every read is a 2-way conflict: groups 0, 1, 2, 3 take the k blocks 0, 2, 1, 3)
-            const int n = lane & 15, kk = lane >> 4, kb = ((kk & 1) << 1) | (kk >> 1);
-            f32x4 acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = acc0;
-            const float4 *ap = reinterpret_cast<const float4 *>(&h1r[n][32 * kb]);
-            const float4 *bp0 = reinterpret_cast<const float4 *>(&w2s[UW * w + n][32 * kb]);
-            const float4 *bp1 = reinterpret_cast<const float4 *>(&w2s[min(UW * w + 16, H - 16) + n][32 * kb]);
-            if constexpr (UW == 32) {
-#pragma unroll
-                for (int q4 = 0; q4 < 8; ++q4) {
-                    const float4 a = ap[q4], b0 = bp0[q4], b1 = bp1[q4];
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0.x, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b1.x, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b0.y, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1.y, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b0.z, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b1.z, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b0.w, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b1.w, acc1, 0, 0, 0);
-                }
-            } else {                                         // one tile per wave: the even and the odd groups of four k's in two accumulators
-#pragma unroll
-                for (int q4 = 0; q4 < 8; q4 += 2) {
-                    const float4 a0 = ap[q4], b0 = bp0[q4], a1 = ap[q4 + 1], b1 = bp0[q4 + 1];
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b0.x, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b1.x, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b0.y, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b1.y, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b0.z, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b1.z, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b0.w, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1.w, acc1, 0, 0, 0);
-                }
-                acc0 += acc1;
-            }
-            // D: unit = tile base + (l & 15), row = 4 (l >> 4) + register: rows < TF live in lanes 0..31
-            if (kk < TF / 4) {
-                const int u0 = UW * w + n, u1 = u0 + 16;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int r = 4 * kk + q;
-                    const float a0 = acc0[q] + b20, v0 = elu(a0);
-                    h2r[r][u0] = v0;
-                    bh2.put(r * H + u0, a0);
-                    if constexpr (UW == 32) {
-                        const float a1 = acc1[q] + b21, v1 = elu(a1);
-                        h2r[r][u1] = v1;
-                        bh2.put(r * H + u1, a1);
-                    }
-                }
-            }
+        {   // layer 2: wave w owns the units [16 w, 16 w + 16), one 16 x 16 tile; lane l: A[row l & 15][k] = h1[row][k], B[k][unit l & 15]
+            // = W2[unit][k] for the k's [32 kb, 32 kb + 32), kb = kblock(l >> 4)
+            const int n = lane & 15, kk = lane >> 4, kb = kblock(kk);
+            const f32x4 acc = mfma_k128(reinterpret_cast<const float4 *>(&h1r[n][32 * kb]), reinterpret_cast<const float4 *>(&w2s[16 * w + n][32 * kb]));
+            mfma_epilogue_elu(acc, b2, kk, 16 * w + n, h2r, bh2);
         }
         lds_barrier();
         STAMP(3);
         {   // layer 3, [16 rows x H] x [H x 16 outputs] as MFMAs with the H units split over the waves (16 each: four MFMAs, lane group
             // kk takes the units 16 w + 4 i + kk); the waves' partial tiles are summed, in fixed order, by the affine phase's threads
-            constexpr int KW = H / (NT / 64);
+            constexpr int KW = H / (NC / 64);
             const int n = lane & 15, kk = lane >> 4;
             const float *ap = &h2r[n][KW * w + kk], *bp = &w3s[n][KW * w + kk];
             f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -264,28 +187,29 @@ __global__ __launch_bounds__(NT) void flow_fwd_kernel(FlowDims Q, FlowP P, const
         }
         lds_barrier();
         STAMP(4);
-        if (t < TF * Dt) {                                  // the outputs' sums, soft clamp + affine transform
+        if (t < TC * Dt) {                                  // the outputs' sums, soft clamp + affine transform
             const int r = t / Dt, d = t - r * Dt, row = r0 + r;
             float os = b3s, ot = b3t;
 #pragma unroll
-            for (int v = 0; v < NT / 64; ++v) { os += part3[v][r][d]; ot += part3[v][r][Dt + d]; }
-            const float sv = Q.clamp * tanhf(os / Q.clamp);
-            const float yv = fmaf(second ? zs[r][d] : zs[r][d1 + d], expf(sv), ot);
-            xout[r][second ? d : d1 + d] = yv;
+            for (int v = 0; v < NC / 64; ++v) { os += part3[v][r][d]; ot += part3[v][r][Dt + d]; }
+            const float sv = soft_clamp(os, Q.clamp);
+            const float yv = fmaf(zs[r][G.xt0 + d], expf(sv), ot);
+            xout[r][G.xt0 + d] = yv;
             o_s[r][d] = sv;                                  // (for the rows' log|det| below)
             if (row < Q.R) {
                 sl[(long long)row * D + d] = sv;
-                out_g[(long long)row * D + (second ? d : d1 + d)] = yv;
+                out_g[(long long)row * D + G.xt0 + d] = yv;
             }
         }
         lds_barrier();
-        if (t < TF) {
+        if (t < TC) {
 #pragma unroll
             for (int d = 0; d < M_MAX / 2; ++d) if (d < Dt) ld_acc += o_s[t][d];
         }
         STAMP(5);
     }
-    if (t < TF && r0 + t < Q.R) ld[r0 + t] = ld_acc;        // log|det| of the row: every log-scale, and the ActNorms'
+#undef NDDM_FETCH_FWD
+    if (t < TC && r0 + t < Q.R) ld[r0 + t] = ld_acc;       // log|det| of the row: every log-scale, and the ActNorms'
     STAMP(6);
 }
 
@@ -308,7 +232,6 @@ constexpr int LDT = H + 4;       // row stride of W2 TRANSPOSED in LDS, w2t[in u
 struct HalfD {                   // one half-layer of kernel (1), resolved by the host
     const float *xtr, *W1, *W2, *W3, *s, *h1, *h2;       // xtr, s: [R, .] slices with row stride D (saved by the forward)
     float *da2, *da1, *dos;      // da2, da1 [R, H], dos [R, M_MAX]: for kernel (2)
-    int Dh, Dt;
 };
 struct NormD { const float *scale; float *gz; unsigned char perm[D_MAX]; };      // gz [R, D]: d(permuted ActNorm output), for kernel (2)
 struct FlowD { HalfD half[2 * L_MAX]; NormD norm[L_MAX]; };
@@ -324,83 +247,85 @@ struct FlowBwdBuf {
 // What a row carries from half-layer to half-layer (the gradients of the layer's output, of its permuted ActNorm output, of the
 // condition) stays in LDS, the next half-layer's weights and saved activations are fetched into registers a half-layer ahead, and
 // the barriers order LDS traffic only (nothing here reads global memory that the kernel wrote): as in the forward.
-template <int TRD, int NTD>      // rows per workgroup, threads: 32 x 1024 (one CU takes all of batch 32) or 16 x 512 (two CUs: full 16-row MFMA tiles each)
-__global__ __launch_bounds__(NTD) void flow_dgrad_kernel(FlowDims Q, FlowD T, FlowBwdBuf U)
+__global__ __launch_bounds__(NC) void flow_dgrad_kernel(FlowDims Q, FlowD T, FlowBwdBuf U)
 {
-    constexpr int G = NTD / H;        // thread t = (unit j = t % H, group g = t / H): a group takes rows 4 g .. 4 g + 3 in the VALU phases
-    static_assert(TRD == 4 * G && TRD % 16 == 0 && NTD / 64 == 8 * (TRD / 16), "one wave per 16 x 16 tile of the [TRD, H] MFMA phase");
-    __shared__ __attribute__((aligned(16))) float h1r[TRD][LDR];        // [row][unit]
-    __shared__ __attribute__((aligned(16))) float h2r[TRD][LDR];        // later: d(pre-activation 1)
-    __shared__ __attribute__((aligned(16))) float da2r[TRD][LDR];       // d(pre-activation 2); later: partial tiles of the input gradient
-    __shared__ float do_s[TRD][M_MAX + 1];      // d(outputs): an MFMA operand read a dword at a time down the rows (+ 1: banks)
+    constexpr int G = NC / H;         // thread t = (unit j = t % H, group g = t / H): a group takes rows 4 g .. 4 g + 3 in the VALU phases
+    static_assert(TC == 4 * G && TC == 16 && NC / 64 == H / 16, "one wave per 16 x 16 tile of the [16, H] MFMA phases");
+    __shared__ __attribute__((aligned(16))) float h1r[TC][LDR];         // [row][unit]
+    __shared__ __attribute__((aligned(16))) float h2r[TC][LDR];         // later: d(pre-activation 1)
+    __shared__ __attribute__((aligned(16))) float da2r[TC][LDR];        // d(pre-activation 2); later: partial tiles of the input gradient
+    __shared__ float do_s[TC][M_MAX + 1];       // d(outputs): an MFMA operand read a dword at a time down the rows (+ 1: banks)
     __shared__ __attribute__((aligned(16))) float w2t[H][LDT];
     __shared__ float w1f[H * DI_MAX + DI_MAX];  // W1 as it lies in memory, [unit][DI] (+ DI_MAX: the last units' reads past their rows)
     __shared__ float w3s[M_MAX][H + 16];        // W3 [output][unit], rows >= M zero (+ 16: lane groups 0 and 1 read rows m, m + 1: banks 16 apart)
-    __shared__ float gout_s[TRD][D_MAX], gz_s[TRD][D_MAX], gy2_s[TRD][D_MAX], gcond_s[TRD][DI_MAX];
+    __shared__ float gout_s[TC][D_MAX], gz_s[TC][D_MAX], gy2_s[TC][D_MAX], gcond_s[TC][DI_MAX];
     const int t = threadIdx.x, j = t & (H - 1), g = t >> 7, lane = t & 63, wave = t >> 6, D = Q.D, d1 = Q.d1, d2 = D - d1;
-    const int r0 = blockIdx.x * TRD;
-    // this thread's (row, column) of the affine phase: rows 0 .. TRD - 1 x up to M_MAX / 2 columns
+    const int r0 = blockIdx.x * TC;
     float gld_sc = 0.0f;                                     // nll form: the uniform gradient of log|det|
     if (U.g_nll) gld_sc = -*U.g_nll / (float)Q.R;
-    if (t < TRD * D) {
+    if (t < TC * D) {
         const int r = t / D, c = t - r * D, row = r0 + r;
         float v = 0.0f;
         if (row < Q.R) v = U.g_nll ? U.z_last[(long long)row * D + c] * (-gld_sc) : U.g_z[(long long)row * D + c];
         gout_s[r][c] = v;
     }
-    if (U.g_nll && t < TRD && r0 + t < Q.R) U.w_gld[r0 + t] = gld_sc;
-    for (int p = t; p < TRD * DI_MAX; p += NTD) (&gcond_s[0][0])[p] = 0.0f;
-    for (int p = t; p < TRD * (M_MAX + 1); p += NTD) (&do_s[0][0])[p] = 0.0f;      // (columns >= M are never written: they meet zero rows of w3s)
-    // one thread's share of the next half-layer's operands
-    f32x4 nw2[H * H / 4 / NTD];       // thread (in unit j, g): out units 4 (g + G k4) .. + 3 of column j
-    float nw1[H * DI_MAX / NTD], nw3[M_MAX * H / NTD], nh1[TRD * H / NTD], nh2[TRD * H / NTD], ns = 0.0f, nx = 0.0f, ngl = 0.0f;
-#define NDDM_FETCH_HALF(X) do {                                                                                               \
-        const int DIn_ = (X).Dh + Q.C, Mn_ = 2 * (X).Dt;                                                                       \
-        _Pragma("unroll") for (int k4 = 0; k4 < H * H / 4 / NTD; ++k4) {          /* (a wave: 64 consecutive floats of a row) */      \
-            const float *w_ = (X).W2 + (long long)(4 * (g + G * k4)) * H + j;                                                    \
-            nw2[k4] = f32x4{w_[0], w_[H], w_[2 * H], w_[3 * H]}; }                                                              \
-        _Pragma("unroll") for (int k = 0; k < H * DI_MAX / NTD; ++k) nw1[k] = (X).W1[min(t + NTD * k, H * DIn_ - 1)];          \
-        _Pragma("unroll") for (int k = 0; k < M_MAX * H / NTD; ++k) {                                                          \
-            const int p_ = t + NTD * k; const float v_ = (X).W3[min(p_, Mn_ * H - 1)]; nw3[k] = p_ < Mn_ * H ? v_ : 0.0f; }      \
-        _Pragma("unroll") for (int k = 0; k < TRD * H / NTD; ++k) {                                                             \
+    if (U.g_nll && t < TC && r0 + t < Q.R) U.w_gld[r0 + t] = gld_sc;
+    for (int p = t; p < TC * DI_MAX; p += NC) (&gcond_s[0][0])[p] = 0.0f;
+    for (int p = t; p < TC * (M_MAX + 1); p += NC) (&do_s[0][0])[p] = 0.0f;      // (columns >= M are never written: they meet zero rows of w3s)
+    // one thread's share of the next half-layer's operands: W2 TRANSPOSED is this kernel's own (thread (in unit j, g): the out units
+    // 4 (g + G k4) .. + 3 of column j; a wave: 64 consecutive floats of a row), the saved activations of its rows, and what thread
+    // (row t / Dt, column t % Dt) of the affine phase needs
+    f32x4 nw2[H * H / 4 / NC];
+    float nw1[H * DI_MAX / NC], nw3[M_MAX * H / NC], nh1[TC * H / NC], nh2[TC * H / NC], ns = 0.0f, nx = 0.0f, ngl = 0.0f;
+#define NDDM_FETCH_DGRAD(hn_) do {              /* (a literal macro: see the forward's) */                                     \
+        const HalfD &Xn = T.half[hn_];                                                                                         \
+        const HalfShape Gn = half_shape(d1, d2, Q.C, (hn_) & 1);                                                               \
+        _Pragma("unroll") for (int k4 = 0; k4 < H * H / 4 / NC; ++k4) {                                                        \
+            const float *w_ = Xn.W2 + (long long)(4 * (g + G * k4)) * H + j;                                                   \
+            nw2[k4] = f32x4{w_[0], w_[H], w_[2 * H], w_[3 * H]}; }                                                             \
+        _Pragma("unroll") for (int k = 0; k < H * DI_MAX / NC; ++k) nw1[k] = Xn.W1[min(t + NC * k, H * Gn.DI - 1)];            \
+        _Pragma("unroll") for (int k = 0; k < M_MAX * H / NC; ++k) {                                                           \
+            const int p_ = t + NC * k; const float v_ = Xn.W3[min(p_, Gn.M * H - 1)]; nw3[k] = p_ < Gn.M * H ? v_ : 0.0f; }    \
+        _Pragma("unroll") for (int k = 0; k < TC * H / NC; ++k) {                                                              \
             const long long o_ = (long long)min(r0 + g + G * k, Q.R - 1) * H + j;                                              \
-            nh1[k] = (X).h1[o_]; nh2[k] = (X).h2[o_];                                                                          \
+            nh1[k] = Xn.h1[o_]; nh2[k] = Xn.h2[o_];                                                                            \
         }                                                                                                                      \
-        {   const int r_ = t / (X).Dt, d_ = t - r_ * (X).Dt; const long long o_ = (long long)min(r0 + min(r_, TRD - 1), Q.R - 1) * D + d_; \
-            ns = (X).s[o_]; nx = (X).xtr[o_]; ngl = U.g_nll ? gld_sc : U.g_ld[min(r0 + min(r_, TRD - 1), Q.R - 1)]; }           \
+        {   const int r_ = t / Gn.Dt, d_ = t - r_ * Gn.Dt; const long long o_ = (long long)min(r0 + min(r_, TC - 1), Q.R - 1) * D + d_; \
+            ns = Xn.s[o_]; nx = Xn.xtr[o_]; ngl = U.g_nll ? gld_sc : U.g_ld[min(r0 + min(r_, TC - 1), Q.R - 1)]; }              \
     } while (0)
-    NDDM_FETCH_HALF(T.half[2 * Q.L - 1]);
+    NDDM_FETCH_DGRAD(2 * Q.L - 1);
     for (int hl = 2 * Q.L - 1; hl >= 0; --hl) {
         const HalfD &X = T.half[hl];
         const bool second = hl & 1;
-        const int DI = X.Dh + Q.C, M = 2 * X.Dt, Dt = X.Dt;
+        const HalfShape S = half_shape(d1, d2, Q.C, second);
+        const int DI = S.DI, Dt = S.Dt;
         const RowBuf bda2(X.da2 + (long long)r0 * H, Q.R - r0, H), bda1(X.da1 + (long long)r0 * H, Q.R - r0, H);
         lds_barrier();                    // the previous half-layer's readers are done
         STAMP(10);
 #pragma unroll
-        for (int k4 = 0; k4 < H * H / 4 / NTD; ++k4) *reinterpret_cast<f32x4 *>(&w2t[j][4 * (g + G * k4)]) = nw2[k4];
+        for (int k4 = 0; k4 < H * H / 4 / NC; ++k4) *reinterpret_cast<f32x4 *>(&w2t[j][4 * (g + G * k4)]) = nw2[k4];
 #pragma unroll
-        for (int k = 0; k < H * DI_MAX / NTD; ++k) w1f[t + NTD * k] = nw1[k];      // (a linear copy; entries beyond H * DI: copies of the last one)
+        for (int k = 0; k < H * DI_MAX / NC; ++k) w1f[t + NC * k] = nw1[k];       // (a linear copy; entries beyond H * DI: copies of the last one)
 #pragma unroll
-        for (int k = 0; k < M_MAX * H / NTD; ++k) { const int p = t + NTD * k; w3s[p >> 7][p & (H - 1)] = nw3[k]; }
+        for (int k = 0; k < M_MAX * H / NC; ++k) { const int p = t + NC * k; w3s[p >> 7][p & (H - 1)] = nw3[k]; }
 #pragma unroll
-        for (int k = 0; k < TRD * H / NTD; ++k) {         // saved activations (rows beyond R: zero)
+        for (int k = 0; k < TC * H / NC; ++k) {           // saved activations (rows beyond R: zero)
             const int r = g + G * k;
             const bool ok = r0 + r < Q.R;
             h1r[r][j] = ok ? nh1[k] : 0.0f;
             h2r[r][j] = ok ? nh2[k] : 0.0f;
         }
         STAMP(15);
-        if (t < TRD * Dt) {                               // through the affine transform and the soft clamp
+        if (t < TC * Dt) {                             // through the affine transform and the soft clamp
             const int r = t / Dt, d = t - r * Dt, row = r0 + r;
             // second: the gradient of out[:, :d1]; first: of out[:, d1:] plus what came through net 2's conditioning input
-            const float gg = second ? gout_s[r][d] : gout_s[r][d1 + d] + gy2_s[r][d];
+            const float gg = second ? gout_s[r][S.xt0 + d] : gout_s[r][S.xt0 + d] + gy2_s[r][d];
             // d s / d o = 1 - tanh^2 = (clamp - s)(clamp + s) / clamp^2: the DIFFERENCE clamp - s is exact where it matters (a log-scale
             // near the clamp's bound: Sterbenz), whereas 1 - (s / clamp)^2 rounds the quotient and its square first -- three times
             // PyTorch's error on saturated units (it keeps tanh's own output), and a sharply trained flow sits at the bound
             const float es = expf(ns), dclamp = (Q.clamp - ns) * (Q.clamp + ns) / (Q.clamp * Q.clamp);
             const float d_os = row < Q.R ? fmaf(gg * nx, es, ngl) * dclamp : 0.0f, d_t = row < Q.R ? gg : 0.0f;
-            gz_s[r][second ? d : d1 + d] = gg * es;      // d z of the transformed half (the other half: the input gradient below)
+            gz_s[r][S.xt0 + d] = gg * es;     // d z of the transformed half (the other half: the input gradient below)
             do_s[r][d] = d_os;
             do_s[r][Dt + d] = d_t;
             if (row < Q.R) {
@@ -409,79 +334,49 @@ __global__ __launch_bounds__(NTD) void flow_dgrad_kernel(FlowDims Q, FlowD T, Fl
             }
         }
         STAMP(16);
-        if (hl > 0) NDDM_FETCH_HALF(T.half[hl - 1]);     // (the loads' results are not waited for before the next half-layer)
+        if (hl > 0) NDDM_FETCH_DGRAD(hl - 1);                       // (the loads' results are not waited for before the next half-layer)
         STAMP(17);
         lds_barrier();
         STAMP(11);
-        {   // d h2 = d(outputs) W3 -> d(pre-activation 2), [TRD x 16] x [16 x H] as MFMAs (outputs >= M: zero rows of w3s): wave ->
-            // (row block, 16 units), lane group kk takes the outputs 4 i + kk
-            const int n = lane & 15, kk = lane >> 4, rb = wave >> 3, ib = wave & 7;
-            const float *ap = &do_s[16 * rb + n][kk], *bp = &w3s[kk][16 * ib + n];
+        {   // d h2 = d(outputs) W3 -> d(pre-activation 2), [16 x 16] x [16 x H] as MFMAs (outputs >= M: zero rows of w3s): wave -> 16
+            // units, lane group kk takes the outputs 4 i + kk
+            const int n = lane & 15, kk = lane >> 4;
+            const float *ap = &do_s[n][kk], *bp = &w3s[kk][16 * wave + n];
             f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int i = 0; i < M_MAX / 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[4 * i], bp[4 * i * (H + 16)], acc, 0, 0, 0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {                    // D: unit 16 ib + (l & 15), row 16 rb + 4 (l >> 4) + register
-                const int r = 16 * rb + 4 * kk + q, i = 16 * ib + n;
-                const float v = acc[q] * elu_grad_from_pre(h2r[r][i]);
-                da2r[r][i] = v;
-                bda2.put(r * H + i, v);
-            }
+            mfma_epilogue_elu_grad(acc, kk, 16 * wave + n, h2r, da2r, bda2);
         }
         lds_barrier();
         STAMP(12);
         {   // d h1 = da2 W2 -> d(pre-activation 1).  Lane l: A[row l & 15][k] = da2[row][k], B[k][i = l & 15] = W2[k][i] = w2t[i][k] for the
-            // out units k = 32 (l >> 4) + s, s = 0 .. 31 (two accumulators: the even and the odd groups of four, a shorter dependent chain)
-            const int n = lane & 15, kk = lane >> 4, rb = wave >> 3, ib = wave & 7;
-            const int kb = ((kk & 1) << 1) | (kk >> 1);      // lane groups 0, 1, 2, 3 take the k blocks 0, 2, 1, 3: see the forward's layer 2
-            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = acc;
-            const float4 *ap = reinterpret_cast<const float4 *>(&da2r[16 * rb + n][32 * kb]);
-            const float4 *bp = reinterpret_cast<const float4 *>(&w2t[16 * ib + n][32 * kb]);
-#pragma unroll
-            for (int q4 = 0; q4 < 8; q4 += 2) {
-                const float4 a0 = ap[q4], b0 = bp[q4], a1 = ap[q4 + 1], b1 = bp[q4 + 1];
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b0.x, acc, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b1.x, acc1, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b0.y, acc, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b1.y, acc1, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b0.z, acc, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b1.z, acc1, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b0.w, acc, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1.w, acc1, 0, 0, 0);
-            }
-            acc += acc1;
-            // D: unit 16 ib + (l & 15), row 16 rb + 4 (l >> 4) + register  (h2r: its readers finished before the barrier above)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = 16 * rb + 4 * kk + q, i = 16 * ib + n;
-                const float v = acc[q] * elu_grad_from_pre(h1r[r][i]);
-                h2r[r][i] = v;
-                bda1.put(r * H + i, v);
-            }
+            // out units k in [32 kb, 32 kb + 32), kb = kblock(l >> 4)  (h2r: its readers finished before the barrier above)
+            const int n = lane & 15, kk = lane >> 4, kb = kblock(kk);
+            const f32x4 acc = mfma_k128(reinterpret_cast<const float4 *>(&da2r[n][32 * kb]), reinterpret_cast<const float4 *>(&w2t[16 * wave + n][32 * kb]));
+            mfma_epilogue_elu_grad(acc, kk, 16 * wave + n, h1r, h2r, bda1);
         }
         lds_barrier();
         STAMP(13);
-        {   // d in = d(a1) W1, [TRD x DI] with k over the H units: wave -> (row block, column block, a quarter of the k's), 8 MFMAs;
+        {   // d in = d(a1) W1, [16 x DI] with k over the H units: wave -> (column block, a quarter of the k's), 8 MFMAs;
             // the four partial tiles are summed through LDS in fixed order.  Lane l: A[row l & 15][k], B[k][column l & 15] for
             // k = 32 q + 8 (l >> 4) + s, s = 0 .. 7.  (Columns >= DI read the next unit's weights: they only reach columns >= DI of the result, which nobody reads.)
-            constexpr int RB = TRD / 16;
-            const int n = lane & 15, kk = lane >> 4, rb = wave % RB, cb = (wave / RB) & 1, q = wave / (2 * RB);
-            float (*part)[TRD][DI_MAX + 1] = reinterpret_cast<float (*)[TRD][DI_MAX + 1]>(&da2r[0][0]);    // (da2r's readers are done)
+            const int n = lane & 15, kk = lane >> 4, cb = wave & 1, q = wave >> 1;
+            float (*part)[TC][DI_MAX + 1] = reinterpret_cast<float (*)[TC][DI_MAX + 1]>(&da2r[0][0]);    // (da2r's readers are done)
             if (16 * cb < DI) {
                 f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-                const float *ap = &h2r[16 * rb + n][32 * q + 8 * kk], *bp = &w1f[(32 * q + 8 * kk) * DI + 16 * cb + n];
+                const float *ap = &h2r[n][32 * q + 8 * kk], *bp = &w1f[(32 * q + 8 * kk) * DI + 16 * cb + n];
                 const float4 a0 = *reinterpret_cast<const float4 *>(ap), a1 = *reinterpret_cast<const float4 *>(ap + 4);
                 const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
                 for (int s_ = 0; s_ < 8; ++s_) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s_], bp[s_ * DI], acc, 0, 0, 0);
 #pragma unroll
-                for (int v = 0; v < 4; ++v) part[q][16 * rb + 4 * kk + v][16 * cb + n] = acc[v];
+                for (int v = 0; v < 4; ++v) part[q][4 * kk + v][16 * cb + n] = acc[v];
             }
             lds_barrier();
-            if (t < TRD * DI) {
+            if (t < TC * DI) {
                 const int r = t / DI, c = t - r * DI;
                 const float acc = (part[0][r][c] + part[1][r][c]) + (part[2][r][c] + part[3][r][c]);
-                if (c >= X.Dh) gcond_s[r][c - X.Dh] += acc;
+                if (c >= S.Dh) gcond_s[r][c - S.Dh] += acc;
                 else if (second) gy2_s[r][c] = acc;      // net 2 is conditioned on out[:, d1:]
                 else gz_s[r][c] += acc;                  // net 1 on z[:, :d1], which net 2 also transformed
             }
@@ -491,17 +386,17 @@ __global__ __launch_bounds__(NTD) void flow_dgrad_kernel(FlowDims Q, FlowD T, Fl
         lds_barrier();
         // back through the permutation and the ActNorm (the parameters' gradients: kernel (2))
         const NormD &N = T.norm[hl >> 1];
-        if (t < TRD * D) {
+        if (t < TC * D) {
             const int r = t / D, c = t - r * D, row = r0 + r, p = N.perm[c];
             const float gv = gz_s[r][c];
             gout_s[r][p] = gv * expf(N.scale[p]);
             if (row < Q.R) N.gz[(long long)row * D + c] = gv;
         }
     }
-#undef NDDM_FETCH_HALF
+#undef NDDM_FETCH_DGRAD
     lds_barrier();
-    if (t < TRD * D) { const int r = t / D, c = t - r * D; if (r0 + r < Q.R) U.gx[(long long)(r0 + r) * D + c] = gout_s[r][c]; }
-    for (int p = t; p < TRD * Q.C; p += NTD) {
+    if (t < TC * D) { const int r = t / D, c = t - r * D; if (r0 + r < Q.R) U.gx[(long long)(r0 + r) * D + c] = gout_s[r][c]; }
+    for (int p = t; p < TC * Q.C; p += NC) {
         const int r = p / Q.C, c = p - r * Q.C;
         if (r0 + r < Q.R) U.gcond[(long long)(r0 + r) * Q.C + c] = gcond_s[r][c];
     }
@@ -692,13 +587,12 @@ int nddm_train_flow_fwd(int L, int R, int D, int d1, int C, float clamp, const v
                         const float *theta, const float *cond, float *z_all, float *out_all, float *s_all, float *h_all, float *ld,
                         float *nll, void *stream)
 {
-    if (!nddm_train_flow_supported(H, L, D, d1, C) || R <= 0) return 1;
-    for (int i = 0; i < L * D; ++i) if (perm[i] < 0 || perm[i] >= D) return 1;
+    if (!nddm_train_flow_supported(H, L, D, d1, C) || R <= 0 || !perm_ok(perm, L, D)) return 1;
     FlowP P = {};
     fill(P, L, D, params, perm);
     const FlowDims Q = {L, R, D, d1, C, clamp};
     const FlowSaved S = {z_all, out_all, s_all, h_all};
-    hipLaunchKernelGGL((flow_fwd_kernel<16, 512>), dim3((R + 15) / 16), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), Q, P, theta, cond, S, ld);
+    hipLaunchKernelGGL(flow_fwd_kernel, dim3((R + TC - 1) / TC), dim3(NC), 0, reinterpret_cast<hipStream_t>(stream), Q, P, theta, cond, S, ld);
     if (nll)
         hipLaunchKernelGGL(nll_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), out_all + (long long)(L - 1) * R * D,
                            ld, R, D, nll);
@@ -715,32 +609,35 @@ int nddm_train_flow_bwd(int L, int R, int D, int d1, int C, float clamp, const v
                         float *h_all, const float *g_z, float *g_ld, const float *g_nll, float *gz_all, float *gx, float *gcond,
                         float *work, void *stream)
 {
-    if (!nddm_train_flow_supported(H, L, D, d1, C) || R <= 0) return 1;
-    for (int i = 0; i < L * D; ++i) if (perm[i] < 0 || perm[i] >= D) return 1;
+    if (!nddm_train_flow_supported(H, L, D, d1, C) || R <= 0 || !perm_ok(perm, L, D)) return 1;
     const int d2 = D - d1;
     const long long RD = (long long)R * D, RH = (long long)R * H, RW = (long long)R * (2 * H + M_MAX);
+    FlowP P = {};
+    fill(P, L, D, params, perm);
     FlowD TD = {};
     FlowW TW = {};
     for (int l = 0; l < L; ++l) {
-        const float *const *q = reinterpret_cast<const float *const *>(params) + 14 * l;
-        float *const *g = reinterpret_cast<float *const *>(grads) + 14 * l;
+        const LayerP &Y = P.layer[l];
+        const LayerOf<float> G = layer_of<float>(grads, l);
         const float *x = l ? out_all + (l - 1) * RD : theta;
         const float *z = z_all + l * RD, *out = out_all + l * RD, *sl = s_all + l * RD, *h = h_all + 4 * l * RH;
         float *gz = gz_all + l * RD, *wa = work + (2 * l) * RW, *wb = work + (2 * l + 1) * RW;
+        const HalfShape Sa = half_shape(d1, d2, C, false), Sb = half_shape(d1, d2, C, true);
         // sub-network 2 (runs first): conditioned on out[:, d1:], transformed z[:, :d1]
-        TD.half[2 * l + 1] = {z, q[8], q[10], q[12], sl + d2, h + 2 * RH, h + 3 * RH, wb, wb + RH, wb + 2 * RH, d2, d1};
-        TW.half[2 * l + 1] = {out + d1, h + 2 * RH, h + 3 * RH, wb, wb + RH, wb + 2 * RH, g[8], g[9], g[10], g[11], g[12], g[13], d2, d1, -1, 0};
+        TD.half[2 * l + 1] = {z + Sb.xt0, Y.b.W1, Y.b.W2, Y.b.W3, sl + d2, h + 2 * RH, h + 3 * RH, wb, wb + RH, wb + 2 * RH};
+        TW.half[2 * l + 1] = {out + Sb.xh0, h + 2 * RH, h + 3 * RH, wb, wb + RH, wb + 2 * RH, G.b.W1, G.b.b1, G.b.W2, G.b.b2, G.b.W3, G.b.b3,
+                              Sb.Dh, Sb.Dt, -1, 0};
         // sub-network 1: conditioned on z[:, :d1], transformed z[:, d1:]
-        TD.half[2 * l] = {z + d1, q[2], q[4], q[6], sl, h, h + RH, wa, wa + RH, wa + 2 * RH, d1, d2};
-        TW.half[2 * l] = {z, h, h + RH, wa, wa + RH, wa + 2 * RH, g[2], g[3], g[4], g[5], g[6], g[7], d1, d2, l, 0};
-        TD.norm[l] = {q[0], gz, {}};
-        TW.norm[l] = {x, q[0], gz, g[0], g[1], {}};
-        for (int d = 0; d < D; ++d) TD.norm[l].perm[d] = TW.norm[l].perm[d] = (unsigned char)perm[l * D + d];
+        TD.half[2 * l] = {z + Sa.xt0, Y.a.W1, Y.a.W2, Y.a.W3, sl, h, h + RH, wa, wa + RH, wa + 2 * RH};
+        TW.half[2 * l] = {z + Sa.xh0, h, h + RH, wa, wa + RH, wa + 2 * RH, G.a.W1, G.a.b1, G.a.W2, G.a.b2, G.a.W3, G.a.b3, Sa.Dh, Sa.Dt, l, 0};
+        TD.norm[l] = {Y.scale, gz, {}};
+        TW.norm[l] = {x, Y.scale, gz, G.scale, G.bias, {}};
+        for (int d = 0; d < D; ++d) TD.norm[l].perm[d] = TW.norm[l].perm[d] = P.perm[l][d];
     }
     const FlowDims Q = {L, R, D, d1, C, clamp};
     const FlowBwdBuf U = {g_z, g_ld, gx, gcond, g_nll, g_ld, out_all + (long long)(L - 1) * RD};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((flow_dgrad_kernel<16, 512>), dim3((R + 15) / 16), dim3(512), 0, st, Q, TD, U);
+    hipLaunchKernelGGL(flow_dgrad_kernel, dim3((R + TC - 1) / TC), dim3(NC), 0, st, Q, TD, U);
     hipLaunchKernelGGL(flow_wgrad_kernel, dim3(2 * L), dim3(NTB), 0, st, Q, TW, cond, static_cast<const float *>(g_ld));
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }

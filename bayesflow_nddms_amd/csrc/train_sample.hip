@@ -34,8 +34,7 @@ namespace nddm_train {
 
 constexpr int TS = 128;         // draws per workgroup
 constexpr int NS = 512;         // threads per workgroup
-constexpr int LDS_R = H + 4;    // row stride of W2, W3 and the activation tile in LDS: 16-byte aligned rows, 16 consecutive rows on 16 distinct 16-byte slots
-constexpr int MS = 8;           // outputs of a sub-network at most: 2 * transformed columns, D <= 8 and d1 = D / 2
+constexpr int MS = 8;          // outputs of a sub-network at most: 2 * transformed columns, D <= 8 and d1 = D / 2
 
 struct SampleDims { int L, B, S, D, d1, C, tiles; float clamp; };
 struct SampleOut { float *theta; const float *lo, *hi; double *part; int *part_n; };    // part [B * tiles, 2 * D_MAX], part_n [B * tiles]
@@ -46,8 +45,8 @@ __global__ __launch_bounds__(H) void sample_cond_kernel(SampleDims Q, FlowP P, c
     const int hl = blockIdx.x % (2 * Q.L), b = blockIdx.x / (2 * Q.L), u = threadIdx.x;
     const bool second = hl & 1;
     const HalfP &W = second ? P.layer[hl >> 1].b : P.layer[hl >> 1].a;
-    const int Dh = second ? Q.D - Q.d1 : Q.d1;
-    const float *w = W.W1 + u * (Dh + Q.C) + Dh, *c = cond + (long long)b * Q.C;
+    const HalfShape G = half_shape(Q.d1, Q.D - Q.d1, Q.C, second);
+    const float *w = W.W1 + u * G.DI + G.Dh, *c = cond + (long long)b * Q.C;
     float acc = 0.0f;
     for (int k = 0; k < Q.C; ++k) acc = fmaf(w[k], c[k], acc);
     cb[(long long)blockIdx.x * H + u] = acc + W.b1[u];
@@ -55,9 +54,10 @@ __global__ __launch_bounds__(H) void sample_cond_kernel(SampleDims Q, FlowP P, c
 
 __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, const float *z, const float *cb, SampleOut O)
 {
-    __shared__ __attribute__((aligned(16))) float w2s[H][LDS_R];       // W2 [unit][k]
-    __shared__ __attribute__((aligned(16))) float hr[TS][LDS_R];       // h1 [row][unit], then h2 in its place
-    __shared__ __attribute__((aligned(16))) float w3s[16][LDS_R];      // W3 [output][unit]; rows >= M zero (the MFMA tile has 16 columns)
+    // (LDR, the row stride of W2, W3 and the activation tile: 16-byte aligned rows, 16 consecutive rows on 16 distinct 16-byte slots)
+    __shared__ __attribute__((aligned(16))) float w2s[H][LDR];         // W2 [unit][k]
+    __shared__ __attribute__((aligned(16))) float hr[TS][LDR];         // h1 [row][unit], then h2 in its place
+    __shared__ __attribute__((aligned(16))) float w3s[16][LDR];        // W3 [output][unit]; rows >= M zero (the MFMA tile has 16 columns)
     __shared__ float o3[TS][MS + 1];                                   // layer 3's products, [row][output]
     __shared__ float xs[2][TS][D_MAX];                                 // the rows; the other copy receives the permutation
     __shared__ float an_e[L_MAX][D_MAX], an_b[L_MAX][D_MAX];           // exp(-scale), bias of every ActNorm
@@ -70,26 +70,28 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
     const float *cb_b = cb + (long long)b * 2 * Q.L * H;
     const int u1 = t & (H - 1), rg = t >> 7;                           // layer 1: unit, group of 32 rows
     const int ub = 64 * (w >> 2) + (lane & 31), rb = 32 * (w & 3);     // layer 2: the lane's unit in the wave's first tile, the wave's first row
-    // one thread's share of the next half-layer's weights (plain local arrays indexed by unrolled constants: registers)
+    // one thread's share of the next half-layer's weights: W2 and W3 as the forward fetches them, its unit's W1 columns of the row's
+    // own part and hoisted condition number, its two units' b2, its column's b3 (thread (row t / Dt, column t % Dt) of the affine phase)
+    // (plain local arrays indexed by unrolled constants: registers.  A literal macro: see the training forward's.)
     f32x4 nw2[H * H / 4 / NS];
     float nw3[MS * H / NS], nw1[4], ncb, nb20, nb21, nb3s, nb3t;
-#define NDDM_FETCH_HALF(l_, second_) do {                                                                                      \
+#define NDDM_FETCH_SAMPLE(l_, second_) do {                                                                                    \
         const HalfP &Wn = (second_) ? P.layer[l_].b : P.layer[l_].a;                                                         \
-        const int Dhn = (second_) ? d2 : d1, Mn = 2 * ((second_) ? d1 : d2), DIn = Dhn + Q.C;                               \
+        const HalfShape Gn = half_shape(d1, d2, Q.C, (second_));                                                             \
         const f32x4 *src_ = reinterpret_cast<const f32x4 *>(Wn.W2);                                                          \
         _Pragma("unroll") for (int k = 0; k < H * H / 4 / NS; ++k) nw2[k] = src_[t + NS * k];                               \
         /* (every load unconditional, from a clamped address) */                                                             \
         _Pragma("unroll") for (int k = 0; k < MS * H / NS; ++k) {                                                            \
-            const int p_ = t + NS * k; const float v_ = Wn.W3[min(p_, Mn * H - 1)]; nw3[k] = p_ < Mn * H ? v_ : 0.0f; }     \
+            const int p_ = t + NS * k; const float v_ = Wn.W3[min(p_, Gn.M * H - 1)]; nw3[k] = p_ < Gn.M * H ? v_ : 0.0f; } \
         _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                                      \
-            const float v_ = Wn.W1[u1 * DIn + min(c, Dhn - 1)]; nw1[c] = c < Dhn ? v_ : 0.0f; }                             \
+            const float v_ = Wn.W1[u1 * Gn.DI + min(c, Gn.Dh - 1)]; nw1[c] = c < Gn.Dh ? v_ : 0.0f; }                       \
         ncb = cb_b[(2 * (l_) + ((second_) ? 1 : 0)) * H + u1];                                                               \
         nb20 = Wn.b2[ub]; nb21 = Wn.b2[ub + 32];                                                                             \
-        {   const int Dt_ = Mn / 2, d_ = t % Dt_; nb3s = Wn.b3[d_]; nb3t = Wn.b3[Dt_ + d_]; }   /* thread (row t / Dt, column t % Dt) of the affine phase */ \
+        nb3s = Wn.b3[t % Gn.Dt]; nb3t = Wn.b3[Gn.Dt + t % Gn.Dt];                                                            \
     } while (0)
-    NDDM_FETCH_HALF(Q.L - 1, true);
+    NDDM_FETCH_SAMPLE(Q.L - 1, true);
     for (int p = t; p < 2 * TS * D_MAX; p += NS) (&xs[0][0][0])[p] = 0.0f;       // (columns >= D and rows >= nvr stay zero)
-    for (int p = t; p < 8 * LDS_R; p += NS) (&w3s[8][0])[p] = 0.0f;              // (M <= 8: the rows 8 .. 15 are never written again)
+    for (int p = t; p < 8 * LDR; p += NS) (&w3s[8][0])[p] = 0.0f;                // (M <= 8: the rows 8 .. 15 are never written again)
     if (t < L_MAX * D_MAX) {
         const int l = t / D_MAX, d = t - l * D_MAX;
         const bool in = l < Q.L && d < D;
@@ -104,8 +106,8 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
     for (int k = 0; k < 2 * Q.L; ++k) {
         const int l = Q.L - 1 - (k >> 1);
         const bool second = !(k & 1);                       // sub-network 2 (conditioned on y2, un-transforms y1) runs first
-        const int Dh = second ? d2 : d1, Dt = second ? d1 : d2, M = 2 * Dt;
-        const int xh0 = second ? d1 : 0, xt0 = second ? 0 : d1;      // first conditioning / transformed column of the row
+        const HalfShape G = half_shape(d1, d2, Q.C, second);
+        const int Dh = G.Dh, Dt = G.Dt, xh0 = G.xh0, xt0 = G.xt0;
         float (*x)[D_MAX] = xs[cur];
         // this half-layer's weights: out of the registers (fetched a half-layer ago) into LDS
         lds_barrier();                                      // (the previous half-layer's readers of w2s, w3s, hr and writers of xs are done)
@@ -114,8 +116,8 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
 #pragma unroll
         for (int q = 0; q < MS * H / NS; ++q) { const int p = t + NS * q; w3s[p >> 7][p & (H - 1)] = nw3[q]; }
         const float w10 = nw1[0], w11 = nw1[1], w12 = nw1[2], w13 = nw1[3], cbv = ncb, b20 = nb20, b21 = nb21, b3s = nb3s, b3t = nb3t;
-        if (k + 1 < 2 * Q.L) {                              // ... and the next one's into the registers
-            if (second) NDDM_FETCH_HALF(l, false); else NDDM_FETCH_HALF(l - 1, true);
+        if (k + 1 < 2 * Q.L) {                              // ... and the next one's into the registers (two sites: `second` a constant in each)
+            if (second) NDDM_FETCH_SAMPLE(l, false); else NDDM_FETCH_SAMPLE(l - 1, true);
         }
         {   // layer 1: the hoisted condition part + the row's own Dh columns; thread = unit u1, rows [32 rg, 32 rg + 32)
             // (a wave reads one row at a time: broadcasts; its 64 units are consecutive words of the tile's row)
@@ -161,8 +163,8 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
         }
         lds_barrier();
         {   // layer 3, [16 rows x H] x [H x 16 outputs] per wave as v_mfma_f32_16x16x4_f32: lane group kk takes the units [32 kb, + 32),
-            // kb = 0, 2, 1, 3 (the forward's choice of banks), four at a time
-            const int n = lane & 15, kk = lane >> 4, kb = ((kk & 1) << 1) | (kk >> 1);
+            // kb = kblock(kk), four at a time, ONE accumulator (mfma_k128's two would be another sum order)
+            const int n = lane & 15, kk = lane >> 4, kb = kblock(kk);
             const float4 *ap = reinterpret_cast<const float4 *>(&hr[16 * w + n][32 * kb]);
             const float4 *bp = reinterpret_cast<const float4 *>(&w3s[n][32 * kb]);
             f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
         if (t < TS * Dt) {                                  // soft clamp + the affine inverse
             const int r = t / Dt, d = t - r * Dt;
             const float os = o3[r][d] + b3s, ot = o3[r][Dt + d] + b3t;
-            const float sv = Q.clamp * tanhf(os / Q.clamp);
+            const float sv = soft_clamp(os, Q.clamp);
             x[r][xt0 + d] = (x[r][xt0 + d] - ot) * expf(-sv);
         }
         if (!second) {                                      // the layer's two halves are undone: inverse permutation, inverse ActNorm
@@ -196,7 +198,7 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
             cur ^= 1;
         }
     }
-#undef NDDM_FETCH_HALF
+#undef NDDM_FETCH_SAMPLE
     __syncthreads();
     const float (*x)[D_MAX] = xs[cur];
     if (O.theta)
@@ -279,8 +281,7 @@ int nddm_train_flow_sample(int hidden, int L, int B, int S, int D, int d1, int C
     if (!params || !perm || !z || !cond || !work) return 1;
     if ((!theta && !sums) || (sums == nullptr) != (n_outside == nullptr) || (lo == nullptr) != (hi == nullptr)) return 1;
     const long long tiles = (S + TS - 1) / TS;
-    if ((long long)B * tiles > 0x7fffffffLL || (long long)B * 2 * L > 0x7fffffffLL) return 1;
-    for (int i = 0; i < L * D; ++i) if (perm[i] < 0 || perm[i] >= D) return 1;
+    if ((long long)B * tiles > 0x7fffffffLL || (long long)B * 2 * L > 0x7fffffffLL || !perm_ok(perm, L, D)) return 1;
     FlowP P = {};
     fill(P, L, D, params, perm);
     const SampleDims Q = {L, B, S, D, d1, C, (int)tiles, clamp};

@@ -14,13 +14,14 @@ import torch
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
+import bayesflow_nddms_amd.build as b          # noqa: E402
+
 which = sys.argv[1] if len(sys.argv) > 1 else "flow"
 block = sys.argv[2] if len(sys.argv) > 2 else "0"
 so = os.path.join(root, "tools", "_stamps.so")
-src = " ".join(os.path.join(root, "bayesflow_nddms_amd", "csrc", f) for f in ("train_kernels.hip", "train_deepset.hip", "train_update.hip"))
+src = " ".join(b.TRAIN_SOURCES)               # every source of libnddm_train.so: _train_lib.lib() binds all of its entry points
 if os.system(f"hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -DNDDM_TRAIN_STAMPS -DNDDM_STAMP_BLOCK={block} {src} -o {so} 2>/dev/null"):
     sys.exit("hipcc failed")
-import bayesflow_nddms_amd.build as b          # noqa: E402
 b.build_train = lambda *a, **k: so
 from bayesflow_nddms_amd import _train_lib     # noqa: E402
 from bayesflow_nddms_amd.amortizer import InvariantNetwork, InvertibleNetwork   # noqa: E402
