@@ -1,5 +1,5 @@
 """ctypes binding of libnddm_train.so: the amortizer's flow as one kernel each way (csrc/train_kernels.hip), its inverse -- the
-posterior sampler -- as one kernel (csrc/train_sample.hip), and the summary
+posterior sampler -- as one kernel (csrc/train_sample.hip), the draws' order statistics (csrc/train_quantile.hip), and the summary
 network's per-trial MLPs (csrc/train_deepset.hip), and the optimizer step on flat buffers (csrc/train_update.hip).
 Optional: `lib()` returns None when the library cannot be built or loaded, and the amortizer then runs its PyTorch path."""
 import ctypes
@@ -37,6 +37,11 @@ def lib():
     L.nddm_train_flow_sample.restype = i32
     L.nddm_train_flow_sample_work_bytes.argtypes = [i32, i32, i32]                                                             # B S D
     L.nddm_train_flow_sample_work_bytes.restype = c.c_longlong
+    L.nddm_train_draw_quantiles_max_draws.argtypes = []                                                                        # csrc/train_quantile.hip
+    L.nddm_train_draw_quantiles_max_draws.restype = i32
+    #                                     B    S    D   theta lo hi probs K  quant order n_inside stream
+    L.nddm_train_draw_quantiles.argtypes = [i32, i32, i32, fp, fp, fp, vp, i32, fp, fp, fp, vp]
+    L.nddm_train_draw_quantiles.restype = i32
     L.nddm_deepset_supported.argtypes = [i32, i32]
     L.nddm_deepset_supported.restype = i32
     common = [fp, i32, i32, i32, i32, i32, fp, i32, fp, f32, fp, i32, fp, i32, fp, fp, fp, fp, fp, i32, fp, i32]   # x .. S_x (csrc/train_deepset.hip)

@@ -555,6 +555,76 @@ class InvertibleNetwork(nn.Module):
         return self.inverse(z.reshape(B * S, D), cond.repeat_interleave(S, dim=0)).reshape(B, S, D)
 
 
+def _quantile_lib(theta, n_probs):
+    """libnddm_train.so if its selection kernel (csrc/train_quantile.hip) covers theta [B, S, D] and this many probabilities, else
+    None (draw_quantiles' PyTorch evaluation of the same definition)."""
+    if not (theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous() and 1 <= theta.shape[2] <= 8
+            and 1 <= n_probs <= 16):
+        return None
+    from . import _train_lib
+    L = _train_lib.lib()
+    return L if L is not None and theta.shape[1] <= L.nddm_train_draw_quantiles_max_draws() else None
+
+
+@torch.no_grad()
+def draw_quantiles(theta, probs, box=None):
+    """Exact quantiles of draws per (set, column): theta [B, S, D] (or [S, D]: one set), probs K probabilities in [0, 1] ->
+    {"quantiles" [B, K, D] float64, "order" [B, K, 2, D] float32, "n_inside" [B] int64}, tensors on theta's device.
+
+    A row (draw) is INSIDE if all its D components are finite and, with box = (low, high) of length D, within it -- the mask is per
+    row, as posterior_moments'.  With x_(0) <= ... <= x_(n-1) the inside values of a column, in float64: h = (n - 1) * p, j = floor(h),
+    g = h - j, a = x_(j), b = x_(min(j + 1, n - 1)); order = (a, b) as the float32 values themselves and quantile = a + (b - a) * g,
+    each operation rounded on its own: np.quantile's default rule (NumPy forms h otherwise: equal to rounding, not bit for bit).  No
+    inside row: nan, n_inside 0.  Zeros come back as +0.
+
+    On the device (float32, contiguous, D <= 8, S <= the kernel's cap, K <= 16) one kernel sorts each (set, column)'s keys in LDS
+    (csrc/train_quantile.hip); everywhere else -- a CPU, more draws, no library -- torch.sort evaluates the same definition, and the
+    two agree bit for bit."""
+    p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+    if p.size == 0 or not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("probs must be probabilities in [0, 1]")
+    if theta.dim() == 2:
+        theta = theta[None]
+    if theta.dim() != 3 or theta.numel() == 0:
+        raise ValueError(f"theta must be [B, S, D] (or [S, D]) and not empty; got {tuple(theta.shape)}")
+    (B, S, D), K, dev = theta.shape, p.size, theta.device
+    if box is not None:
+        box = tuple(v.to(dev, torch.float32).contiguous() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float32), device=dev)
+                    for v in box)
+        if len(box) != 2 or box[0].shape != (D,) or box[1].shape != (D,):
+            raise ValueError(f"box must be a (low, high) pair of length-{D} sequences")
+    L = _quantile_lib(theta, K)
+    if L is not None:
+        quant = torch.empty(B, K, D, dtype=torch.float64, device=dev)
+        order = torch.empty(B, K, 2, D, dtype=torch.float32, device=dev)
+        n_in = torch.empty(B, dtype=torch.int64, device=dev)
+        lo, hi = (None, None) if box is None else (box[0].data_ptr(), box[1].data_ptr())
+        rc = L.nddm_train_draw_quantiles(B, S, D, theta.data_ptr(), lo, hi, p.ctypes.data, K, quant.data_ptr(), order.data_ptr(),
+                                         n_in.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"nddm_train_draw_quantiles failed ({rc})")
+        return {"quantiles": quant, "order": order, "n_inside": n_in}
+    th = theta.to(torch.float32)
+    inside = torch.isfinite(th).all(dim=-1)
+    if box is not None:
+        inside &= ((th >= box[0]) & (th <= box[1])).all(dim=-1)
+    n_in = inside.sum(dim=1)
+    # (+ 0.0: -0 becomes +0, as in the kernel's keys; outside rows sort to the end)
+    srt = torch.sort(torch.where(inside[..., None], th + 0.0, torch.full((), float("inf"), device=dev)), dim=1).values
+    last = n_in.clamp(min=1) - 1
+    h = last.double()[:, None] * torch.as_tensor(p, device=dev)[None, :]                 # [B, K]
+    fl = h.floor()
+    g, j = (h - fl)[..., None], fl.long()
+    j1 = torch.minimum(j + 1, last[:, None])
+    a = torch.gather(srt, 1, j[..., None].expand(B, K, D))
+    b = torch.gather(srt, 1, j1[..., None].expand(B, K, D))
+    empty = (n_in == 0)[:, None, None]
+    nan32 = torch.full((), float("nan"), device=dev)
+    a, b = torch.where(empty, nan32, a), torch.where(empty, nan32, b)
+    ad, bd = a.double(), b.double()
+    return {"quantiles": ad + (bd - ad) * g, "order": torch.stack([a, b], dim=2), "n_inside": n_in}
+
+
 class AmortizedPosterior(nn.Module):
     """bf.amortizers.AmortizedPosterior(inference_net, summary_net): maximum-likelihood training of q(theta | data)."""
 
@@ -655,6 +725,20 @@ class AmortizedPosterior(nn.Module):
         bit-reproducible), whole data sets per launch, as many as keep the base normals of a launch within z_bytes.  Elsewhere
         (a CPU, a shape the kernel does not cover) the same numbers come from the PyTorch inverse's draws, summed in float64.  The
         base normals are torch.randn(sets * n_samples, P) per launch: those of sample() whenever one launch holds all B sets."""
+        return self._moments(*self._moment_sums(input_dict, n_samples, box, z_bytes), n_samples)
+
+    @staticmethod
+    def _moments(sums, n_out, n_samples):
+        P = sums.shape[1] // 2
+        n_in = (n_samples - n_out).double()[:, None]
+        mean = sums[:, :P] / n_in
+        sd = (sums[:, P:] / n_in - mean * mean).clamp_min(0.0).sqrt()
+        return {"mean": mean.cpu().numpy(), "sd": sd.cpu().numpy(), "n_outside": n_out.cpu().numpy(), "n_samples": int(n_samples)}
+
+    def _moment_sums(self, input_dict, n_samples, box, z_bytes, on_draws=None):
+        """posterior_moments' loop -> (sums [B, 2 P] float64, n_outside [B] int64), device tensors.  on_draws(theta [sets, n_samples, P],
+        box): called after every launch with that launch's draws (a scratch buffer that the next launch overwrites) and the box
+        as device tensors; the sampler then writes the draws as well as the sums."""
         cond = self._conditions(input_dict)
         B, P, dev, net = cond.shape[0], self.inference_net.num_params, cond.device, self.inference_net
         if box is not None:
@@ -664,26 +748,70 @@ class AmortizedPosterior(nn.Module):
         sums = torch.empty(B, 2 * P, dtype=torch.float64, device=dev)
         n_out = torch.empty(B, dtype=torch.int64, device=dev)
         per = max(1, int(z_bytes) // max(1, 4 * n_samples * P))
+        scratch = None
         for b0 in range(0, B, per):
             c = cond[b0:b0 + per]
             nb = c.shape[0]
             z = torch.randn(nb * n_samples, P, device=dev)
             L = net._sample_lib(z.view(nb, n_samples, P), c) if hasattr(net, "_sample_lib") else None
             if L is not None:
-                net._fused_sample(L, z.view(nb, n_samples, P), c, box=box, draws=False, moments=True, sums=sums[b0:b0 + nb],
-                                  n_outside=n_out[b0:b0 + nb])
+                if on_draws is not None and scratch is None:
+                    scratch = torch.empty(min(per, B), n_samples, P, dtype=torch.float32, device=dev)
+                net._fused_sample(L, z.view(nb, n_samples, P), c, box=box, draws=on_draws is not None, moments=True,
+                                  out=None if on_draws is None else scratch[:nb], sums=sums[b0:b0 + nb], n_outside=n_out[b0:b0 + nb])
+                if on_draws is not None:
+                    on_draws(scratch[:nb], box)
                 continue
             th = net.inverse(z, c.repeat_interleave(n_samples, dim=0)).reshape(nb, n_samples, P)
+            if on_draws is not None:
+                on_draws(th.contiguous(), box)
             inside = torch.isfinite(th).all(dim=-1)
             if box is not None:
                 inside &= ((th >= box[0]) & (th <= box[1])).all(dim=-1)
             th = torch.where(inside[..., None], th.double(), torch.zeros((), dtype=torch.float64, device=dev))
             sums[b0:b0 + nb] = torch.cat([th.sum(dim=1), (th * th).sum(dim=1)], dim=-1)
             n_out[b0:b0 + nb] = (~inside).sum(dim=1)
-        n_in = (n_samples - n_out).double()[:, None]
-        mean = sums[:, :P] / n_in
-        sd = (sums[:, P:] / n_in - mean * mean).clamp_min(0.0).sqrt()
-        return {"mean": mean.cpu().numpy(), "sd": sd.cpu().numpy(), "n_outside": n_out.cpu().numpy(), "n_samples": int(n_samples)}
+        return sums, n_out
+
+    # pyhddmjagsutils.summary's names for the quantiles its recovery plots draw
+    SUMMARY_NAMES = {0.5: "median", 0.025: "95lower", 0.975: "95upper", 0.005: "99lower", 0.995: "99upper"}
+
+    @torch.no_grad()
+    def posterior_summary(self, input_dict, n_samples, probs=(.005, .025, .5, .975, .995), box=None, z_bytes=64 << 20, keep_draws=False):
+        """The reference's posterior summary (pyhddmjagsutils.summary: mean, std, median, 95 % and 99 % credible intervals) of every
+        data set from n_samples draws each, without the draws leaving the device:
+        {"mean", "std", "median", "95lower", "95upper", "99lower", "99upper" [B, P] each; "quantiles" [B, K, P], "probs" [K],
+        "n_outside" [B], "n_samples"}, float64 (numpy).  A named quantile is present when `probs` holds its probability (.5, .025,
+        .975, .005, .995).  keep_draws=True adds "draws" [B, n_samples, P] float32 (small B, tests).
+
+        posterior_moments' loop and random stream: whole data sets per launch, torch.randn(sets * n_samples, P) per launch, as
+        many sets as keep the base normals within z_bytes; `mean`, `std` (its `sd`) and `n_outside` are that call's numbers, bit for
+        bit under the same seed, box and z_bytes.  Each launch's draws go into one scratch buffer of the base normals' size (so
+        the call holds up to 2 x z_bytes: fewer sets per launch would consume torch.randn otherwise than posterior_moments does),
+        which `draw_quantiles` turns into exact order statistics on the same stream before the next launch overwrites it.  box:
+        posterior_moments' -- the quantiles are over the inside draws, the sample the moments use.  Where the fused sampler does
+        not apply the draws come from the PyTorch inverse and the quantiles from draw_quantiles' fallback."""
+        p = np.asarray(probs, dtype=np.float64).reshape(-1)
+        if p.size == 0 or not np.all((p >= 0.0) & (p <= 1.0)):
+            raise ValueError("probs must be probabilities in [0, 1]")
+        quants, kept = [], []
+
+        def on_draws(theta, box_t):
+            quants.append(draw_quantiles(theta, p, box=box_t)["quantiles"])
+            if keep_draws:
+                kept.append(theta.clone())
+
+        m = self._moments(*self._moment_sums(input_dict, n_samples, box, z_bytes, on_draws), n_samples)
+        q = torch.cat(quants, dim=0).cpu().numpy()
+        out = {"mean": m["mean"], "std": m["sd"]}
+        for k, pk in enumerate(p):
+            name = self.SUMMARY_NAMES.get(float(pk))
+            if name is not None:
+                out[name] = q[:, k, :]
+        out.update(quantiles=q, probs=p, n_outside=m["n_outside"], n_samples=int(n_samples))
+        if keep_draws:
+            out["draws"] = torch.cat(kept, dim=0).cpu().numpy()
+        return out
 
 
 class Trainer:

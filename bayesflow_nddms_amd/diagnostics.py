@@ -142,6 +142,39 @@ def rhat_neff(samples):
             "std": x.reshape(x.shape[0], -1).std(axis=1).reshape(lead)}
 
 
+def summary(insamples):
+    """The reference's `summary` (pyhddmjagsutils.py:334-388) for MCMC output in its JAGS-sample layout -- what mcmc.hmc_fit /
+    hmc_fit_joint return and rhat_neff accepts: a dict of arrays [..., iterations, chains] (keys that begin with '_' are skipped) -> per
+    key {'mean', 'std', 'median', '95lower', '95upper', '99lower', '99upper'}, each float64 of the leading shape, over the key's
+    iterations x chains samples.  mean and std (ddof 0) are NumPy's in float64.  The quantiles are exact order statistics,
+    interpolated as np.quantile's default does, of the samples as float32 (the fits' samples are float32 values) through
+    amortizer.draw_quantiles as [variables, iterations x chains, 1]: one kernel launch per key on the device when there is one,
+    the PyTorch evaluation of the same definition otherwise.  A non-finite sample is left out of its variable's quantiles."""
+    import torch
+    from .amortizer import draw_quantiles
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    names = (("median", .5), ("95lower", .025), ("95upper", .975), ("99lower", .005), ("99upper", .995))
+    result = {}
+    for key, v in insamples.items():
+        if key.startswith("_"):
+            continue
+        x = np.asarray(v.cpu() if hasattr(v, "is_cuda") else v, dtype=np.float64)
+        if x.ndim < 2 or x.shape[-1] * x.shape[-2] == 0:
+            raise ValueError(f"samples of '{key}' must be [..., iterations >= 1, chains >= 1], got {x.shape}")
+        lead = x.shape[:-2]
+        allsamps = x.reshape(lead + (x.shape[-2] * x.shape[-1],))
+        res = {"mean": np.mean(allsamps, axis=-1), "std": np.std(allsamps, axis=-1)}
+        if allsamps.size:
+            th = torch.as_tensor(allsamps.reshape(-1, allsamps.shape[-1]).astype(np.float32), device=dev)[:, :, None]
+            q = draw_quantiles(th, [p for _, p in names])["quantiles"][:, :, 0].cpu().numpy()
+        else:
+            q = np.empty((0, len(names)))
+        for k, (name, _) in enumerate(names):
+            res[name] = q[:, k].reshape(lead)
+        result[key] = res
+    return result
+
+
 def posterior_log_likelihood(samples, data, model):
     """Score posterior draws by the exact likelihood: samples [D, S, P] (what amortizer.sample returns for a batch of D data sets;
     [S, P] for one), data [D, n_trials, 2] in the simulator's format (model = engine.BASIC_DDM_DC or engine.ALPHA_NOT_SCALED) ->
