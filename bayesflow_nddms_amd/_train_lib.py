@@ -1,5 +1,5 @@
 """ctypes binding of libnddm_train.so: the amortizer's flow as one kernel each way (csrc/train_kernels.hip), its inverse -- the
-posterior sampler -- as one kernel (csrc/train_sample.hip), the draws' order statistics (csrc/train_quantile.hip), and the summary
+posterior sampler -- as one kernel (csrc/train_sample.hip), the draws' order statistics (csrc/train_quantile.hip) and importance weights (csrc/train_importance.hip), and the summary
 network's per-trial MLPs (csrc/train_deepset.hip), and the optimizer step on flat buffers (csrc/train_update.hip).
 Optional: `lib()` returns None when the library cannot be built or loaded, and the amortizer then runs its PyTorch path."""
 import ctypes
@@ -35,6 +35,12 @@ def lib():
     #                                  hidden L  B    S    D    d1   C    clamp params perm z cond theta lo hi sums n_outside work stream
     L.nddm_train_flow_sample.argtypes = [i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, fp, fp, fp, fp, fp, fp, fp, fp, vp]   # csrc/train_sample.hip
     L.nddm_train_flow_sample.restype = i32
+    #                                       ... hi sums n_outside log_q work stream: the same launch + the flow's log density at each draw
+    L.nddm_train_flow_sample_logq.argtypes = [i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]
+    L.nddm_train_flow_sample_logq.restype = i32
+    #                                 B    S    D   theta log_q log_lik prior | log_evidence ess max_share mean sd n_zero n_nan log_w | stream
+    L.nddm_train_importance.argtypes = [i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]                     # csrc/train_importance.hip
+    L.nddm_train_importance.restype = i32
     L.nddm_train_flow_sample_work_bytes.argtypes = [i32, i32, i32]                                                             # B S D
     L.nddm_train_flow_sample_work_bytes.restype = c.c_longlong
     L.nddm_train_draw_quantiles_max_draws.argtypes = []                                                                        # csrc/train_quantile.hip

@@ -399,12 +399,15 @@ class _AffineCoupling(nn.Module):
         y1 = torch.addcmul(t, x1, torch.exp(sb))
         return torch.cat([y1, y2], dim=-1), [sa, sb]
 
-    def inverse(self, y, cond):
+    def inverse(self, y, cond, scales=None):
+        """scales: a list that receives the two log-scales [s_b, s_a] -- the forward's, at the point this returns."""
         y1, y2 = y[:, :self.d1], y[:, self.d1:]
-        s, t = self._st(self.net2, y2, cond)
-        x1 = (y1 - t) * torch.exp(-s)
-        s, t = self._st(self.net1, x1, cond)
-        x2 = (y2 - t) * torch.exp(-s)
+        sb, t = self._st(self.net2, y2, cond)
+        x1 = (y1 - t) * torch.exp(-sb)
+        sa, t = self._st(self.net1, x1, cond)
+        x2 = (y2 - t) * torch.exp(-sa)
+        if scales is not None:
+            scales += [sb, sa]
         return torch.cat([x1, x2], dim=-1)
 
 
@@ -507,6 +510,19 @@ class InvertibleNetwork(nn.Module):
             x = (x - self.an_bias[i]) * torch.exp(-self.an_scale[i])
         return x
 
+    def inverse_with_log_density(self, z, cond):
+        """`inverse` with the log-scales kept: z [R, D], cond [R, C] -> (theta [R, D], log_q [R]), the flow's own log density at the draw
+        it returns, log q(theta | cond) = -|z|^2 / 2 - (D / 2) log 2 pi + log|det| -- the forward's log|det| is the sum of the SAME
+        soft-clamped log-scales the inverse forms on its way (each half-layer sees the inputs the forward's sees) and of the ActNorm
+        log-scales.  The PyTorch composition: the fallback of inverse_per_set(log_density=True) and the fused sampler's yardstick."""
+        x, scales = z, []
+        for i in reversed(range(len(self.layers))):
+            x = self.layers[i].inverse(x, cond, scales)
+            x = x @ getattr(self, f"pmat{i}").t()
+            x = (x - self.an_bias[i]) * torch.exp(-self.an_scale[i])
+        log_det = torch.cat(scales, dim=-1).sum(-1) + torch.cat(list(self.an_scale)).sum()
+        return x, -0.5 * (z ** 2).sum(-1) - 0.5 * self.num_params * math.log(2.0 * math.pi) + log_det
+
     def _sample_lib(self, z, cond):
         """libnddm_train.so if the fused sampler covers z [B, S, D] with one condition row per set, cond [B, C]; else None.  The
         kernel is no autograd node: where a gradient could be asked for, the PyTorch composition serves."""
@@ -516,11 +532,14 @@ class InvertibleNetwork(nn.Module):
             return None
         return self._fused_lib(z.reshape(-1, z.shape[-1]), cond, rows_limit=False)
 
-    def _fused_sample(self, L, z, cond, box=None, draws=True, moments=False, out=None, sums=None, n_outside=None):
+    def _fused_sample(self, L, z, cond, box=None, draws=True, moments=False, out=None, sums=None, n_outside=None, log_q=False,
+                      log_q_out=None):
         """One launch of csrc/train_sample.hip on z [B, S, D], cond [B, C] -> (theta [B, S, D] or None, sums [B, 2 D] float64 or None,
         n_outside [B] int64 or None): the draws (draws=True), and / or (moments=True) per set the float64 sums of theta and of
         theta^2 over the draws INSIDE -- every component finite and, with box = (lo [D], hi [D]) float32 tensors, within it -- and
-        the number of draws outside.  out / sums / n_outside: contiguous tensors to write into (else allocated here)."""
+        the number of draws outside.  out / sums / n_outside: contiguous tensors to write into (else allocated here).
+        log_q=True appends a fourth item, log_q [B, S] float32 (written into log_q_out if given): the flow's own log density at each
+        draw, from the same launch -- the other three keep their bits (inverse_with_log_density is the PyTorch form)."""
         import ctypes
         (B, S, D), C, dev, nl = z.shape, cond.shape[1], z.device, len(self.layers)
         params = self._flow_params()
@@ -532,26 +551,39 @@ class InvertibleNetwork(nn.Module):
         if moments:
             sums = torch.empty(B, 2 * D, dtype=torch.float64, device=dev) if sums is None else sums
             n_outside = torch.empty(B, dtype=torch.int64, device=dev) if n_outside is None else n_outside
+        if log_q and log_q_out is None:
+            log_q_out = torch.empty(B, S, dtype=torch.float32, device=dev)
         lo, hi = (None, None) if box is None else (v.to(dev, torch.float32).contiguous() for v in box)
         work = torch.empty(int(L.nddm_train_flow_sample_work_bytes(B, S, D)), dtype=torch.uint8, device=dev)
         ptr = lambda v: None if v is None else v.data_ptr()       # noqa: E731
-        rc = L.nddm_train_flow_sample(params[4].shape[0], nl, B, S, D, self.layers[0].d1, C, float(self.layers[0].clamp), ptrs, perm,
-                                      z.data_ptr(), cond.data_ptr(), ptr(out) if draws else None, ptr(lo), ptr(hi),
-                                      ptr(sums) if moments else None, ptr(n_outside) if moments else None, work.data_ptr(),
-                                      torch.cuda.current_stream(dev).cuda_stream)
+        args = (params[4].shape[0], nl, B, S, D, self.layers[0].d1, C, float(self.layers[0].clamp), ptrs, perm, z.data_ptr(), cond.data_ptr(),
+                ptr(out) if draws else None, ptr(lo), ptr(hi), ptr(sums) if moments else None, ptr(n_outside) if moments else None)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if log_q:
+            rc = L.nddm_train_flow_sample_logq(*args, log_q_out.data_ptr(), work.data_ptr(), st)
+        else:
+            rc = L.nddm_train_flow_sample(*args, work.data_ptr(), st)
         if rc != 0:
             raise RuntimeError(f"nddm_train_flow_sample failed ({rc})")
-        return (out if draws else None), (sums if moments else None), (n_outside if moments else None)
+        res = (out if draws else None), (sums if moments else None), (n_outside if moments else None)
+        return res + (log_q_out,) if log_q else res
 
-    def inverse_per_set(self, z, cond):
+    def inverse_per_set(self, z, cond, log_density=False):
         """The inverse on draws grouped by data set: z [B, S, D] base normals, cond [B, C] ONE condition row per set -> [B, S, D].
         Where the fused sampler applies (cuda, float32, the shapes of nddm_train_flow_supported, self.fused, no gradient asked for) it
         is one kernel that never expands the condition (csrc/train_sample.hip); otherwise `inverse` on the condition repeated S
-        times -- the same map."""
+        times -- the same map.  log_density=True -> (theta [B, S, D], log_q [B, S]): the flow's log density at each draw as well, from
+        the same kernel, or from inverse_with_log_density."""
         B, S, D = z.shape
         L = self._sample_lib(z, cond)
         if L is not None:
+            if log_density:
+                res = self._fused_sample(L, z, cond, log_q=True)
+                return res[0], res[3]
             return self._fused_sample(L, z, cond)[0]
+        if log_density:
+            th, lq = self.inverse_with_log_density(z.reshape(B * S, D), cond.repeat_interleave(S, dim=0))
+            return th.reshape(B, S, D), lq.reshape(B, S)
         return self.inverse(z.reshape(B * S, D), cond.repeat_interleave(S, dim=0)).reshape(B, S, D)
 
 
@@ -623,6 +655,113 @@ def draw_quantiles(theta, probs, box=None):
     a, b = torch.where(empty, nan32, a), torch.where(empty, nan32, b)
     ad, bd = a.double(), b.double()
     return {"quantiles": ad + (bd - ad) * g, "order": torch.stack([a, b], dim=2), "n_inside": n_in}
+
+
+def _importance_lib(theta, log_q, log_lik):
+    """libnddm_train.so if its weight-and-reduce kernel (csrc/train_importance.hip) covers these tensors, else None
+    (importance_weights' torch evaluation of the same definition)."""
+    if not (theta.is_cuda and log_q.device == theta.device and log_lik.device == theta.device and theta.dtype == torch.float32
+            and log_q.dtype == torch.float32 and log_lik.dtype == torch.float64 and theta.is_contiguous() and log_q.is_contiguous()
+            and log_lik.is_contiguous() and 1 <= theta.shape[2] <= 8):
+        return None
+    from . import _train_lib
+    return _train_lib.lib()
+
+
+def _log_prior_torch(table, th):
+    """priors.log_prior_density in torch float64 on th [..., P]'s device (table: priors.prior_table's host array)."""
+    ninf = torch.full((), float("-inf"), dtype=torch.float64, device=th.device)
+    out = torch.zeros(th.shape[:-1], dtype=torch.float64, device=th.device)
+    for d, (kind, p1, p2, lo, hi, ln) in enumerate(table.tolist()):
+        x = th[..., d]
+        if kind in (0.0, 1.0):
+            u = (x - p1) / p2
+            lp = -0.5 * u * u - ln
+        elif kind == 2.0:
+            lp = torch.full_like(x, -ln)
+            if p1 != 1.0:
+                lp = lp + (p1 - 1.0) * torch.log(x)
+            if p2 != 1.0:
+                lp = lp + (p2 - 1.0) * torch.log1p(-x)
+        else:
+            lp = torch.full_like(x, -ln)
+        out = out + torch.where(torch.isfinite(x) & (x >= lo) & (x <= hi), lp, ninf)
+    return out
+
+
+@torch.no_grad()
+def importance_weights(theta, log_q, log_lik, prior, want_log_w=False, out=None):
+    """Self-normalised importance sampling of a proposal's draws against the exact posterior, per data set: theta [B, S, D] draws of
+    q (or [S, D]: one set), log_q [B, S] their log density under q (InvertibleNetwork.inverse_per_set(log_density=True)), log_lik [B, S]
+    the exact log-likelihood of the set's data at each draw (diagnostics.posterior_log_likelihood), prior a model name of
+    priors.PRIOR_DENSITY ("basic", "single", "scale"), such a description, or priors.prior_table's array ->
+    {"log_evidence", "ess", "max_share" [B]; "mean", "sd" [B, D] float64; "n_zero", "n_nan" [B] int64; "log_w" [B, S] float64 with
+    want_log_w}, tensors on theta's device.  In float64, per draw
+        log w = log_lik + log prior(theta) - log_q
+    with weight 0 (log w = -inf), in this order: where the log prior is -inf -- a component outside its support or not finite --
+    whatever log_lik holds (counted in n_zero); else where log_lik or log_q is NaN (counted in n_nan, and only there: nothing is
+    swept under the rug); else where log_lik or log w is -inf (n_zero); else where log w is +inf (n_nan).  With m = max log w and
+    u = exp(log w - m):  log_evidence = m + log(sum u / S), an estimate of log p(data) -- by S, not by the number of positive
+    weights: a draw of q outside the prior's support is a draw whose weight is zero;  ess = (sum u)^2 / sum u^2;  max_share =
+    1 / sum u, the largest normalised weight;  mean, sd the weighted moments (ddof 0, the variance clamped at 0).  A set without
+    a positive weight: nan mean, sd and max_share, ess 0, log_evidence -inf.
+
+    On the device (float32 contiguous theta and log_q, float64 log_lik, D <= 8) one kernel, a workgroup per set, the float64 sums in
+    a fixed order (csrc/train_importance.hip: bit-reproducible, a set's numbers independent of B); everywhere else the same
+    definition in torch float64.  The two agree to the summation bound and a few ulp of exp, not bit for bit.
+    out: a dict of contiguous tensors, by the result's keys, to write into (posterior_importance's slices)."""
+    from . import priors
+    table = np.ascontiguousarray(prior if isinstance(prior, np.ndarray) else priors.prior_table(prior), dtype=np.float64)
+    if theta.dim() == 2:
+        theta, log_q, log_lik = theta[None], log_q.reshape(1, -1), log_lik.reshape(1, -1)
+    if theta.dim() != 3 or theta.numel() == 0:
+        raise ValueError(f"theta must be [B, S, D] (or [S, D]) and not empty; got {tuple(theta.shape)}")
+    (B, S, D), dev = theta.shape, theta.device
+    if tuple(log_q.shape) != (B, S) or tuple(log_lik.shape) != (B, S) or table.shape != (D, 6):
+        raise ValueError(f"log_q and log_lik must be [{B}, {S}] and the prior have {D} columns")
+    L = _importance_lib(theta, log_q, log_lik)
+    if L is not None:
+        o = dict(out or {})
+        for k, shape, dt in (("log_evidence", (B,), torch.float64), ("ess", (B,), torch.float64), ("max_share", (B,), torch.float64),
+                             ("mean", (B, D), torch.float64), ("sd", (B, D), torch.float64), ("n_zero", (B,), torch.int64),
+                             ("n_nan", (B,), torch.int64)) + ((("log_w", (B, S), torch.float64),) if want_log_w else ()):
+            if k not in o:
+                o[k] = torch.empty(shape, dtype=dt, device=dev)
+        tab = torch.as_tensor(table, device=dev)
+        st = torch.cuda.current_stream(dev)
+        rc = L.nddm_train_importance(B, S, D, theta.data_ptr(), log_q.data_ptr(), log_lik.data_ptr(), tab.data_ptr(),
+                                     o["log_evidence"].data_ptr(), o["ess"].data_ptr(), o["max_share"].data_ptr(), o["mean"].data_ptr(),
+                                     o["sd"].data_ptr(), o["n_zero"].data_ptr(), o["n_nan"].data_ptr(),
+                                     o["log_w"].data_ptr() if want_log_w else None, st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"nddm_train_importance failed ({rc})")
+        return o                                                  # (tab was made on this stream: the allocator reuses it in stream order)
+    th, lq, ll = theta.double(), log_q.double(), log_lik.double()
+    ninf = torch.full((), float("-inf"), dtype=torch.float64, device=dev)
+    lp = _log_prior_torch(table, th)
+    zero_prior = lp == ninf
+    nan = ~zero_prior & (torch.isnan(ll) | torch.isnan(lq))
+    lw = torch.where(zero_prior | nan | (ll == ninf), ninf, ll + lp - lq)
+    nan = nan | (~zero_prior & (torch.isnan(lw) | (lw == float("inf"))))
+    lw = torch.where(nan, ninf, lw)
+    m = lw.max(dim=1, keepdim=True).values
+    u = torch.where(lw == ninf, torch.zeros((), dtype=torch.float64, device=dev), torch.exp(lw - torch.where(m == ninf, torch.zeros_like(m), m)))
+    tz = torch.where((u > 0)[..., None], th, torch.zeros((), dtype=torch.float64, device=dev))      # (a zero weight's draw may not be finite)
+    sw, sw2 = u.sum(dim=1), (u * u).sum(dim=1)
+    any_w = sw > 0
+    nan64 = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    mean = (u[..., None] * tz).sum(dim=1) / sw[:, None]
+    var = (u[..., None] * (tz * tz)).sum(dim=1) / sw[:, None] - mean * mean
+    res = {"log_evidence": torch.where(any_w, m[:, 0] + torch.log(sw / S), ninf), "ess": torch.where(any_w, sw * sw / sw2, torch.zeros_like(sw)),
+           "max_share": torch.where(any_w, 1.0 / sw, nan64), "mean": torch.where(any_w[:, None], mean, nan64),
+           "sd": torch.where(any_w[:, None], var.clamp_min(0.0).sqrt(), nan64), "n_zero": ((lw == ninf) & ~nan).sum(dim=1),
+           "n_nan": nan.sum(dim=1)}
+    if want_log_w:
+        res["log_w"] = lw
+    for k, v in (out or {}).items():
+        if k in res:
+            res[k] = v.copy_(res[k])
+    return res
 
 
 class AmortizedPosterior(nn.Module):
@@ -812,6 +951,85 @@ class AmortizedPosterior(nn.Module):
         if keep_draws:
             out["draws"] = torch.cat(kept, dim=0).cpu().numpy()
         return out
+
+    @torch.no_grad()
+    def posterior_importance(self, input_dict, n_samples, model="basic", z_bytes=64 << 20, keep_draws=False, keep_weights=False):
+        """The amortizer's draws importance-weighted against the EXACT posterior of every data set (importance_weights: log w =
+        log p(data | theta) + log p(theta) - log q(theta | data)), without the draws leaving the device:
+        {"mean", "std" [B, P]: the weighted posterior moments -- a consistent estimate of the exact posterior's, whatever the
+        amortizer's error, and a far-tail draw simply has weight 0;  "ess" [B]: the effective sample size, per data set how good the
+        amortizer is;  "log_evidence" [B]: an estimate of log p(data);  "max_share" [B]: the largest normalised weight;  "n_zero",
+        "n_nan" [B], "n_samples"}, float64 / int64 (numpy).  keep_draws=True adds "draws" [B, n_samples, P] float32 and "log_q"
+        [B, n_samples] float32, keep_weights=True "log_w" [B, n_samples] float64 (small B, tests).
+
+        posterior_moments' loop and random stream: whole data sets per launch, torch.randn(sets * n_samples, P) per launch, as
+        many sets as keep the base normals within z_bytes -- the draws are those of sample(..., fused=True) under the same seed
+        whenever one launch holds all sets.  Per launch three kernels, all on torch's current stream (engine launches there too):
+        the fused sampler writes draws and log q into scratch (csrc/train_sample.hip), the broadcast-layout Wiener likelihood scores
+        them against the set's trials, input_dict["summary_conditions"] -- basic_ddm_dc's (rt, choice), timeouts right-censored --
+        and csrc/train_importance.hip weighs and reduces.  Where the fused sampler does not apply the draws and log q come from
+        inverse_with_log_density.  model: "basic" only; the single-trial models' likelihood is not wired here yet."""
+        if model != "basic":
+            raise NotImplementedError(f"posterior_importance scores model='basic' only; for {model!r} the next step is the marginal "
+                                      "likelihood, likelihood.single_trial_logpdf, as the target")
+        from . import engine, priors
+        table = priors.prior_table(model)
+        cond = self._conditions(input_dict)
+        data = self._t(input_dict["summary_conditions"])
+        B, P, dev, net, S = cond.shape[0], self.inference_net.num_params, cond.device, self.inference_net, int(n_samples)
+        if table.shape[0] != P or data.dim() != 3 or data.shape[0] != B or data.shape[2] != 2:
+            raise ValueError(f"model {model!r} has {table.shape[0]} parameters and (rt, choice) trials [B, N, 2]; the network has {P} and "
+                             f"summary_conditions are {tuple(data.shape)}")
+        res = {k: torch.empty(B, dtype=torch.float64, device=dev) for k in ("log_evidence", "ess", "max_share")}
+        res.update({k: torch.empty(B, P, dtype=torch.float64, device=dev) for k in ("mean", "sd")})
+        res.update({k: torch.empty(B, dtype=torch.int64, device=dev) for k in ("n_zero", "n_nan")})
+        per = max(1, int(z_bytes) // max(1, 4 * S * P))
+        scratch = torch.empty(min(per, B), S, P, dtype=torch.float32, device=dev)
+        scratch_q = torch.empty(min(per, B), S, dtype=torch.float32, device=dev)
+        kept, kept_q, kept_w = [], [], []
+        for b0 in range(0, B, per):
+            c = cond[b0:b0 + per]
+            nb = c.shape[0]
+            z = torch.randn(nb * S, P, device=dev)
+            L = net._sample_lib(z.view(nb, S, P), c) if hasattr(net, "_sample_lib") else None
+            if L is not None:
+                th, lq = scratch[:nb], scratch_q[:nb]
+                net._fused_sample(L, z.view(nb, S, P), c, out=th, log_q=True, log_q_out=lq)
+            else:
+                th, lq = net.inverse_with_log_density(z, c.repeat_interleave(S, dim=0))
+                th, lq = th.reshape(nb, S, P).contiguous(), lq.reshape(nb, S).contiguous()
+            ll = engine.wiener_log_likelihood(engine.BASIC_DDM_DC, th.view(nb * S, P), data[b0:b0 + nb], draws_per_dataset=S,
+                                              device=dev)["loglik"].view(nb, S)
+            w = importance_weights(th, lq, ll, table, want_log_w=keep_weights, out={k: v[b0:b0 + nb] for k, v in res.items()})
+            if keep_draws:
+                kept.append(th.clone())
+                kept_q.append(lq.clone())
+            if keep_weights:
+                kept_w.append(w["log_w"])
+        out = {("std" if k == "sd" else k): v.cpu().numpy() for k, v in res.items()}
+        out["n_samples"] = S
+        if keep_draws:
+            out["draws"], out["log_q"] = torch.cat(kept, dim=0).cpu().numpy(), torch.cat(kept_q, dim=0).cpu().numpy()
+        if keep_weights:
+            out["log_w"] = torch.cat(kept_w, dim=0).cpu().numpy()
+        return out
+
+    @torch.no_grad()
+    def log_posterior(self, input_dict, to_numpy=True):
+        """bf.amortizers.AmortizedPosterior.log_posterior: log q(parameters | conditions) through the flow's FORWARD, z, log|det| =
+        inference_net(parameters, conditions) -> -|z|^2 / 2 - (P / 2) log 2 pi + log|det|.  input_dict["parameters"]: [B, P], a row
+        per data set -> [B]; or [B, S, P], S rows per data set (posterior draws: the condition row is repeated) -> [B, S].  The
+        independent route to the number the fused sampler emits with its draws (inverse_per_set(log_density=True))."""
+        theta, cond = self._t(input_dict["parameters"]), self._conditions(input_dict)
+        shape = theta.shape[:-1]
+        if theta.dim() == 3:
+            if theta.shape[0] != cond.shape[0]:
+                raise ValueError(f"parameters hold {theta.shape[0]} data sets but the conditions {cond.shape[0]}")
+            cond = cond.repeat_interleave(theta.shape[1], dim=0)
+            theta = theta.reshape(-1, theta.shape[-1])
+        z, log_det = self.inference_net(theta.contiguous(), cond)
+        lq = (-0.5 * (z ** 2).sum(-1) - 0.5 * theta.shape[-1] * math.log(2.0 * math.pi) + log_det).reshape(shape)
+        return lq.cpu().numpy() if to_numpy else lq
 
 
 class Trainer:

@@ -27,7 +27,15 @@
 // sums of theta and theta^2 over its inside draws and its count of outside draws (rows summed in index order: eight segments
 // of sixteen rows, then the eight segment sums), and a second kernel adds a data set's tiles in index order.  No
 // floating-point atomics: the sums are bit-reproducible, and a data set's do not depend on B or on its neighbours.
-// gfx950 only.  tests/test_gpu_flow_sample.py holds it to a float64 inverse of the same network.
+// The flow's own density at the draw (flow_sample_logq_kernel, the same body with LQ = true): the forward's log|det| is the sum of the
+// same soft-clamped log-scales s the affine inverse forms, and of the ActNorm log-scales, so
+//     log q(theta | cond) = -|z|^2 / 2 - (D / 2) log 2 pi + sum_{half-layers} sum_d s_d + sum_l sum_d scale[l][d]
+// costs a row one float32 add per transformed column: the affine phase leaves s where it read the sub-network's output (o3), and
+// after the next barrier thread r adds row r's columns in index order to a register -- half-layers in the kernel's order, so the
+// value is bit-reproducible and depends on the row only, like the draw.  Two kernels, not a run-time switch: without log_q the
+// instructions are the ones they were.
+// gfx950 only.  tests/test_gpu_flow_sample.py holds it to a float64 inverse of the same network, tests/test_gpu_flow_importance.py
+// the density to the float64 forward.
 #include "train_flow.h"
 
 namespace nddm_train {
@@ -37,7 +45,7 @@ constexpr int NS = 512;         // threads per workgroup
 constexpr int MS = 8;          // outputs of a sub-network at most: 2 * transformed columns, D <= 8 and d1 = D / 2
 
 struct SampleDims { int L, B, S, D, d1, C, tiles; float clamp; };
-struct SampleOut { float *theta; const float *lo, *hi; double *part; int *part_n; };    // part [B * tiles, 2 * D_MAX], part_n [B * tiles]
+struct SampleOut { float *theta; const float *lo, *hi; double *part; int *part_n; float *log_q; };    // part [B * tiles, 2 * D_MAX], part_n [B * tiles], log_q [B, S]
 
 // cb[b, hl, u] = b1[u] + sum_c W1[u][Dh + c] cond[b][c] for the half-layer hl = 2 l + (sub-network 2 ? 1 : 0)
 __global__ __launch_bounds__(H) void sample_cond_kernel(SampleDims Q, FlowP P, const float *cond, float *cb)
@@ -52,7 +60,7 @@ __global__ __launch_bounds__(H) void sample_cond_kernel(SampleDims Q, FlowP P, c
     cb[(long long)blockIdx.x * H + u] = acc + W.b1[u];
 }
 
-__global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, const float *z, const float *cb, SampleOut O)
+template <bool LQ> __device__ __forceinline__ void flow_sample_body(const SampleDims &Q, const FlowP &P, const float *z, const float *cb, const SampleOut &O)
 {
     // (LDR, the row stride of W2, W3 and the activation tile: 16-byte aligned rows, 16 consecutive rows on 16 distinct 16-byte slots)
     __shared__ __attribute__((aligned(16))) float w2s[H][LDR];         // W2 [unit][k]
@@ -103,6 +111,7 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
     __syncthreads();
     for (int p = t; p < nvr * D; p += NS) { const int r = p / D, c = p - r * D; xs[0][r][c] = z[row0 * D + p]; }
     int cur = 0;
+    float lq = 0.0f;                                        // LQ: thread r < TS holds row r's sum of s
     for (int k = 0; k < 2 * Q.L; ++k) {
         const int l = Q.L - 1 - (k >> 1);
         const bool second = !(k & 1);                       // sub-network 2 (conditioned on y2, un-transforms y1) runs first
@@ -111,6 +120,10 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
         float (*x)[D_MAX] = xs[cur];
         // this half-layer's weights: out of the registers (fetched a half-layer ago) into LDS
         lds_barrier();                                      // (the previous half-layer's readers of w2s, w3s, hr and writers of xs are done)
+        if constexpr (LQ) {                                 // the previous half-layer's s (it transformed the columns this one is conditioned on)
+            if (k > 0 && t < TS)
+                for (int d = 0; d < Dh; ++d) lq += o3[t][d];
+        }
 #pragma unroll
         for (int q = 0; q < H * H / 4 / NS; ++q) { const int p4 = t + NS * q; *reinterpret_cast<f32x4 *>(&w2s[p4 >> 5][4 * (p4 & 31)]) = nw2[q]; }
 #pragma unroll
@@ -187,6 +200,7 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
             const float os = o3[r][d] + b3s, ot = o3[r][Dt + d] + b3t;
             const float sv = soft_clamp(os, Q.clamp);
             x[r][xt0 + d] = (x[r][xt0 + d] - ot) * expf(-sv);
+            if constexpr (LQ) o3[r][d] = sv;                // (only this thread reads o3[r][d]; layer 3 writes it again three barriers on)
         }
         if (!second) {                                      // the layer's two halves are undone: inverse permutation, inverse ActNorm
             lds_barrier();
@@ -203,6 +217,17 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
     const float (*x)[D_MAX] = xs[cur];
     if (O.theta)
         for (int p = t; p < nvr * D; p += NS) { const int r = p / D, c = p - r * D; O.theta[row0 * D + p] = x[r][c]; }
+    if constexpr (LQ) {
+        if (t < nvr) {                                       // (the last half-layer is sub-network 1's: d2 columns)
+            for (int d = 0; d < d2; ++d) lq += o3[t][d];
+            for (int l = Q.L - 1; l >= 0; --l)
+                for (int d = 0; d < D; ++d) lq += P.layer[l].scale[d];
+            const float *zr = z + (row0 + t) * D;
+            float zz = 0.0f;
+            for (int d = 0; d < D; ++d) zz = fmaf(zr[d], zr[d], zz);
+            O.log_q[row0 + t] = (-0.5f * zz - (float)D * 0.918938533204672742f) + lq;
+        }
+    }
     if (O.part) {
         if (t < TS) {
             bool in = t < nvr;
@@ -232,6 +257,16 @@ __global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, 
         }
         if (t == 0) O.part_n[blockIdx.x] = n_out_s;
     }
+}
+
+__global__ __launch_bounds__(NS) void flow_sample_kernel(SampleDims Q, FlowP P, const float *z, const float *cb, SampleOut O)
+{
+    flow_sample_body<false>(Q, P, z, cb, O);
+}
+
+__global__ __launch_bounds__(NS) void flow_sample_logq_kernel(SampleDims Q, FlowP P, const float *z, const float *cb, SampleOut O)
+{
+    flow_sample_body<true>(Q, P, z, cb, O);
 }
 
 // a data set's tiles, added in index order
@@ -271,15 +306,17 @@ long long nddm_train_flow_sample_work_bytes(int B, int S, int D)
 /* z [B, S, D] base normals, cond [B, C] one condition row per data set -> theta [B, S, D] (may be NULL: statistics only).
  * lo, hi [D] (both or neither): the box of the statistics.  sums [B, 2 D] doubles (the sums of theta, then of theta^2, over a
  * set's inside draws) and n_outside [B] 64-bit integers: both or neither (draws only).  work: nddm_train_flow_sample_work_bytes
- * (B, S, D) bytes, 8-byte aligned.  params, perm: as nddm_train_flow_fwd.  Everything on `stream`, nothing synchronises.
+ * (B, S, D) bytes, 8-byte aligned.  params, perm: as nddm_train_flow_fwd.  log_q [B, S] floats or NULL: the flow's log density at
+ * each draw (see the head of this file); the draws, sums and counts have the same bits with it and without.  At least one of theta,
+ * sums, log_q.  Everything on `stream`, nothing synchronises.
  * -> 0; 1 for a shape the gate refuses or a missing argument, before anything is read or launched; 2 for a launch error. */
-int nddm_train_flow_sample(int hidden, int L, int B, int S, int D, int d1, int C, float clamp, const void *const *params, const int *perm,
-                           const float *z, const float *cond, float *theta, const float *lo, const float *hi, double *sums,
-                           long long *n_outside, void *work, void *stream)
+int nddm_train_flow_sample_logq(int hidden, int L, int B, int S, int D, int d1, int C, float clamp, const void *const *params, const int *perm,
+                                const float *z, const float *cond, float *theta, const float *lo, const float *hi, double *sums,
+                                long long *n_outside, float *log_q, void *work, void *stream)
 {
     if (!nddm_train_flow_supported(hidden, L, D, d1, C) || B <= 0 || S <= 0) return 1;
     if (!params || !perm || !z || !cond || !work) return 1;
-    if ((!theta && !sums) || (sums == nullptr) != (n_outside == nullptr) || (lo == nullptr) != (hi == nullptr)) return 1;
+    if ((!theta && !sums && !log_q) || (sums == nullptr) != (n_outside == nullptr) || (lo == nullptr) != (hi == nullptr)) return 1;
     const long long tiles = (S + TS - 1) / TS;
     if ((long long)B * tiles > 0x7fffffffLL || (long long)B * 2 * L > 0x7fffffffLL || !perm_ok(perm, L, D)) return 1;
     FlowP P = {};
@@ -288,14 +325,25 @@ int nddm_train_flow_sample(int hidden, int L, int B, int S, int D, int d1, int C
     float *cb = static_cast<float *>(work);
     double *part = reinterpret_cast<double *>(static_cast<char *>(work) + (long long)B * 2 * L_MAX * H * 4);
     int *part_n = reinterpret_cast<int *>(part + (long long)B * tiles * 2 * D_MAX);
-    const SampleOut O = {theta, lo, hi, sums ? part : nullptr, sums ? part_n : nullptr};
+    const SampleOut O = {theta, lo, hi, sums ? part : nullptr, sums ? part_n : nullptr, log_q};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(sample_cond_kernel, dim3(B * 2 * L), dim3(H), 0, st, Q, P, cond, cb);
-    hipLaunchKernelGGL(flow_sample_kernel, dim3((unsigned)(B * tiles)), dim3(NS), 0, st, Q, P, z, static_cast<const float *>(cb), O);
+    if (log_q)
+        hipLaunchKernelGGL(flow_sample_logq_kernel, dim3((unsigned)(B * tiles)), dim3(NS), 0, st, Q, P, z, static_cast<const float *>(cb), O);
+    else
+        hipLaunchKernelGGL(flow_sample_kernel, dim3((unsigned)(B * tiles)), dim3(NS), 0, st, Q, P, z, static_cast<const float *>(cb), O);
     if (sums)
         hipLaunchKernelGGL(sample_combine_kernel, dim3(B), dim3(64), 0, st, Q, static_cast<const double *>(part),
                            static_cast<const int *>(part_n), sums, n_outside);
     return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+/* nddm_train_flow_sample_logq without the density: the draws and / or the statistics. */
+int nddm_train_flow_sample(int hidden, int L, int B, int S, int D, int d1, int C, float clamp, const void *const *params, const int *perm,
+                           const float *z, const float *cond, float *theta, const float *lo, const float *hi, double *sums,
+                           long long *n_outside, void *work, void *stream)
+{
+    return nddm_train_flow_sample_logq(hidden, L, B, S, D, d1, C, clamp, params, perm, z, cond, theta, lo, hi, sums, n_outside, nullptr, work, stream);
 }
 
 }  // extern "C"

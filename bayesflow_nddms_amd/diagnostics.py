@@ -179,7 +179,8 @@ def posterior_log_likelihood(samples, data, model):
     """Score posterior draws by the exact likelihood: samples [D, S, P] (what amortizer.sample returns for a batch of D data sets;
     [S, P] for one), data [D, n_trials, 2] in the simulator's format (model = engine.BASIC_DDM_DC or engine.ALPHA_NOT_SCALED) ->
     float64 [D, S] = log p(data[d] | samples[d, s]), in one launch of the broadcast layout (each data set staged once per 16 draws).
-    The numbers importance weights, posterior predictive log scores and LOO / WAIC start from."""
+    The numbers importance weights (amortizer.importance_weights, AmortizedPosterior.posterior_importance), posterior predictive log
+    scores and LOO / WAIC start from."""
     from . import engine
     single = samples.ndim == 2
     s = samples[None] if single else samples

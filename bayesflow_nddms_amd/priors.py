@@ -79,6 +79,71 @@ def prior_box(model="basic", widen=1.0):
     return lo - widen * (hi - lo), hi + widen * (hi - lo)
 
 
+# The priors above as densities, ONE description per column from which both the host's log density (log_prior_density) and the
+# table the importance kernel reads (prior_table, csrc/train_importance.hip) are built:
+#   ("normal", mean, sd) | ("truncnormal", mean, sd, low, high) | ("beta", a, b) on [0, 1] | ("uniform", low, high) | ("fixed", value)
+_BASIC_DENSITY = (("normal", 0.0, 2.0), ("truncnormal", 1.0, 0.5, 0.0, 10.0), ("beta", 2.0, 2.0), ("truncnormal", 0.5, 0.25, 0.0, 1.5),
+                  ("truncnormal", 1.0, 0.5, 0.0, 10.0))
+_SINGLE_DENSITY = _BASIC_DENSITY[:4] + (("truncnormal", 1.0, 0.5, 0.0, 3.0), ("truncnormal", 1.0, 0.5, 0.0, 10.0), ("uniform", 0.0, 5.0))
+PRIOR_DENSITY = {"basic": _BASIC_DENSITY, "single": _SINGLE_DENSITY, "scale": _SINGLE_DENSITY + (("uniform", 0.0, 2.0),)}
+PRIOR_KINDS = {"normal": 0, "truncnormal": 1, "beta": 2, "uniform": 3, "fixed": 4}
+
+
+def prior_table(model="basic"):
+    """float64 [P, 6], one row per column: kind (PRIOR_KINDS), two shape parameters, low, high, and the log normaliser -- what is
+    subtracted from the kernel of the log density inside [low, high]; outside (or at a non-finite value) the log density is -inf.
+        normal       mean, sd;  -inf, inf;  log(sd) + log(2 pi) / 2
+        truncnormal  mean, sd;  low, high;  the same + log(Phi((high - mean) / sd) - Phi((low - mean) / sd))
+        beta         a, b;      0, 1;       log B(a, b)      (a term whose exponent is 0 is 0, also at the edge: scipy's xlogy)
+        uniform      0, 0;      low, high;  log(high - low)
+        fixed        value, 0;  value, value;  0             (a column that is no random variable: 0 at its value, -inf elsewhere)
+    model: a name of PRIOR_DENSITY or such a description itself (a sequence of tuples)."""
+    from scipy.special import betaln, ndtr
+    rows = []
+    for col in (PRIOR_DENSITY[model] if isinstance(model, str) else model):
+        kind, a = col[0], [float(v) for v in col[1:]]
+        if kind == "normal":
+            row = [a[0], a[1], -np.inf, np.inf, np.log(a[1]) + 0.5 * np.log(2.0 * np.pi)]
+        elif kind == "truncnormal":
+            mass = ndtr((a[3] - a[0]) / a[1]) - ndtr((a[2] - a[0]) / a[1])
+            row = [a[0], a[1], a[2], a[3], np.log(a[1]) + 0.5 * np.log(2.0 * np.pi) + np.log(mass)]
+        elif kind == "beta":
+            row = [a[0], a[1], 0.0, 1.0, float(betaln(a[0], a[1]))]
+        elif kind == "uniform":
+            row = [0.0, 0.0, a[0], a[1], np.log(a[1] - a[0])]
+        elif kind == "fixed":
+            row = [a[0], 0.0, a[0], a[0], 0.0]
+        else:
+            raise ValueError(f"unknown prior kind {kind!r}")
+        rows.append([float(PRIOR_KINDS[kind])] + row)
+    return np.asarray(rows, dtype=np.float64)
+
+
+def log_prior_density(model, theta):
+    """log p(theta) under the model's prior, float64: theta [..., P] -> [...], the sum over the columns of prior_table(model)'s
+    densities; -inf where a component is outside its support or not finite.  The host definition of what the importance kernel
+    evaluates (amortizer.importance_weights)."""
+    table = prior_table(model)
+    th = np.asarray(theta, dtype=np.float64)
+    if th.shape[-1] != table.shape[0]:
+        raise ValueError(f"theta must have {table.shape[0]} columns, got {th.shape}")
+    out = np.zeros(th.shape[:-1])
+    with np.errstate(all="ignore"):
+        for d, (kind, p1, p2, lo, hi, ln) in enumerate(table):
+            x = th[..., d]
+            if kind in (0.0, 1.0):
+                u = (x - p1) / p2
+                lp = -0.5 * u * u - ln
+            elif kind == 2.0:
+                ta = 0.0 if p1 == 1.0 else (p1 - 1.0) * np.log(x)
+                tb = 0.0 if p2 == 1.0 else (p2 - 1.0) * np.log1p(-x)
+                lp = ta + tb - ln
+            else:
+                lp = np.full(x.shape, -ln)
+            out = out + np.where(np.isfinite(x) & (x >= lo) & (x <= hi), lp, -np.inf)
+    return out
+
+
 class DevicePrior:
     """Batched on-device draw_prior: `DevicePrior('basic')(B)` -> torch float32 [B, P] on the GPU.
 
