@@ -1,6 +1,6 @@
 """ctypes binding of libnddm_train.so: the amortizer's flow as one kernel each way (csrc/train_kernels.hip), its inverse -- the
 posterior sampler -- as one kernel (csrc/train_sample.hip), the draws' order statistics (csrc/train_quantile.hip) and importance weights (csrc/train_importance.hip), and the summary
-network's per-trial MLPs (csrc/train_deepset.hip), and the optimizer step on flat buffers (csrc/train_update.hip).
+network's per-trial MLPs and its inference forward with a trial count per set (csrc/train_deepset.hip), and the optimizer step on flat buffers (csrc/train_update.hip).
 Optional: `lib()` returns None when the library cannot be built or loaded, and the amortizer then runs its PyTorch path."""
 import ctypes
 import os
@@ -63,6 +63,11 @@ def lib():
     L.nddm_deepset_reduce.argtypes = [fp, i32, i32, i32, i32, fp, vp]
     L.nddm_deepset_reduce.restype = i32
     i64 = c.c_longlong
+    L.nddm_deepset_summary_work_bytes.argtypes = [i32, i32, i32]                                                 # B N blocks
+    L.nddm_deepset_summary_work_bytes.restype = i64
+    #                                   x  d_in B    N   counts blocks params summary_dim direct n_direct direct_stride out work work_bytes stream
+    L.nddm_deepset_summary.argtypes = [fp, i32, i32, i32, vp, i32, c.POINTER(vp), i32, fp, i32, i32, fp, vp, i64, vp]
+    L.nddm_deepset_summary.restype = i32
     L.nddm_train_adam_step.argtypes = [fp, fp, fp, fp, i64, fp, f32, f32, f32, f32, f32, f32, f32, fp, fp, fp, fp, i32, fp, vp]
     L.nddm_train_adam_step.restype = i32
     L.nddm_train_stage.argtypes = [fp, fp, i64, fp, fp, i64, fp, f32, f32, vp]

@@ -112,13 +112,29 @@ class InvariantNetwork(nn.Module):
         # kernels produce no gradient of the data.
         if not torch.is_grad_enabled() or x.shape[0] * x.shape[1] > self.FUSED_MAX_ROWS or x.requires_grad:
             return None
+        return self._deepset_lib(x.shape[2])
+
+    def _deepset_lib(self, d_in):
+        """libnddm_train.so if the network has the shape its DeepSet kernels are written for (3-layer ReLU MLPs of hidden width 64)."""
         mlps = [m for blk in self.equiv for m in (blk.inv, blk.eq)] + [self.pre_pool, self.post_pool]
         if any(len(m) != 5 or not isinstance(m[1], nn.ReLU) or m[2].weight.shape != (64, 64) or m[4].weight.shape[1] != 64
                for m in mlps) or any(m[4].weight.shape[0] != 64 for m in mlps[:-1]) or not 1 <= self.summary_dim <= 64:
             return None
         from . import _train_lib
         L = _train_lib.lib()
-        return L if L is not None and L.nddm_deepset_supported(64, x.shape[2]) else None
+        return L if L is not None and L.nddm_deepset_supported(64, d_in) else None
+
+    def _summary_lib(self, x, direct):
+        """`summarize`'s gate, its own (`_fused_lib` is the training path's and refuses no_grad): the library if the inference
+        kernels (csrc/train_deepset.hip: nddm_deepset_summary) serve this tensor -- cuda, float32, [B, N, d_in <= 4] -- this network
+        (hidden width 64, float32 parameters on x's device) and these direct conditions ([B, k] with summary_dim + k <= 64)."""
+        if not (self.fused and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] >= 1 and x.shape[1] >= 1 and x.shape[2] <= 4):
+            return None
+        if direct is not None and (direct.dim() != 2 or direct.shape[0] != x.shape[0] or self.summary_dim + direct.shape[1] > 64):
+            return None
+        if any(p.dtype != torch.float32 or p.device != x.device or not p.is_contiguous() for p in self.parameters()):
+            return None
+        return self._deepset_lib(x.shape[2])
 
     def fused_params(self):
         """The parameter tensors in the order the kernels (and their flat weight-gradient buffer) take them: per block the
@@ -132,14 +148,80 @@ class InvariantNetwork(nn.Module):
 
     FUSED_MAX_ROWS = 1 << 19      # sets x trials (the training loop's 32 x 300 is 9600): 1.3 GB of saved activations at the cap
 
-    def forward(self, x, mask=None, inv_n=None, n_valid=None, direct=None):
+    @staticmethod
+    def _set_counts(counts, B, N, device):
+        """counts -> int32 [B] on `device`.  Host-side counts (a sequence, an array, a CPU tensor) are checked against [1, N]; a
+        tensor already on an accelerator is not read back: its rows are the caller's responsibility."""
+        if torch.is_tensor(counts) and counts.device.type != "cpu":
+            c = counts.reshape(-1)
+        else:
+            c = torch.as_tensor(np.asarray(counts.detach().numpy() if torch.is_tensor(counts) else counts)).reshape(-1)
+            if c.numel() and (c.is_floating_point() and bool((c != c.round()).any()) or int(c.min()) < 1 or int(c.max()) > N):
+                raise ValueError(f"counts must be whole numbers in [1, {N}] (the sets are padded to {N} trials)")
+        if c.numel() != B:
+            raise ValueError(f"counts has {c.numel()} entries for {B} data sets")
+        return c.to(device=device, dtype=torch.int32)
+
+    def _forward_counts(self, x, counts, direct):
+        """The definition of a ragged batch (`forward(x, counts=...)`): the mask / inv_n arithmetic with a mask [B, N, 1] and a
+        1 / n per set; the padding is zeroed first, so whatever it holds (NaN too) never enters a product."""
+        B, N = x.shape[0], x.shape[1]
+        c = self._set_counts(counts, B, N, x.device)
+        real = torch.arange(N, device=x.device).view(1, N, 1) < c.view(B, 1, 1)
+        mask, inv_n = real.to(x.dtype), 1.0 / c.to(x.dtype)
+        x = torch.where(real, x, torch.zeros((), dtype=x.dtype, device=x.device))
+        for block in self.equiv:
+            x = block(x, mask, inv_n.view(B, 1, 1))
+        summ = self.post_pool((self.pre_pool(x) * mask).sum(dim=1) * inv_n.view(B, 1))
+        return summ if direct is None else torch.cat([summ, direct.to(summ.device, summ.dtype)], dim=-1)
+
+    @torch.no_grad()
+    def summarize(self, x, counts=None, direct=None):
+        """The inference forward: x [B, N, d] -> [B, summary_dim (+ k)], where set b's summary is over its first counts[b] trials
+        (counts: B whole numbers in [1, N], a sequence or a tensor; None: all N of every set) and direct [B, k] is appended as
+        `forward` appends it.  On the device -- float32, hidden width 64, d <= 4, summary_dim + k <= 64, `self.fused` -- the whole
+        network is blocks + 2 launches that keep nothing for a backward and never read a row at or beyond its set's count (csrc/
+        train_deepset.hip: nddm_deepset_summary); row b is bit for bit what the call gives for x[b:b+1, :counts[b]] alone, and with
+        equal counts what the training kernels' forward gives.  Everywhere else: `forward(x, counts=counts, direct=direct)`."""
+        if direct is not None:
+            direct = torch.as_tensor(direct).to(x.device, x.dtype)
+        L = self._summary_lib(x, direct)
+        if L is None:
+            return self.forward(x, direct=direct) if counts is None else self.forward(x, counts=counts, direct=direct)
+        import ctypes
+        B, N, d = x.shape
+        x = x.contiguous()
+        cnt = None if counts is None else self._set_counts(counts, B, N, x.device).contiguous()
+        params, nb = self.fused_params(), len(self.equiv)
+        ptrs = (ctypes.c_void_p * len(params))(*[p.data_ptr() for p in params])
+        k = 0 if direct is None else direct.shape[1]
+        if direct is not None and k > 1 and direct.stride(1) != 1:
+            direct = direct.contiguous()
+        nbytes = L.nddm_deepset_summary_work_bytes(B, N, nb)
+        work = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
+        out = torch.empty((B, self.summary_dim + k), dtype=torch.float32, device=x.device)
+        rc = L.nddm_deepset_summary(x.data_ptr(), d, B, N, None if cnt is None else cnt.data_ptr(), nb, ptrs, self.summary_dim,
+                                    None if direct is None else direct.data_ptr(), k, 0 if direct is None else direct.stride(0),
+                                    out.data_ptr(), work.data_ptr(), nbytes, torch.cuda.current_stream(x.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"nddm_deepset_summary failed ({rc})")
+        return out
+
+    def forward(self, x, mask=None, inv_n=None, n_valid=None, direct=None, counts=None):
         """direct [B, k] (or broadcastable rows): "direct conditions" (log N, basic_ddm_dc.py:151-155) appended to the summary --
         the result is then the flow's condition [B, summary_dim + k] (the kernels write both into one buffer: no concatenation,
         and the backward takes the condition's gradient as it comes).
         mask [1, N, 1] (1 = a real trial, 0 = padding) and inv_n = 1 / (number of real trials), both device tensors -- or
         n_valid, the number of real trials as a device scalar (the first n_valid trials are the real ones): the pooled means
         then run over the real trials only, so a batch padded to a fixed length (one hipGraph per length bucket,
-        GraphTrainer) gives what the unpadded batch gives."""
+        GraphTrainer) gives what the unpadded batch gives.
+        counts (B whole numbers in [1, N]; not with mask / inv_n / n_valid): a RAGGED batch -- the first counts[b] trials of set b
+        are real and row b of the result is what the network gives for x[b:b+1, :counts[b]] alone, to float32 round-off.  This
+        is the PyTorch composition on every device (differentiable in the parameters); `summarize` is its inference kernel."""
+        if counts is not None:
+            if mask is not None or inv_n is not None or n_valid is not None:
+                raise ValueError("counts (a trial count per set) cannot be combined with mask / inv_n / n_valid (batch-shared)")
+            return self._forward_counts(x, counts, direct)
         L = self._fused_lib(x)
         if direct is not None and (L is None or direct.dim() != 2 or direct.shape[0] != x.shape[0] or direct.dtype != torch.float32
                                    or self.summary_dim + direct.shape[1] > 64 or direct.requires_grad):
@@ -764,6 +846,35 @@ def importance_weights(theta, log_q, log_lik, prior, want_log_w=False, out=None)
     return res
 
 
+def observed_batch(datasets, device=None):
+    """Observed data sets of DIFFERENT trial counts -- a sequence of arrays [n_b, d], a participant each -- as ONE amortizer input:
+    {"summary_conditions": float32 [B, max n_b, d], set b's trials first and ZEROS after them; "summary_counts": int32 [B], the n_b;
+    "direct_conditions": float32 [B, 1], log n_b (what the models' configurators compute from sim_non_batchable_context)}, torch
+    tensors on `device` (None: the CPU).  With it
+
+        post = amortizer.sample(observed_batch(per_participant), 1000, fused=True)
+
+    replaces the reference's loop of one configurator(...) and one amortizer.sample(...) per participant (fitting_stahl_data.py:
+    196-211); posterior_moments, posterior_summary and log_posterior take the same dict.  The summary network never reads the
+    padding.  posterior_importance does, and the ZERO padding is what makes it work there: a row (rt 0, choice 0) is to basic_ddm_dc's
+    likelihood a censored timeout at t = 0 - tau <= 0, which scores log 1 = 0 (csrc/nddm_wiener.h), so a padded set's likelihood
+    is its own trials'."""
+    sets = [np.asarray(s, dtype=np.float32) for s in datasets]
+    if not sets:
+        raise ValueError("observed_batch needs at least one data set")
+    if any(s.ndim != 2 or s.shape[0] < 1 for s in sets):
+        raise ValueError("every data set must be an array [n_b, d] with n_b >= 1 trials")
+    d = sets[0].shape[1]
+    if d < 1 or any(s.shape[1] != d for s in sets):
+        raise ValueError(f"every data set must have the same number of columns; got {sorted({s.shape[1] for s in sets})}")
+    counts = np.array([s.shape[0] for s in sets], dtype=np.int32)
+    x = np.zeros((len(sets), int(counts.max()), d), dtype=np.float32)
+    for b, s in enumerate(sets):
+        x[b, :s.shape[0]] = s
+    out = {"summary_conditions": x, "summary_counts": counts, "direct_conditions": np.log(counts.astype(np.float64)).astype(np.float32)[:, None]}
+    return {k: torch.as_tensor(v, device=device) for k, v in out.items()}
+
+
 class AmortizedPosterior(nn.Module):
     """bf.amortizers.AmortizedPosterior(inference_net, summary_net): maximum-likelihood training of q(theta | data)."""
 
@@ -781,6 +892,14 @@ class AmortizedPosterior(nn.Module):
         x = self._t(input_dict["summary_conditions"])
         direct = input_dict.get("direct_conditions", None)
         direct = None if direct is None else self._t(direct)
+        cnt = input_dict.get("summary_counts", None)      # a trial count per set (additive key): a ragged batch, `observed_batch`
+        if cnt is not None:
+            if pad is not None or nv is not None:
+                raise ValueError("summary_counts (a trial count per set) cannot be combined with summary_mask / summary_n (batch-shared)")
+            if not isinstance(self.summary_net, InvariantNetwork):
+                raise TypeError("summary_counts needs a summary network that takes a count per set (InvariantNetwork)")
+            # inference (sample, posterior_*, log_posterior) through the kernels, training through the differentiable definition
+            return self.summary_net(x, counts=cnt, direct=direct) if torch.is_grad_enabled() else self.summary_net.summarize(x, cnt, direct)
         if direct is not None and isinstance(self.summary_net, InvariantNetwork):
             # (the summary network appends the direct conditions itself: with the kernels, without a concatenation)
             if nv is not None:
@@ -968,7 +1087,11 @@ class AmortizedPosterior(nn.Module):
         the fused sampler writes draws and log q into scratch (csrc/train_sample.hip), the broadcast-layout Wiener likelihood scores
         them against the set's trials, input_dict["summary_conditions"] -- basic_ddm_dc's (rt, choice), timeouts right-censored --
         and csrc/train_importance.hip weighs and reduces.  Where the fused sampler does not apply the draws and log q come from
-        inverse_with_log_density.  model: "basic" only; the single-trial models' likelihood is not wired here yet."""
+        inverse_with_log_density.  model: "basic" only; the single-trial models' likelihood is not wired here yet.
+
+        A ragged batch (`observed_batch`: "summary_counts") needs nothing more, because its padding is ZEROS: the likelihood scores
+        all max n_b rows of every set, and a row (rt 0, choice 0) is a timeout censored at t = -tau <= 0, log 1 = 0 exactly, so each
+        set's log-likelihood is its own trials' (tests/test_gpu_ragged_summary.py).  Padding of any other value would be scored."""
         if model != "basic":
             raise NotImplementedError(f"posterior_importance scores model='basic' only; for {model!r} the next step is the marginal "
                                       "likelihood, likelihood.single_trial_logpdf, as the target")

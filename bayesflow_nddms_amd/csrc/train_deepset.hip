@@ -14,6 +14,9 @@
 // Every step of a layer is written ONCE ("the forward steps", "the backward steps"); the four kernels are sequences of those calls, so the
 // kernels that run two MLPs in one launch write what two launches of the single kernels write, bit for bit
 // (tests/test_gpu_deepset_pairs.py).
+// Inference (nddm_deepset_summary, at the end of the forward section): the same forward steps with nothing saved for a backward and a
+// trial count PER SET -- the whole summary network of a batch of data sets of different sizes in blocks + 2 launches
+// (tests/test_gpu_ragged_summary.py).
 // gfx950 only.  tests/test_gpu_training.py compares with the PyTorch composition.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,9 +70,17 @@ struct Lane {
 struct Span {
     int b, sp, n_begin, n_end, wg;
     long long row0;                         // the set's first row of every [B * N, .] array
-    __device__ __forceinline__ Span(const Common &C)
-        : b(blockIdx.x / C.S), sp(blockIdx.x - b * C.S), n_begin(sp * C.rows_per_wg), n_end(min(C.N, n_begin + C.rows_per_wg)), wg(blockIdx.x),
+    __device__ __forceinline__ Span(const Common &C) : Span(C, C.N) {}
+    // ... of a set whose rows end at n_valid <= N (inference: the set's own count; n_end <= n_begin: the workgroup owns no trial)
+    __device__ __forceinline__ Span(const Common &C, int n_valid)
+        : b(blockIdx.x / C.S), sp(blockIdx.x - b * C.S), n_begin(sp * C.rows_per_wg), n_end(min(n_valid, n_begin + C.rows_per_wg)), wg(blockIdx.x),
           row0((long long)b * C.N) {}
+};
+// Inference (nddm_deepset_summary): every set has its own number of real trials, its first n[b] of n_max (null: n_max of every set)
+struct SetCounts {
+    const int *n; int n_max;
+    __device__ __forceinline__ int of(int b) const { return n ? min(max(n[b], 0), n_max) : n_max; }
+    __device__ __forceinline__ float inv(int b) const { return 1.0f / (float)of(b); }
 };
 
 // acc += A B over 64 k's.  Lane l holds A[i = l & 31][k] and B[k][j = l & 31] for the 32 k's of its half (l >> 5): the order of
@@ -179,13 +190,15 @@ __device__ __forceinline__ float4 x_row4(const Common &C, long long row, int c4,
     a.x *= inv_n; a.y *= inv_n; a.z *= inv_n; a.w *= inv_n;
     return a;
 }
-// fetch_tile of a 64-wide input (store_tile stores it)
-__device__ __forceinline__ void fetch_x_tile(f32x4 (&v)[NQ], const Common &C, const Span &W, int n0, float inv_n, int t)
+// fetch_tile of a 64-wide input (store_tile stores it).  rows: not null (the MLP after the pooling at inference, one row per set):
+// every row takes the 1 / n of its own set instead of inv_n
+__device__ __forceinline__ void fetch_x_tile(f32x4 (&v)[NQ], const Common &C, const Span &W, int n0, float inv_n, int t, const SetCounts *rows = nullptr)
 {
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
         const int p = t + NT * k, r = p >> 4, c4 = p & 15;
-        const float4 xv = x_row4(C, W.row0 + min(n0 + r, W.n_end - 1), c4, inv_n);       // (clamped: rows beyond the range are zeroed at the store)
+        const long long row = W.row0 + min(n0 + r, W.n_end - 1);                         // (clamped: rows beyond the range are zeroed at the store)
+        const float4 xv = x_row4(C, row, c4, rows ? rows->inv((int)row) : inv_n);
         v[k] = f32x4{xv.x, xv.y, xv.z, xv.w};
     }
 }
@@ -254,9 +267,9 @@ __device__ __forceinline__ void context_issue(const Common &C, int b, int t, Ctx
         L.b1 = C.P.b1[t & (HS - 1)];
     }
 }
-__device__ __forceinline__ void context_publish(const Common &C, float *pooled, int t, const CtxLoad &L)
+__device__ __forceinline__ void context_publish(const Common &C, float *pooled, int t, const CtxLoad &L, float inv_n)
 {
-    if (C.ctx_part && t < HS) pooled[t] = L.sum * inv_count(C);
+    if (C.ctx_part && t < HS) pooled[t] = L.sum * inv_n;
 }
 __device__ __forceinline__ void context_product(const Common &C, const float *pooled, float *cs, int t, const CtxLoad &L)   // (behind a barrier)
 {
@@ -272,11 +285,11 @@ __device__ __forceinline__ void context_product(const Common &C, const float *po
         cs[t] = L.b1;
     }
 }
-__device__ __forceinline__ void context(const Common &C, int b, float *pooled, float *cs, int t)
+__device__ __forceinline__ void context(const Common &C, int b, float *pooled, float *cs, int t, float inv_n)
 {
     CtxLoad L;
     context_issue(C, b, t, L);
-    context_publish(C, pooled, t, L);
+    context_publish(C, pooled, t, L, inv_n);
     if (C.ctx_part) __syncthreads();
     context_product(C, pooled, cs, t, L);
 }
@@ -287,8 +300,9 @@ __device__ __forceinline__ f32x16 fwd_product(const float (*in)[LD], const float
 {
     return mma64<1, 1>(&in[32 * L.rb + L.m][32 * L.kk], &w[L.u][32 * L.kk], zero16());
 }
-// a hidden layer: out = ReLU(in W^T + bias), to LDS (the next layer's input) and to global memory (saved for the backward; rows
-// beyond the tile's valid ones are dropped by g's range check)
+// a hidden layer: out = ReLU(in W^T + bias), to LDS (the next layer's input) and (SAVE: training) to global memory, saved for the
+// backward; rows beyond the tile's valid ones are dropped by g's range check
+template <bool SAVE = true>
 __device__ __forceinline__ void relu_layer(const float (*in)[LD], const float (*w)[LD], float bias, float (*out)[LD], const RowTile &g, const Lane &L)
 {
     const f32x16 acc = fwd_product(in, w, L);
@@ -297,10 +311,11 @@ __device__ __forceinline__ void relu_layer(const float (*in)[LD], const float (*
         const int r = 32 * L.rb + drow(v, L.kk);
         const float val = fmaxf(acc[v] + bias, 0.0f);
         out[r][L.u] = val;
-        g.put(r, L.u, val);
+        if (SAVE) g.put(r, L.u, val);
     }
 }
 // the first hidden layer of a small input as plain FMAs (cs: bias and context): thread (unit t & 63, rows 16 (t >> 6) ...)
+template <bool SAVE = true>
 __device__ __forceinline__ void small_layer1(const float (*xsmall)[DS_MAX], const float (*w1small)[DS_MAX], const float *cs, int d_in,
                                              float (*out)[LD], const RowTile &g, const Lane &L)
 {
@@ -316,7 +331,7 @@ __device__ __forceinline__ void small_layer1(const float (*xsmall)[DS_MAX], cons
         for (int c = 0; c < DS_MAX; ++c) if (c < d_in) a = fmaf(w[c], xsmall[r][c], a);
         const float val = fmaxf(a, 0.0f);
         out[r][L.uu] = val;
-        g.put(r, L.uu, val);
+        if (SAVE) g.put(r, L.uu, val);
     }
 }
 // the masked sums of an output over the workgroup's trials: the fixed-order sum of the four lanes that share a column
@@ -340,8 +355,37 @@ struct FwdOut {
     int n_extra, extra_stride;   // "direct conditions" of the amortizer (log N) appended to the summary without a concatenation
 };
 
-template <bool BIG>        // d_in == 64 (layer 1 is an MFMA product) or d_in <= DS_MAX
-__global__ __launch_bounds__(NT) void mlp_fwd_kernel(Common C, FwdOut O)
+// layer 3 (no activation) of one tile: its output rows -- and the direct conditions' columns beside them -- to y, and this thread's
+// share of the masked sums of the output into pacc.  rows (see fetch_x_tile): the row of a set WITHOUT trials is NaN -- its input, a
+// mean over nothing, is 0 x inf already, but the ReLUs' fmaxf gives a NaN no way through the layers, so it is written here
+__device__ __forceinline__ void output_layer(const float (*in)[LD], const float (*w)[LD], float bias3, const Common &C, const FwdOut &O, const Span &W,
+                                             int n0, float &pacc, const Lane &L, const SetCounts *rows = nullptr)
+{
+    const int u = L.u, n_end = W.n_end;
+    const f32x16 acc = fwd_product(in, w, L);
+    // (branch-free: y as a raw buffer of the tile's valid rows -- of NO rows if y is not wanted -- whose range check drops the
+    //  stores of the other rows; a lane whose column is not written aims past the buffer; the pooled sum takes a zero mask)
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(O.y ? O.y + (W.row0 + n0) * O.ldy : O.h1, 0,
+                                                                          O.y ? (n_end - n0) * O.ldy * 4 : 0, 0x00020000);
+    const bool colv = u < C.d_out, cole = O.extra && !colv && u < C.d_out + O.n_extra;
+    const int ue = min(max(u - C.d_out, 0), max(O.n_extra - 1, 0));
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const int r = 32 * L.rb + drow(v, L.kk), n = n0 + r;
+        float val = acc[v] + bias3;
+        if (rows) val = rows->of((int)W.row0 + min(n, n_end - 1)) > 0 ? val : __builtin_nanf("");
+        if (O.pool_part) pacc = fmaf(colv ? mask_or_zero(C, n, n_end) : 0.0f, val, pacc);
+        float outv = val;
+        if (O.extra) { const float e = O.extra[(W.row0 + min(n, n_end - 1)) * O.extra_stride + ue]; outv = cole ? e : val; }
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, outv), ry, (colv || cole) ? (r * O.ldy + u) * 4 : 0x7ffffff0, 0, 0);
+    }
+}
+
+// One MLP over the workgroup's trials W, as the sequence of steps that both the training kernel (SAVE: h1 and h2 go to global
+// memory for the backward) and the inference kernels (not SAVE: nothing but y / pool_part is written) are.  inv_n: 1 / (the set's
+// number of real trials); rows: see fetch_x_tile.
+template <bool BIG, bool SAVE>        // BIG: d_in == 64 (layer 1 is an MFMA product) or d_in <= DS_MAX
+__device__ __forceinline__ void mlp_fwd_steps(const Common &C, const FwdOut &O, const Span &W, float inv_n, const SetCounts *rows)
 {
     __shared__ __attribute__((aligned(16))) float w1s[BIG ? HS : 1][LD];
     __shared__ __attribute__((aligned(16))) float w2s[HS][LD];
@@ -352,15 +396,13 @@ __global__ __launch_bounds__(NT) void mlp_fwd_kernel(Common C, FwdOut O)
     __shared__ float w1small[BIG ? 1 : HS][DS_MAX], xsmall[BIG ? 1 : TM][DS_MAX];
     __shared__ float cs[HS], pooled[HS], red[4][64];
     const Lane L;
-    const Span W(C);
     const int t = L.t, u = L.u, n_begin = W.n_begin, n_end = W.n_end;
     STAMP(100);
-    const float inv_n = inv_count(C);
     // every global load first: W1 (needed first), W2, W3 into registers; W2 and W3 go to LDS behind layers 1 and 2 (the barriers
     // that are there anyway), so their latency runs beside the input tile's, the context's and layer 1
     // (the loads complete in issue order: the input tile and W1 first, they are stored first)
     f32x4 r1[NQ], r2[NQ], r3[NQ], rx[NQ];
-    if (BIG) fetch_x_tile(rx, C, W, n_begin, inv_n, t);
+    if (BIG) fetch_x_tile(rx, C, W, n_begin, inv_n, t, rows);
     else fill_xsmall(xsmall, C, W, n_begin, t);
     fetch64(r1, BIG ? C.P.W1 : C.P.W2, BIG ? C.P.ldw1 : HS, t);
     fetch64(r2, C.P.W2, HS, t);
@@ -369,7 +411,7 @@ __global__ __launch_bounds__(NT) void mlp_fwd_kernel(Common C, FwdOut O)
         store_tile(xs, rx, W, n_begin, t);
         store64(w1s, r1, t);
     } else fill_w1small(w1small, C, t);
-    context(C, W.b, pooled, cs, t);
+    context(C, W.b, pooled, cs, t, inv_n);
     __syncthreads();
     const float bias2 = C.P.b2[u], bias3 = u < C.d_out ? C.P.b3[u] : 0.0f, bias1 = cs[u];
     float pacc = 0.0f;
@@ -377,44 +419,33 @@ __global__ __launch_bounds__(NT) void mlp_fwd_kernel(Common C, FwdOut O)
     for (int n0 = n_begin; n0 < n_end; n0 += TM) {
         if (n0 != n_begin) {
             if (BIG) {
-                fetch_x_tile(rx, C, W, n0, inv_n, t);
+                fetch_x_tile(rx, C, W, n0, inv_n, t, rows);
                 store_tile(xs, rx, W, n0, t);
             } else fill_xsmall(xsmall, C, W, n0, t);
             __syncthreads();
         }
         STAMP(102);
-        const RowTile th1(O.h1 + (W.row0 + n0) * HS, n_end - n0), th2(O.h2 + (W.row0 + n0) * HS, n_end - n0);
-        if (BIG) relu_layer(xs, w1s, bias1, h1s, th1, L);                   // layer 1
-        else small_layer1(xsmall, w1small, cs, C.d_in, h1s, th1, L);
+        const RowTile th1(O.h1 + (W.row0 + n0) * HS, SAVE ? n_end - n0 : 0), th2(O.h2 + (W.row0 + n0) * HS, SAVE ? n_end - n0 : 0);
+        if (BIG) relu_layer<SAVE>(xs, w1s, bias1, h1s, th1, L);             // layer 1
+        else small_layer1<SAVE>(xsmall, w1small, cs, C.d_in, h1s, th1, L);
         if (n0 == n_begin) store64(w2s, r2, t);      // (its first reader is layer 2, behind the barrier)
         __syncthreads();
         STAMP(103);
-        relu_layer(h1s, w2s, bias2, h2s, th2, L);    // layer 2
+        relu_layer<SAVE>(h1s, w2s, bias2, h2s, th2, L);      // layer 2
         if (n0 == n_begin) store64(w3s, r3, t, C.d_out);
         __syncthreads();
         STAMP(104);
-        {                                            // layer 3 (no activation), and the masked sums of its output
-            const f32x16 acc = fwd_product(h2s, w3s, L);
-            // (branch-free: y as a raw buffer of the tile's valid rows -- of NO rows if y is not wanted -- whose range check drops the
-            //  stores of the other rows; a lane whose column is not written aims past the buffer; the pooled sum takes a zero mask)
-            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(O.y ? O.y + (W.row0 + n0) * O.ldy : O.h1, 0,
-                                                                                  O.y ? (n_end - n0) * O.ldy * 4 : 0, 0x00020000);
-            const bool colv = u < C.d_out, cole = O.extra && !colv && u < C.d_out + O.n_extra;
-            const int ue = min(max(u - C.d_out, 0), max(O.n_extra - 1, 0));
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int r = 32 * L.rb + drow(v, L.kk), n = n0 + r;
-                const float val = acc[v] + bias3;
-                if (O.pool_part) pacc = fmaf(colv ? mask_or_zero(C, n, n_end) : 0.0f, val, pacc);
-                float outv = val;
-                if (O.extra) { const float e = O.extra[(W.row0 + min(n, n_end - 1)) * O.extra_stride + ue]; outv = cole ? e : val; }
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, outv), ry, (colv || cole) ? (r * O.ldy + u) * 4 : 0x7ffffff0, 0, 0);
-            }
-        }
+        output_layer(h2s, w3s, bias3, C, O, W, n0, pacc, L, rows);       // layer 3, and the masked sums of its output
         STAMP(105);
         // (the next tile's writes to xs / h1s / h2s are each behind a barrier every reader of this tile has passed)
     }
     if (O.pool_part) pooled_sum(red, pacc, O.pool_part + (long long)W.wg * HS, L);
+}
+
+template <bool BIG>
+__global__ __launch_bounds__(NT) void mlp_fwd_kernel(Common C, FwdOut O)
+{
+    mlp_fwd_steps<BIG, true>(C, O, Span(C), inv_count(C), nullptr);
 }
 
 // ---- two MLPs in one launch --------------------------------------------------------------------------------------------------
@@ -423,8 +454,10 @@ __global__ __launch_bounds__(NT) void mlp_fwd_kernel(Common C, FwdOut O)
 // output are wanted).  B's rows are A's rows, so nothing crosses a workgroup between them: the y tile stays in LDS as B's input,
 // B's three weight matrices are fetched into registers while A computes and stored to LDS when A's readers are done -- one launch
 // and one exposed weight-staging latency instead of two of each.  One 64-row tile per workgroup (rows_per_wg == TM).
-template <bool BIG>        // of MLP A: d_in == 64 or d_in <= DS_MAX (B's input is A's 64-wide output)
-__global__ __launch_bounds__(NT) void mlp2_fwd_kernel(Common C, FwdOut O, Mlp P2, FwdOut O2)
+// As steps over the workgroup's trials W, like mlp_fwd_steps: SAVE (training) stores both MLPs' h1 / h2 and always y; not SAVE
+// (inference) only O2.pool_part, and y where O.y is not null (the next block reads it; after the last block nobody does).
+template <bool BIG, bool SAVE>        // BIG, of MLP A: d_in == 64 or d_in <= DS_MAX (B's input is A's 64-wide output)
+__device__ __forceinline__ void mlp2_fwd_steps(const Common &C, const FwdOut &O, const Mlp &P2, const FwdOut &O2, const Span &W, float inv_n)
 {
     __shared__ __attribute__((aligned(16))) float w1s[HS][LD];
     __shared__ __attribute__((aligned(16))) float w2s[HS][LD];
@@ -435,9 +468,7 @@ __global__ __launch_bounds__(NT) void mlp2_fwd_kernel(Common C, FwdOut O, Mlp P2
     __shared__ float w1small[BIG ? 1 : HS][DS_MAX], xsmall[BIG ? 1 : TM][DS_MAX];
     __shared__ float cs[HS], pooled[HS], red[4][64];
     const Lane L;
-    const Span W(C);
     const int t = L.t, u = L.u, n0 = W.n_begin, n_end = W.n_end;
-    const float inv_n = inv_count(C);
     // ---- every global load up front, in the order of need: A's input tile and W1 (stored at once), A's W2 and W3 (stored behind
     //      A's layers 1 and 2), B's three matrices (stored when A is done)
     f32x4 r1[NQ], r2[NQ], r3[NQ], rx[NQ];
@@ -454,19 +485,20 @@ __global__ __launch_bounds__(NT) void mlp2_fwd_kernel(Common C, FwdOut O, Mlp P2
         store_tile(xs, rx, W, n0, t);
         store64(w1s, r1, t);
     } else fill_w1small(w1small, C, t);
-    context(C, W.b, pooled, cs, t);
+    context(C, W.b, pooled, cs, t, inv_n);
     __syncthreads();
     const float bias2 = C.P.b2[u], bias3 = C.P.b3[u], bias1 = cs[u];
     const float c1 = P2.b1[u], c2 = P2.b2[u], c3 = P2.b3[u];
-    const int nv = n_end - n0;                       // the tile's valid rows: stores beyond them are dropped by the buffers' range check
-    const RowTile th1(O.h1 + (W.row0 + n0) * HS, nv), th2(O.h2 + (W.row0 + n0) * HS, nv), ty(O.y + (W.row0 + n0) * HS, nv);
-    const RowTile tg1(O2.h1 + (W.row0 + n0) * HS, nv), tg2(O2.h2 + (W.row0 + n0) * HS, nv);
+    const int nv = n_end - n0, ns = SAVE ? nv : 0;   // the tile's valid rows: stores beyond them are dropped by the buffers' range check
+    const bool want_y = SAVE || O.y != nullptr;
+    const RowTile th1(O.h1 + (W.row0 + n0) * HS, ns), th2(O.h2 + (W.row0 + n0) * HS, ns), ty(O.y + (W.row0 + n0) * HS, want_y ? nv : 0);
+    const RowTile tg1(O2.h1 + (W.row0 + n0) * HS, ns), tg2(O2.h2 + (W.row0 + n0) * HS, ns);
     // ---- MLP A
-    if (BIG) relu_layer(xs, w1s, bias1, h1s, th1, L);
-    else small_layer1(xsmall, w1small, cs, C.d_in, h1s, th1, L);
+    if (BIG) relu_layer<SAVE>(xs, w1s, bias1, h1s, th1, L);
+    else small_layer1<SAVE>(xsmall, w1small, cs, C.d_in, h1s, th1, L);
     store64(w2s, r2, t);
     __syncthreads();
-    relu_layer(h1s, w2s, bias2, h2s, th2, L);
+    relu_layer<SAVE>(h1s, w2s, bias2, h2s, th2, L);
     store64(w3s, r3, t);
     __syncthreads();
     {   // A's output: to global memory (the next equivariant MLP and the backward read it) and into xs as B's input
@@ -476,7 +508,7 @@ __global__ __launch_bounds__(NT) void mlp2_fwd_kernel(Common C, FwdOut O, Mlp P2
             const int r = 32 * L.rb + drow(v, L.kk), n = n0 + r;
             const float val = n < n_end ? acc[v] + bias3 : 0.0f;          // (rows beyond the set: zero, as a loaded tile has them)
             xs[r][u] = val;                                               // (xs: A's layer 1 finished reading it two barriers ago)
-            ty.put(r, u, val);
+            if (want_y) ty.put(r, u, val);
         }
     }
     __syncthreads();                                 // A's readers of w1s / w2s / w3s / h1s / h2s are done; xs is complete
@@ -485,9 +517,9 @@ __global__ __launch_bounds__(NT) void mlp2_fwd_kernel(Common C, FwdOut O, Mlp P2
     store64(w3s, q3, t);
     __syncthreads();
     // ---- MLP B
-    relu_layer(xs, w1s, c1, h1s, tg1, L);
+    relu_layer<SAVE>(xs, w1s, c1, h1s, tg1, L);
     __syncthreads();
-    relu_layer(h1s, w2s, c2, h2s, tg2, L);
+    relu_layer<SAVE>(h1s, w2s, c2, h2s, tg2, L);
     __syncthreads();
     float pacc = 0.0f;
     {
@@ -499,6 +531,47 @@ __global__ __launch_bounds__(NT) void mlp2_fwd_kernel(Common C, FwdOut O, Mlp P2
         }
     }
     pooled_sum(red, pacc, O2.pool_part + (long long)W.wg * HS, L);
+}
+
+template <bool BIG>
+__global__ __launch_bounds__(NT) void mlp2_fwd_kernel(Common C, FwdOut O, Mlp P2, FwdOut O2)
+{
+    mlp2_fwd_steps<BIG, true>(C, O, P2, O2, Span(C), inv_count(C));
+}
+
+// ---- inference: the whole summary network with a trial count per set (nddm_deepset_summary) -----------------------------------
+// The same steps, one 64-row tile per workgroup as in training, with three differences: nothing is saved for a backward; set b's rows
+// end at its own count K.of(b), so a row at or beyond it is never loaded (Common's mask stays null: every row a workgroup owns is
+// real) and 1 / n is the set's own; a workgroup whose tile lies wholly beyond its set's count writes zero partial sums -- what the
+// consumers add in tile order -- and is done.  For equal counts these are the training forward's sums in the training forward's
+// order (there the rows beyond the count enter every sum as fmaf(0, finite, sum)).
+__device__ __forceinline__ bool tile_is_empty(const Span &W, float *pool_part)
+{
+    if (W.n_begin < W.n_end) return false;
+    if (threadIdx.x < HS) pool_part[(long long)W.wg * HS + threadIdx.x] = 0.0f;
+    return true;
+}
+// the first pooling MLP, on the raw trials (no context): writes O.pool_part
+__global__ __launch_bounds__(NT) void summary_first_kernel(Common C, FwdOut O, SetCounts K)
+{
+    const int b = blockIdx.x / C.S;
+    const Span W(C, K.of(b));
+    if (tile_is_empty(W, O.pool_part)) return;
+    mlp_fwd_steps<false, false>(C, O, W, K.inv(b), nullptr);
+}
+// an equivariant MLP and the pooling MLP on its output: writes O2.pool_part, and O.y where the next block wants it
+template <bool BIG>
+__global__ __launch_bounds__(NT) void summary_pair_kernel(Common C, FwdOut O, Mlp P2, FwdOut O2, SetCounts K)
+{
+    const int b = blockIdx.x / C.S;
+    const Span W(C, K.of(b));
+    if (tile_is_empty(W, O2.pool_part)) return;
+    mlp2_fwd_steps<BIG, false>(C, O, P2, O2, W, K.inv(b));
+}
+// the MLP after the pooling, launched over the B pooled rows as ONE "set": row r is the mean of set r, by set r's own count
+__global__ __launch_bounds__(NT) void summary_post_kernel(Common C, FwdOut O, SetCounts K)
+{
+    mlp_fwd_steps<true, false>(C, O, Span(C), 0.0f, &K);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -695,7 +768,7 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(Common C, BwdIO Q)
         store64(w2s, r2, t);
         if (BIG && Q.gx) store64(w1s, r1, t);
     }
-    context_publish(C, pooled, t, Lc);               // (pooled: also for the context columns' weight gradient)
+    context_publish(C, pooled, t, Lc, inv_n);        // (pooled: also for the context columns' weight gradient)
     if (gpw && t < HS) dsum[t] = Lg.sum;
     __syncthreads();
     context_product(C, pooled, cs, t, Lc);
@@ -798,7 +871,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         GpLoad Lg;
         context_issue(C, b, t, Lc);
         if (Q.gp_W) gp_issue(Q.gpool, Q.gp_S, Q.gp_W, Q.gp_ldw, b, t, Lg);
-        context_publish(C, pooled, t, Lc);
+        context_publish(C, pooled, t, Lc, inv_n);
         if (Q.gp_W && t < HS) dsum[t] = Lg.sum;
         __syncthreads();
         context_product(C, pooled, cs, t, Lc);
@@ -1037,6 +1110,64 @@ int nddm_deepset_reduce(const float *part, int G, int P, int P_main, int G_tail,
     if (G <= 0 || P <= 0 || P_main < 0 || P_main > P || G_tail < 0 || G_tail > G) return 1;
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((P + 63) / 64), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), part, G, P, P_main,
                        G_tail, out);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+/* ---- inference: the whole summary network, a trial count per set.
+ * Bytes of the work buffer of nddm_deepset_summary: the per-tile pooled partial sums [blocks + 1, B, S, 64] of the pooling MLPs
+ * (S = ceil(N / 64)) and, with two blocks or more, the rows [B * N, 64] one equivariant MLP hands to the next (two such buffers,
+ * written in turn, from three blocks on).  -1: bad arguments. */
+static int summary_y_buffers(int blocks) { return blocks < 2 ? 0 : (blocks == 2 ? 1 : 2); }
+long long nddm_deepset_summary_work_bytes(int B, int N, int blocks)
+{
+    if (B <= 0 || N <= 0 || blocks < 0) return -1;
+    const long long S = (N + TM - 1) / TM;
+    return 4LL * HS * ((blocks + 1LL) * B * S + summary_y_buffers(blocks) * (long long)B * N);
+}
+
+/* x [B, N, d_in] (1 <= d_in <= 4) -> out [B, summary_dim + n_direct]: the summary of the first counts[b] trials of every set b
+ * (counts: int32 [B] on the device, clamped to [0, N] for addressing; a set of count 0 gets a non-finite row; NULL: N of every set),
+ * then the direct conditions' columns direct[b * direct_stride + .] (NULL: none).  params: 6 (2 blocks + 2) device pointers, host
+ * array, in InvariantNetwork.fused_params() order -- W1, b1, W2, b2, W3, b3 of every block's invariant then equivariant MLP, of the
+ * pre-pooling and of the post-pooling MLP (hidden width 64; W3 / b3 of the last: summary_dim rows).  work: 16-byte aligned, at least
+ * nddm_deepset_summary_work_bytes(B, N, blocks).  blocks + 2 launches on `stream`; no synchronisation, no atomics, no allocation;
+ * rows at or beyond a set's count are never read, and nothing but out and work is written.  0, 1: bad arguments, 2: a launch failed. */
+int nddm_deepset_summary(const float *x, int d_in, int B, int N, const int *counts, int blocks, const float *const *params, int summary_dim,
+                         const float *direct, int n_direct, int direct_stride, float *out, void *work, long long work_bytes, void *stream)
+{
+    const long long need = nddm_deepset_summary_work_bytes(B, N, blocks);
+    if (!direct) n_direct = 0;
+    if (need < 0 || !x || d_in < 1 || d_in > DS_MAX || !params || summary_dim < 1 || n_direct < 0 || summary_dim + n_direct > HS || !out || !work
+        || (reinterpret_cast<uintptr_t>(work) & 15) || work_bytes < need || (long long)B * ((N + TM - 1) / TM) > 0x7fffffffLL)
+        return 1;
+    for (int k = 0; k < 6 * (2 * blocks + 2); ++k) if (!params[k]) return 1;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int S = (N + TM - 1) / TM, Sp = (B + TM - 1) / TM;
+    const long long pool_sz = (long long)B * S * HS, y_sz = (long long)B * N * HS;
+    float *pools = static_cast<float *>(work), *ys = pools + (blocks + 1) * pool_sz;
+    auto mlp = [&](int k, int ldw1) { const float *const *p = params + 6 * k; return Mlp{p[0], ldw1, p[1], p[2], p[3], p[4], p[5]}; };
+    const SetCounts K = {counts, N};
+    // the first pooling MLP (block 0's invariant half, or without blocks the pre-pooling MLP) on the raw trials
+    const Common C0 = {x, d_in, B, N, S, TM, nullptr, 0, nullptr, 0.0f, nullptr, 0, mlp(0, d_in), HS, nullptr, 0};
+    const FwdOut O0 = {nullptr, nullptr, nullptr, pools, HS, nullptr, 0, 0};
+    hipLaunchKernelGGL(summary_first_kernel, dim3(B * S), dim3(NT), 0, st, C0, O0, K);
+    // every block's equivariant MLP with the pooling MLP that consumes its rows (the next block's invariant half, or the pre-pooling MLP)
+    const float *cur = x;
+    int d = d_in;
+    for (int i = 0; i < blocks; ++i) {
+        float *y = i + 1 < blocks ? ys + (i & 1) * y_sz : nullptr;
+        const Common C = {cur, d, B, N, S, TM, nullptr, 0, nullptr, 0.0f, pools + i * pool_sz, S, mlp(2 * i + 1, d + HS), HS, nullptr, 0};
+        const FwdOut O = {nullptr, nullptr, y, nullptr, HS, nullptr, 0, 0}, O2 = {nullptr, nullptr, nullptr, pools + (i + 1) * pool_sz, HS, nullptr, 0, 0};
+        const Mlp P2 = mlp(2 * i + 2, HS);
+        if (d == HS) hipLaunchKernelGGL(summary_pair_kernel<true>, dim3(B * S), dim3(NT), 0, st, C, O, P2, O2, K);
+        else hipLaunchKernelGGL(summary_pair_kernel<false>, dim3(B * S), dim3(NT), 0, st, C, O, P2, O2, K);
+        cur = y;
+        d = HS;
+    }
+    // the MLP after the pooling: B rows, each the mean of its set's partial sums by its set's own count
+    const Common Cp = {nullptr, HS, 1, B, Sp, TM, nullptr, 0, nullptr, 0.0f, nullptr, 0, mlp(2 * blocks + 1, HS), summary_dim, pools + blocks * pool_sz, S};
+    const FwdOut Op = {nullptr, nullptr, out, nullptr, summary_dim + n_direct, direct, n_direct, direct_stride};
+    hipLaunchKernelGGL(summary_post_kernel, dim3(Sp), dim3(NT), 0, st, Cp, Op, K);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
