@@ -739,6 +739,114 @@ def draw_quantiles(theta, probs, box=None):
     return {"quantiles": ad + (bd - ad) * g, "order": torch.stack([a, b], dim=2), "n_inside": n_in}
 
 
+WEIGHT_ONE = 2 ** 36        # the integer weight of a set's largest finite log weight (quantize_weights)
+
+
+@torch.no_grad()
+def quantize_weights(log_w):
+    """Log weights [B, S] (or [S]) -> integer weights, int64 of the same shape, per set (the last dimension): with m the largest FINITE
+    log_w of the set, W = rint(exp(log_w - m) * 2^36) in float64 (torch.round: half to even), and 0 where log_w is not finite (NaN, +-inf).  So 0 <= W <= 2^36, the
+    largest is exactly 2^36, and a draw below 2^-37 of the largest weighs nothing.  Sums of up to 32 768 such weights are exact in int64
+    and in float64, whatever the order: what weighted_draw_quantiles' definition stands on."""
+    lw = log_w.to(torch.float64)
+    fin = torch.isfinite(lw)
+    ninf = torch.full((), float("-inf"), dtype=torch.float64, device=lw.device)
+    m = torch.where(fin, lw, ninf).max(dim=-1, keepdim=True).values
+    u = torch.round(torch.exp(lw - m) * float(WEIGHT_ONE))
+    return torch.where(fin, u, torch.zeros((), dtype=torch.float64, device=lw.device)).to(torch.int64)
+
+
+def _wquantile_lib(theta, n_probs, w):
+    """libnddm_train.so if its weighted selection kernel (csrc/train_wquantile.hip) covers theta [B, S, D], this many probabilities and
+    w [B, S] (float64 log weights or int64 weights), else None (weighted_draw_quantiles' PyTorch evaluation of the same definition)."""
+    if not (theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous() and 1 <= theta.shape[2] <= 8 and 1 <= n_probs <= 16
+            and w.device == theta.device and w.is_contiguous() and w.dtype in (torch.float64, torch.int64)):
+        return None
+    from . import _train_lib
+    L = _train_lib.lib()
+    return L if L is not None and theta.shape[1] <= L.nddm_train_weighted_quantiles_max_draws() else None
+
+
+@torch.no_grad()
+def weighted_draw_quantiles(theta, probs, log_w=None, weights=None, want_weights=False):
+    """Exact WEIGHTED quantiles of draws per (set, column): theta [B, S, D] (or [S, D]: one set), probs K probabilities in [0, 1], and
+    EXACTLY ONE of log_w [B, S] (log weights: importance_weights' "log_w") and weights [B, S] int64 in [0, 2^36] (quantize_weights'
+    output; the range is the caller's to keep) -> {"quantiles" [B, K, D] float64, "order" [B, K, 2, D] float32, "n_positive" [B] int64;
+    "weights" [B, S] int64 with want_weights}, tensors on theta's device.
+
+    The definition is on the integer weights W = quantize_weights(log_w), so that every sum is exact and every route agrees bit for
+    bit.  A row is INSIDE if W >= 1 and all its D components are finite (no box: the prior term of an importance weight has already
+    zeroed what a box would remove); n_positive counts them.  Per column the inside rows sorted by value (-0 taken as +0), ties by row
+    index: x_0 <= ... <= x_(n-1) with weights W_0 .. W_(n-1), S_k = W_0 + ... + W_k, c_k = 2 S_k - W_k - W_0 (so c_0 = 0 and
+    c_(k+1) - c_k = W_k + W_(k+1) > 0) and T = c_(n-1).  For p, in float64 with every operation rounded on its own: h = p T; k the
+    largest index with c_k <= h; if k = n - 1: a = b = x_(n-1), g = 0; else a = x_k, b = x_(k+1), g = (h - c_k) / (W_k + W_(k+1));
+    order = (a, b) and quantile = a + (b - a) g.  Equal weights give draw_quantiles' rule (np.quantile's default) bit for bit; p = 0
+    gives the smallest inside value and p = 1 the largest; the quantile is non-decreasing in p.  No inside row: nan, n_positive 0.
+
+    On the device (float32 contiguous theta, D <= 8, K <= 16, S <= the kernel's cap, 16 384) one kernel sorts each (set, column)'s
+    (key, row) items in LDS and scans the integer weights in sorted order (csrc/train_wquantile.hip); everywhere else -- a CPU, more
+    draws, no library -- a stable torch.sort, an int64 cumsum and searchsorted evaluate the same definition.  Given `weights` the two
+    agree bit for bit; given log_w they can differ only through exp, by at most 1 in a W."""
+    p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+    if p.size == 0 or not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("probs must be probabilities in [0, 1]")
+    if (log_w is None) == (weights is None):
+        raise ValueError("give exactly one of log_w and weights")
+    if theta.dim() == 2:
+        theta = theta[None]
+        log_w, weights = (None if v is None else v.reshape(1, -1) for v in (log_w, weights))
+    if theta.dim() != 3 or theta.numel() == 0:
+        raise ValueError(f"theta must be [B, S, D] (or [S, D]) and not empty; got {tuple(theta.shape)}")
+    (B, S, D), K, dev = theta.shape, p.size, theta.device
+    w = log_w if weights is None else weights
+    if tuple(w.shape) != (B, S) or w.device != dev:
+        raise ValueError(f"log_w / weights must be [{B}, {S}] on theta's device; got {tuple(w.shape)} on {w.device}")
+    if weights is not None and weights.dtype != torch.int64:
+        raise ValueError(f"weights must be int64 (quantize_weights' output); got {weights.dtype}")
+    w = w.contiguous() if weights is not None else w.to(torch.float64).contiguous()
+    L = _wquantile_lib(theta, K, w)
+    if L is not None:
+        quant = torch.empty(B, K, D, dtype=torch.float64, device=dev)
+        order = torch.empty(B, K, 2, D, dtype=torch.float32, device=dev)
+        n_pos = torch.empty(B, dtype=torch.int64, device=dev)
+        w_out = torch.empty(B, S, dtype=torch.int64, device=dev) if want_weights and weights is None else None
+        rc = L.nddm_train_weighted_quantiles(B, S, D, theta.data_ptr(), w.data_ptr() if weights is None else None,
+                                             None if weights is None else w.data_ptr(), p.ctypes.data, K, quant.data_ptr(), order.data_ptr(),
+                                             n_pos.data_ptr(), None if w_out is None else w_out.data_ptr(),
+                                             torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"nddm_train_weighted_quantiles failed ({rc})")
+        res = {"quantiles": quant, "order": order, "n_positive": n_pos}
+        if want_weights:
+            res["weights"] = w if w_out is None else w_out
+        return res
+    W = w if weights is not None else quantize_weights(w)
+    th = theta.to(torch.float32)
+    inside = torch.isfinite(th).all(dim=-1) & (W >= 1)
+    n = inside.sum(dim=1)
+    # (+ 0.0: -0 becomes +0, as in the kernel's keys; rows not inside sort to the end with weight 0; stable: ties by row index)
+    srt, idx = torch.sort(torch.where(inside[..., None], th + 0.0, torch.full((), float("inf"), device=dev)), dim=1, stable=True)
+    Ws = torch.gather(torch.where(inside, W, torch.zeros((), dtype=torch.int64, device=dev))[..., None].expand(B, S, D), 1, idx)
+    c = 2 * torch.cumsum(Ws, dim=1) - Ws - Ws[:, :1]                                     # [B, S, D]: increasing up to n - 1, larger after
+    last = (n.clamp(min=1) - 1)[:, None, None].expand(B, 1, D)
+    h = torch.as_tensor(p, device=dev)[None, :, None] * torch.gather(c, 1, last).double()   # [B, K, D]
+    cd = c.double().transpose(1, 2).contiguous()                                        # [B, D, S] (exact: every c <= 2^52)
+    k = (torch.searchsorted(cd, h.transpose(1, 2).contiguous(), right=True) - 1).transpose(1, 2)      # [B, K, D]: the largest k with c_k <= h
+    k = torch.minimum(k.clamp(min=0), last)
+    k1 = torch.minimum(k + 1, last)
+    a, b = torch.gather(srt, 1, k), torch.gather(srt, 1, k1)
+    step = (torch.gather(Ws, 1, k) + torch.gather(Ws, 1, k1)).double()
+    g = torch.where(k == last, torch.zeros((), dtype=torch.float64, device=dev), (h - torch.gather(c, 1, k).double()) / step)
+    empty = (n == 0)[:, None, None]
+    nan32 = torch.full((), float("nan"), device=dev)
+    a, b = torch.where(empty, nan32, a), torch.where(empty, nan32, b)
+    ad, bd = a.double(), b.double()
+    res = {"quantiles": ad + (bd - ad) * g, "order": torch.stack([a, b], dim=2), "n_positive": n}
+    if want_weights:
+        res["weights"] = W
+    return res
+
+
 def _importance_lib(theta, log_q, log_lik):
     """libnddm_train.so if its weight-and-reduce kernel (csrc/train_importance.hip) covers these tensors, else None
     (importance_weights' torch evaluation of the same definition)."""
@@ -1072,7 +1180,7 @@ class AmortizedPosterior(nn.Module):
         return out
 
     @torch.no_grad()
-    def posterior_importance(self, input_dict, n_samples, model="basic", z_bytes=64 << 20, keep_draws=False, keep_weights=False):
+    def posterior_importance(self, input_dict, n_samples, model="basic", z_bytes=64 << 20, keep_draws=False, keep_weights=False, probs=None):
         """The amortizer's draws importance-weighted against the EXACT posterior of every data set (importance_weights: log w =
         log p(data | theta) + log p(theta) - log q(theta | data)), without the draws leaving the device:
         {"mean", "std" [B, P]: the weighted posterior moments -- a consistent estimate of the exact posterior's, whatever the
@@ -1089,6 +1197,14 @@ class AmortizedPosterior(nn.Module):
         and csrc/train_importance.hip weighs and reduces.  Where the fused sampler does not apply the draws and log q come from
         inverse_with_log_density.  model: "basic" only; the single-trial models' likelihood is not wired here yet.
 
+        probs: None (the default: the call above, nothing more launched or allocated) or K probabilities in [0, 1] -- the WEIGHTED
+        quantiles of the exact posterior as well (weighted_draw_quantiles' definition on the call's own log weights): the result gains
+        "quantiles" [B, K, P] and "probs" [K] and, for the probabilities pyhddmjagsutils.summary names (.5, .025, .975, .005, .995),
+        "median", "95lower", "95upper", "99lower", "99upper" [B, P] -- with probs=(.005, .025, .5, .975, .995) the reference's whole
+        summary under the exact posterior.  Each launch then keeps its log weights in a scratch buffer [sets, n_samples] float64 and
+        a fourth kernel (csrc/train_wquantile.hip, up to 16 384 draws; the torch evaluation beyond) turns draws and weights into
+        quantiles on the same stream before the next launch overwrites them; every other number keeps its bits.
+
         A ragged batch (`observed_batch`: "summary_counts") needs nothing more, because its padding is ZEROS: the likelihood scores
         all max n_b rows of every set, and a row (rt 0, choice 0) is a timeout censored at t = -tau <= 0, log 1 = 0 exactly, so each
         set's log-likelihood is its own trials' (tests/test_gpu_ragged_summary.py).  Padding of any other value would be scored."""
@@ -1096,6 +1212,10 @@ class AmortizedPosterior(nn.Module):
             raise NotImplementedError(f"posterior_importance scores model='basic' only; for {model!r} the next step is the marginal "
                                       "likelihood, likelihood.single_trial_logpdf, as the target")
         from . import engine, priors
+        if probs is not None:
+            probs = np.asarray(probs, dtype=np.float64).reshape(-1)
+            if probs.size == 0 or not np.all((probs >= 0.0) & (probs <= 1.0)):
+                raise ValueError("probs must be probabilities in [0, 1]")
         table = priors.prior_table(model)
         cond = self._conditions(input_dict)
         data = self._t(input_dict["summary_conditions"])
@@ -1109,7 +1229,8 @@ class AmortizedPosterior(nn.Module):
         per = max(1, int(z_bytes) // max(1, 4 * S * P))
         scratch = torch.empty(min(per, B), S, P, dtype=torch.float32, device=dev)
         scratch_q = torch.empty(min(per, B), S, dtype=torch.float32, device=dev)
-        kept, kept_q, kept_w = [], [], []
+        scratch_w = None if probs is None else torch.empty(min(per, B), S, dtype=torch.float64, device=dev)
+        kept, kept_q, kept_w, quants = [], [], [], []
         for b0 in range(0, B, per):
             c = cond[b0:b0 + per]
             nb = c.shape[0]
@@ -1123,14 +1244,26 @@ class AmortizedPosterior(nn.Module):
                 th, lq = th.reshape(nb, S, P).contiguous(), lq.reshape(nb, S).contiguous()
             ll = engine.wiener_log_likelihood(engine.BASIC_DDM_DC, th.view(nb * S, P), data[b0:b0 + nb], draws_per_dataset=S,
                                               device=dev)["loglik"].view(nb, S)
-            w = importance_weights(th, lq, ll, table, want_log_w=keep_weights, out={k: v[b0:b0 + nb] for k, v in res.items()})
+            out_w = {k: v[b0:b0 + nb] for k, v in res.items()}
+            if probs is not None:
+                out_w["log_w"] = scratch_w[:nb]
+            w = importance_weights(th, lq, ll, table, want_log_w=keep_weights or probs is not None, out=out_w)
+            if probs is not None:
+                quants.append(weighted_draw_quantiles(th, probs, log_w=w["log_w"])["quantiles"])
             if keep_draws:
                 kept.append(th.clone())
                 kept_q.append(lq.clone())
             if keep_weights:
-                kept_w.append(w["log_w"])
+                kept_w.append(w["log_w"] if probs is None else w["log_w"].clone())
         out = {("std" if k == "sd" else k): v.cpu().numpy() for k, v in res.items()}
         out["n_samples"] = S
+        if probs is not None:
+            q = torch.cat(quants, dim=0).cpu().numpy()
+            for k, pk in enumerate(probs):
+                name = self.SUMMARY_NAMES.get(float(pk))
+                if name is not None:
+                    out[name] = q[:, k, :]
+            out.update(quantiles=q, probs=probs)
         if keep_draws:
             out["draws"], out["log_q"] = torch.cat(kept, dim=0).cpu().numpy(), torch.cat(kept_q, dim=0).cpu().numpy()
         if keep_weights:

@@ -11,8 +11,7 @@
 // (16-byte accesses).  The LDS image is padded by 8 words per 64: the passes whose lowest stride is 8, 16 or 32 would otherwise
 // put a half-wave's 32 lanes on 8, 16 or 32 words of one bank row.  No floating-point atomics: the result is a pure function of
 // the set's own rows.  theta is only read.
-#include <hip/hip_runtime.h>
-#include <math.h>
+#include "train_quantile.h"                                   // the key map, the padded image and the network, shared with train_wquantile.hip
 
 namespace nddm_train {
 
@@ -26,108 +25,6 @@ struct QuantArgs {
     long long *n_inside;
     double p[Q_MAX_PROBS];
 };
-
-__device__ __forceinline__ int q_phys(int i) { return i + ((i >> 6) << 3); }
-
-// float -> key with the floats' order (finite values): negatives inverted, the others with the sign bit set.  -0 is taken as +0
-// (the two compare equal; +0 is what comes back).  No finite value maps to 0xFFFFFFFF (that would be a NaN's bits).
-__device__ __forceinline__ unsigned q_key(float v)
-{
-    unsigned u = __float_as_uint(v);
-    if ((u << 1) == 0u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float q_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-// ascending compare-exchanges of 2^NB keys over their index bits NB-1 .. 0
-template <int NB> __device__ __forceinline__ void q_network(unsigned (&v)[8])
-{
-#pragma unroll
-    for (int s = NB - 1; s >= 0; --s)
-#pragma unroll
-        for (int e = 0; e < (1 << NB); ++e)
-            if (!(e & (1 << s))) {
-                const unsigned a = v[e], b = v[e | (1 << s)];
-                v[e] = min(a, b);
-                v[e | (1 << s)] = max(a, b);
-            }
-}
-
-// the strides 2^(lb+NB-1) .. 2^lb of phase k (lb >= 3): a group is the 2^NB keys that differ in those index bits; its direction is
-// one bit of the index above them (descending = ascending on the inverted keys)
-template <int LOGN, int T, int NB> __device__ __forceinline__ void q_pass(unsigned *keys, int lb, int k, int t)
-{
-    constexpr int G = (1 << LOGN) >> NB;
-    for (int g = t; g < G; g += T) {
-        const int base = ((g >> lb) << (lb + NB)) | (g & ((1 << lb) - 1));
-        const unsigned flip = (base & k) ? 0xFFFFFFFFu : 0u;
-        unsigned v[8];
-#pragma unroll
-        for (int e = 0; e < (1 << NB); ++e) v[e] = keys[q_phys(base + (e << lb))] ^ flip;
-        q_network<NB>(v);
-#pragma unroll
-        for (int e = 0; e < (1 << NB); ++e) keys[q_phys(base + (e << lb))] = v[e] ^ flip;
-    }
-}
-
-// the strides 4, 2, 1 of phase k >= 16 on 8 contiguous keys (a padded block of 64 keeps them contiguous and 32-byte aligned)
-template <int LOGN, int T> __device__ __forceinline__ void q_pass_low(unsigned *keys, int k, int t)
-{
-    constexpr int G = (1 << LOGN) >> 3;
-    for (int g = t; g < G; g += T) {
-        const unsigned flip = ((g << 3) & k) ? 0xFFFFFFFFu : 0u;
-        uint4 *p = reinterpret_cast<uint4 *>(keys + q_phys(g << 3));
-        const uint4 a = p[0], b = p[1];
-        unsigned v[8] = {a.x ^ flip, a.y ^ flip, a.z ^ flip, a.w ^ flip, b.x ^ flip, b.y ^ flip, b.z ^ flip, b.w ^ flip};
-        q_network<3>(v);
-        p[0] = make_uint4(v[0] ^ flip, v[1] ^ flip, v[2] ^ flip, v[3] ^ flip);
-        p[1] = make_uint4(v[4] ^ flip, v[5] ^ flip, v[6] ^ flip, v[7] ^ flip);
-    }
-}
-
-// the phases k = 2, 4, 8 whole, on 8 contiguous keys
-template <int LOGN, int T> __device__ __forceinline__ void q_pass_first(unsigned *keys, int t)
-{
-    constexpr int G = (1 << LOGN) >> 3;
-    for (int g = t; g < G; g += T) {
-        uint4 *p = reinterpret_cast<uint4 *>(keys + q_phys(g << 3));
-        const uint4 a = p[0], b = p[1];
-        unsigned v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int m = 1; m <= 3; ++m)
-#pragma unroll
-            for (int s = m - 1; s >= 0; --s)
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (!(e & (1 << s))) {
-                        const bool desc = (((g << 3) | e) & (1 << m)) != 0;
-                        const unsigned x = v[e], y = v[e | (1 << s)];
-                        v[e] = desc ? max(x, y) : min(x, y);
-                        v[e | (1 << s)] = desc ? min(x, y) : max(x, y);
-                    }
-        p[0] = make_uint4(v[0], v[1], v[2], v[3]);
-        p[1] = make_uint4(v[4], v[5], v[6], v[7]);
-    }
-}
-
-// h = (n - 1) p, j = floor(h), g = h - j;  a + (b - a) g: every operation rounded on its own (no contraction into an fma)
-__device__ __forceinline__ double q_position(int n, double p, int &j)
-{
-#pragma clang fp contract(off)
-    const double h = (double)(n - 1) * p;
-    const double f = floor(h);
-    j = (int)f;
-    return h - f;
-}
-
-__device__ __forceinline__ double q_lerp(double a, double b, double g)
-{
-#pragma clang fp contract(off)
-    const double d = b - a;
-    const double m = d * g;
-    return a + m;
-}
 
 template <int LOGN, int T> __global__ __launch_bounds__(T) void draw_quantiles_kernel(QuantArgs A)
 {
@@ -157,22 +54,7 @@ template <int LOGN, int T> __global__ __launch_bounds__(T) void draw_quantiles_k
     }
     if (cnt) atomicAdd(&n_s, cnt);                            // (an integer count: the order does not matter)
     __syncthreads();
-    q_pass_first<LOGN, T>(keys, t);
-    __syncthreads();
-#pragma unroll 1
-    for (int m = 4; m <= LOGN; ++m) {
-        const int k = 1 << m;                                 // (the last phase: no index has that bit, all ascending)
-        int u = m - 3;                                        // the strides 2^(m-1) .. 8: index bits 3 .. 3 + u - 1, from the top
-        for (; u >= 3; u -= 3) {
-            q_pass<LOGN, T, 3>(keys, u, k, t);
-            __syncthreads();
-        }
-        if (u == 2) q_pass<LOGN, T, 2>(keys, 3, k, t);
-        if (u == 1) q_pass<LOGN, T, 1>(keys, 3, k, t);
-        if (u) __syncthreads();
-        q_pass_low<LOGN, T>(keys, k, t);
-        __syncthreads();
-    }
+    q_sort<unsigned, LOGN, T>(keys, t);
     const int n = n_s;
     if (t < K) {
         double q = __longlong_as_double(0x7ff8000000000000LL);
