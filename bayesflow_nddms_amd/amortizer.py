@@ -954,6 +954,151 @@ def importance_weights(theta, log_q, log_lik, prior, want_log_w=False, out=None)
     return res
 
 
+@torch.no_grad()
+def weighted_moments(theta, log_w, out=None):
+    """The moments of GIVEN log weights: theta [B, S, D] draws (or [S, D]: one set), log_w [B, S] -> importance_weights' result --
+    {"log_evidence", "ess", "max_share" [B]; "mean", "sd" [B, D]; "n_zero", "n_nan" [B]} -- with log_w in the place of log_lik + log
+    prior - log_q: the same kernel (csrc/train_importance.hip) with a zero log_q and a NEUTRAL prior table (every column uniform on
+    (-inf, inf) with log normaliser 0), so the kernel's log w is log_w + 0 - 0, the given number.  What pareto_smooth's log weights go
+    through.  A NaN or +inf log weight is counted in n_nan and weighs nothing, as there; a draw with a non-finite component counts
+    in n_zero.  out: importance_weights' (a dict of tensors to write into)."""
+    if theta.dim() == 2:
+        theta, log_w = theta[None], log_w.reshape(1, -1)
+    if theta.dim() != 3 or theta.numel() == 0 or tuple(log_w.shape) != tuple(theta.shape[:2]):
+        raise ValueError(f"theta must be [B, S, D] (or [S, D]), not empty, and log_w [B, S]; got {tuple(theta.shape)} and {tuple(log_w.shape)}")
+    D = theta.shape[2]
+    neutral = np.tile(np.array([3.0, 0.0, 0.0, -np.inf, np.inf, 0.0]), (D, 1))      # (priors.PRIOR_KINDS["uniform"] = 3)
+    log_q = torch.zeros(theta.shape[:2], dtype=torch.float32, device=theta.device)
+    return importance_weights(theta, log_q, log_w.to(torch.float64).contiguous(), neutral, out=out)
+
+
+PSIS_LOG_DBL_MIN = -708.3964185322641      # log(DBL_MIN): the floor of pareto_smooth's cutoff
+
+
+def pareto_tail_size(S):
+    """M = min(ceil(S / 5), ceil(3 sqrt(S))), in integers: how many of a set's S weights pareto_smooth fits at most."""
+    S = int(S)
+    return min((S + 4) // 5, math.isqrt(9 * S - 1) + 1)
+
+
+def pareto_k_threshold(S):
+    """min(1 - 1 / log10(S), 0.7): the pareto_k below which an importance-sampling estimate from S draws is reliable."""
+    S = int(S)
+    return min(1.0 - 1.0 / math.log10(S), 0.7) if S > 1 else float("-inf")
+
+
+def _psis_lib(log_w):
+    """libnddm_train.so if its smoothing kernel (csrc/train_psis.hip) covers log_w [B, S], else None (pareto_smooth's torch evaluation)."""
+    if not (log_w.is_cuda and log_w.dtype == torch.float64 and log_w.is_contiguous()):
+        return None
+    from . import _train_lib
+    L = _train_lib.lib()
+    return L if L is not None and log_w.shape[1] <= L.nddm_train_pareto_smooth_max_draws() else None
+
+
+def _pareto_smooth_torch(lw, M, want_log_w):
+    """pareto_smooth's definition on lw [B, S] float64 on any device, every set at once and without a host synchronisation ->
+    (pareto_k, sigma, cutoff [B] float64, n_tail [B] int64, the smoothed log weights [B, S] or None).  A stable sort gives the cutoff and
+    the tail in (value, row) order as its last M columns; a set's n <= M tail rows are the last n of those, the others are masked."""
+    (B, S), dev = lw.shape, lw.device
+    c = lambda v: torch.full((), v, dtype=torch.float64, device=dev)                      # noqa: E731
+    fin = torch.isfinite(lw)
+    m = torch.where(fin, lw, c(-math.inf)).max(dim=1, keepdim=True).values                # (-inf: no finite log weight, every x -inf)
+    xs, idx = torch.sort(torch.where(fin, lw - m, c(-math.inf)), dim=1, stable=True)      # ascending by value, ties by row index
+    cutoff = (xs[:, S - M - 1] if S - M - 1 >= 0 else c(-math.inf).expand(B)).clamp_min(PSIS_LOG_DBL_MIN)
+    tx, rows = xs[:, S - M:], idx[:, S - M:]
+    inside = tx > cutoff[:, None]
+    n = inside.sum(dim=1)
+    nd, fit = n.double(), n > 4
+    e_c = torch.exp(cutoff)[:, None]
+    y = torch.where(inside, torch.exp(tx) - e_c, c(0.0))
+    first = M - n                                                                         # the column of rank 0
+    m_est = 30.0 + torch.floor(torch.sqrt(nd))
+    j = torch.arange(1, 31 + math.isqrt(M), dtype=torch.float64, device=dev)[None, :]
+    live = j <= m_est[:, None]
+    yq = y.gather(1, (first + torch.floor(nd / 4.0 + 0.5).long() - 1).clamp(0, M - 1)[:, None])
+
+    def mean_log1p(b):                                                                    # b [B, J] -> mean over the tail of log1p(-b y), [B, J]
+        return torch.where(inside[:, None, :], torch.log1p(-b[:, :, None] * y[:, None, :]), c(0.0)).sum(dim=2) / nd[:, None]
+
+    bj = (1.0 - torch.sqrt(m_est[:, None] / (j - 0.5))) / (3.0 * yq) + 1.0 / y[:, M - 1:]
+    kj = mean_log1p(bj)
+    Lj = nd[:, None] * (torch.log(-bj / kj) - kj - 1.0)
+    wj = torch.where(live, 1.0 / torch.where(live[:, None, :], torch.exp(Lj[:, None, :] - Lj[:, :, None]), c(0.0)).sum(dim=2), c(0.0))
+    b = torch.where(live, bj * (wj / wj.sum(dim=1, keepdim=True)), c(0.0)).sum(dim=1)
+    k_raw = mean_log1p(b[:, None])[:, 0]
+    sigma = torch.where(fit, -k_raw / b, c(math.nan))
+    k = torch.where(fit, (nd * k_raw + 5.0) / (nd + 10.0), c(math.inf))
+    if not want_log_w:
+        return k, sigma, cutoff, n, None
+    apply = fit & torch.isfinite(k) & torch.isfinite(sigma) & (sigma > 0.0)
+    lp = torch.log1p(-((torch.arange(M, device=dev)[None, :] - first[:, None]).double() + 0.5) / nd[:, None])
+    q = torch.where((k == 0.0)[:, None], -sigma[:, None] * lp, sigma[:, None] * torch.expm1(-k[:, None] * lp) / k[:, None])
+    new = torch.where(apply[:, None] & inside, m + torch.log(q + e_c).clamp_max(0.0), lw.gather(1, rows))
+    return k, sigma, cutoff, n, lw.clone().scatter_(1, rows, new)                          # (every other row: its input bits)
+
+
+@torch.no_grad()
+def pareto_smooth(log_w, want_log_w=True, out=None):
+    """Pareto-smoothed importance sampling (Vehtari, Simpson, Gelman, Yao, Gabry) of log weights [B, S] (or [S]: one set), per set ->
+    {"pareto_k", "sigma", "cutoff" [B] float64, "n_tail" [B] int64; "log_w" [B, S] float64 with want_log_w}, tensors on log_w's device.
+    pareto_k (k-hat) is the shape of a generalised Pareto distribution fitted to the set's largest weights, the diagnostic:
+    below pareto_k_threshold(S) (0.7 from 1000 draws on) an estimate from these weights is reliable at this sample size, above it
+    it is not -- whatever ess and max_share say, which look healthy on a sample that has not met the heavy tail yet.  "log_w" holds
+    the input with those largest weights replaced by the fitted distribution's expected order statistics (a lower-variance estimate;
+    feed it to weighted_moments and weighted_draw_quantiles).
+
+    The definition, float64, one set: a log weight that is not finite (NaN, +-inf) is a weight of zero (quantize_weights' rule); m the
+    largest finite log_w, x = log_w - m (-inf where not finite); M = pareto_tail_size(S); c the order statistic of rank S - M - 1 of x
+    (ascending, 0-based; -inf if the rank is negative); cutoff = max(c, log DBL_MIN).  The tail is the rows with x > cutoff, strictly (so
+    n_tail <= M; a value equal to the cutoff stays out), ordered by value, ties by row index.  No finite log weight or n_tail <= 4:
+    pareto_k = +inf, sigma = nan, "log_w" is the input.  Else y_r = exp(x_(r)) - exp(cutoff) and Zhang and Stephens' estimator with the
+    PSIS prior: m_est = 30 + isqrt(n) candidates b_j = (1 - sqrt(m_est / (j - 0.5))) / (3 y_q) + 1 / y_(n-1), q = floor(n / 4 + 0.5) - 1;
+    k_j = mean_r log1p(-b_j y_r); L_j = n (log(-b_j / k_j) - k_j - 1); w_j = 1 / sum_i exp(L_i - L_j), normalised; b = sum_j b_j w_j;
+    k_raw = mean_r log1p(-b y_r); sigma = -k_raw / b; pareto_k = (n k_raw + 5) / (n + 10).  If pareto_k and sigma are finite and sigma
+    > 0 the tail row of rank r becomes m + min(log(q_r + exp(cutoff)), 0), q_r = sigma expm1(-pareto_k log1p(-p_r)) / pareto_k at p_r =
+    (r + 0.5) / n; otherwise "log_w" is the input and pareto_k is reported as computed.  Every other row keeps its input bits.
+
+    On the device (float64 contiguous log_w, S <= the kernel's cap, 16 384) one kernel, a workgroup per set (csrc/train_psis.hip: an
+    exact selection of the cutoff, the tail ranked in LDS, the fit's sums in a fixed tree -- bit-reproducible, a set's numbers
+    independent of B, unchanged by a permutation of distinct rows); everywhere else -- a CPU, more draws, no library -- a torch float64
+    evaluation of the same definition, every set at once.  n_tail, cutoff and which rows change agree exactly; pareto_k, sigma and the
+    smoothed values to the summation order and a few ulp of exp / log1p / expm1 (tests/psis_ref.py::tolerances).
+    out: a contiguous float64 tensor [B, S] on log_w's device, not log_w itself, to write "log_w" into (posterior_importance's scratch)."""
+    if log_w.dim() == 1:
+        log_w = log_w[None]
+    if log_w.dim() != 2 or log_w.numel() == 0:
+        raise ValueError(f"log_w must be [B, S] (or [S]) and not empty; got {tuple(log_w.shape)}")
+    (B, S), dev = log_w.shape, log_w.device
+    lw = log_w.to(torch.float64).contiguous()
+    M = pareto_tail_size(S)
+    if not want_log_w:
+        out = None
+    elif out is not None and (tuple(out.shape) != (B, S) or out.dtype != torch.float64 or out.device != dev or not out.is_contiguous()
+                              or out.data_ptr() == lw.data_ptr()):
+        raise ValueError(f"out must be a contiguous float64 tensor [{B}, {S}] on log_w's device and not log_w itself")
+    L = _psis_lib(lw)
+    if L is not None:
+        res = {k: torch.empty(B, dtype=torch.float64, device=dev) for k in ("pareto_k", "sigma", "cutoff")}
+        res["n_tail"] = torch.empty(B, dtype=torch.int64, device=dev)
+        if want_log_w and out is None:
+            out = torch.empty(B, S, dtype=torch.float64, device=dev)
+        rc = L.nddm_train_pareto_smooth(B, S, M, lw.data_ptr(), None if out is None else out.data_ptr(), res["pareto_k"].data_ptr(),
+                                        res["sigma"].data_ptr(), res["n_tail"].data_ptr(), res["cutoff"].data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"nddm_train_pareto_smooth failed ({rc})")
+        if want_log_w:
+            res["log_w"] = out
+        return res
+    per = max(1, (8 << 20) // ((31 + math.isqrt(M)) * M))                # sets per pass: the fit's [sets, candidates, M] terms within 64 MB
+    parts = [_pareto_smooth_torch(lw[b0:b0 + per], M, want_log_w) for b0 in range(0, B, per)]
+    res = {key: torch.cat([p[i] for p in parts]) for i, key in enumerate(("pareto_k", "sigma", "cutoff", "n_tail"))}
+    if want_log_w:
+        res["log_w"] = torch.cat([p[4] for p in parts]) if out is None else out.copy_(torch.cat([p[4] for p in parts]))
+    return res
+
+
 def observed_batch(datasets, device=None):
     """Observed data sets of DIFFERENT trial counts -- a sequence of arrays [n_b, d], a participant each -- as ONE amortizer input:
     {"summary_conditions": float32 [B, max n_b, d], set b's trials first and ZEROS after them; "summary_counts": int32 [B], the n_b;
@@ -1180,7 +1325,8 @@ class AmortizedPosterior(nn.Module):
         return out
 
     @torch.no_grad()
-    def posterior_importance(self, input_dict, n_samples, model="basic", z_bytes=64 << 20, keep_draws=False, keep_weights=False, probs=None):
+    def posterior_importance(self, input_dict, n_samples, model="basic", z_bytes=64 << 20, keep_draws=False, keep_weights=False, probs=None,
+                             smooth=False):
         """The amortizer's draws importance-weighted against the EXACT posterior of every data set (importance_weights: log w =
         log p(data | theta) + log p(theta) - log q(theta | data)), without the draws leaving the device:
         {"mean", "std" [B, P]: the weighted posterior moments -- a consistent estimate of the exact posterior's, whatever the
@@ -1207,7 +1353,16 @@ class AmortizedPosterior(nn.Module):
 
         A ragged batch (`observed_batch`: "summary_counts") needs nothing more, because its padding is ZEROS: the likelihood scores
         all max n_b rows of every set, and a row (rt 0, choice 0) is a timeout censored at t = -tau <= 0, log 1 = 0 exactly, so each
-        set's log-likelihood is its own trials' (tests/test_gpu_ragged_summary.py).  Padding of any other value would be scored."""
+        set's log-likelihood is its own trials' (tests/test_gpu_ragged_summary.py).  Padding of any other value would be scored.
+
+        smooth: False (the default: the call above, its bits and its launches) or True -- Pareto-smoothed importance sampling.  Each
+        launch's log weights then go through pareto_smooth into a second scratch buffer [sets, n_samples] float64 (csrc/train_psis.hip, up
+        to 16 384 draws; the torch evaluation beyond), weighted_moments launches csrc/train_importance.hip a second time on the smoothed
+        weights, and with probs the weighted quantiles are taken on them.  "mean", "std", "ess", "max_share", "log_evidence" and the
+        quantiles are then those of the SMOOTHED weights, and the result gains "pareto_k" [B] float64 -- the diagnostic: at or above
+        "k_threshold" (pareto_k_threshold(n_samples), a float) a set's numbers are not to be trusted at this sample size, whatever
+        its ess says -- "n_tail" [B] int64, and "raw": a dict of the unsmoothed "mean", "std", "ess", "max_share" and "log_evidence", the
+        smooth=False call's bits under the same seed.  keep_weights=True also returns "log_w_smoothed" [B, n_samples] float64."""
         if model != "basic":
             raise NotImplementedError(f"posterior_importance scores model='basic' only; for {model!r} the next step is the marginal "
                                       "likelihood, likelihood.single_trial_logpdf, as the target")
@@ -1229,8 +1384,12 @@ class AmortizedPosterior(nn.Module):
         per = max(1, int(z_bytes) // max(1, 4 * S * P))
         scratch = torch.empty(min(per, B), S, P, dtype=torch.float32, device=dev)
         scratch_q = torch.empty(min(per, B), S, dtype=torch.float32, device=dev)
-        scratch_w = None if probs is None else torch.empty(min(per, B), S, dtype=torch.float64, device=dev)
+        scratch_w = None if probs is None and not smooth else torch.empty(min(per, B), S, dtype=torch.float64, device=dev)
         kept, kept_q, kept_w, quants = [], [], [], []
+        if smooth:
+            scratch_s, kept_s = torch.empty(min(per, B), S, dtype=torch.float64, device=dev), []
+            res_s = {k: torch.empty_like(v) for k, v in res.items()}
+            res_k = {"pareto_k": torch.empty(B, dtype=torch.float64, device=dev), "n_tail": torch.empty(B, dtype=torch.int64, device=dev)}
         for b0 in range(0, B, per):
             c = cond[b0:b0 + per]
             nb = c.shape[0]
@@ -1245,18 +1404,33 @@ class AmortizedPosterior(nn.Module):
             ll = engine.wiener_log_likelihood(engine.BASIC_DDM_DC, th.view(nb * S, P), data[b0:b0 + nb], draws_per_dataset=S,
                                               device=dev)["loglik"].view(nb, S)
             out_w = {k: v[b0:b0 + nb] for k, v in res.items()}
-            if probs is not None:
+            if scratch_w is not None:
                 out_w["log_w"] = scratch_w[:nb]
-            w = importance_weights(th, lq, ll, table, want_log_w=keep_weights or probs is not None, out=out_w)
+            w = importance_weights(th, lq, ll, table, want_log_w=keep_weights or scratch_w is not None, out=out_w)
+            log_w = w["log_w"] if keep_weights or scratch_w is not None else None
+            if smooth:
+                sm = pareto_smooth(log_w, out=scratch_s[:nb])
+                for k, v in res_k.items():
+                    v[b0:b0 + nb] = sm[k]
+                log_w = sm["log_w"]
+                weighted_moments(th, log_w, out={k: v[b0:b0 + nb] for k, v in res_s.items()})
+                if keep_weights:
+                    kept_s.append(log_w.clone())
             if probs is not None:
-                quants.append(weighted_draw_quantiles(th, probs, log_w=w["log_w"])["quantiles"])
+                quants.append(weighted_draw_quantiles(th, probs, log_w=log_w)["quantiles"])
             if keep_draws:
                 kept.append(th.clone())
                 kept_q.append(lq.clone())
             if keep_weights:
-                kept_w.append(w["log_w"] if probs is None else w["log_w"].clone())
+                kept_w.append(w["log_w"] if scratch_w is None else w["log_w"].clone())
         out = {("std" if k == "sd" else k): v.cpu().numpy() for k, v in res.items()}
         out["n_samples"] = S
+        if smooth:
+            out["raw"] = {k: out[k] for k in ("mean", "std", "ess", "max_share", "log_evidence")}
+            out.update({("std" if k == "sd" else k): res_s[k].cpu().numpy() for k in ("mean", "sd", "ess", "max_share", "log_evidence")})
+            out.update({k: v.cpu().numpy() for k, v in res_k.items()}, k_threshold=pareto_k_threshold(S))
+            if keep_weights:
+                out["log_w_smoothed"] = torch.cat(kept_s, dim=0).cpu().numpy()
         if probs is not None:
             q = torch.cat(quants, dim=0).cpu().numpy()
             for k, pk in enumerate(probs):
