@@ -1,5 +1,5 @@
 """ctypes binding of libnddm_train.so: the amortizer's flow as one kernel each way (csrc/train_kernels.hip), its inverse -- the
-posterior sampler -- as one kernel (csrc/train_sample.hip), the draws' order statistics (csrc/train_quantile.hip) importance weights (csrc/train_importance.hip) weighted quantiles (csrc/train_wquantile.hip) and the weights' Pareto smoothing (csrc/train_psis.hip), and the summary
+posterior sampler -- as one kernel (csrc/train_sample.hip), the draws' order statistics (csrc/train_quantile.hip) importance weights (csrc/train_importance.hip) weighted quantiles (csrc/train_wquantile.hip) the weights' Pareto smoothing (csrc/train_psis.hip) and the resampling of weighted draws (csrc/train_resample.hip), and the summary
 network's per-trial MLPs and its inference forward with a trial count per set (csrc/train_deepset.hip), and the optimizer step on flat buffers (csrc/train_update.hip).
 Optional: `lib()` returns None when the library cannot be built or loaded, and the amortizer then runs its PyTorch path."""
 import ctypes
@@ -58,6 +58,13 @@ def lib():
     #                                    B    S    M   log_w out_log_w pareto_k sigma n_tail cutoff stream
     L.nddm_train_pareto_smooth.argtypes = [i32, i32, i32, fp, fp, fp, fp, fp, fp, vp]
     L.nddm_train_pareto_smooth.restype = i32
+    L.nddm_train_resample_max_draws.argtypes = []                                                                              # csrc/train_resample.hip
+    L.nddm_train_resample_max_draws.restype = i32
+    L.nddm_train_resample_max_out.argtypes = []
+    L.nddm_train_resample_max_out.restype = i32
+    #                               B    S    D    M   theta log_w w_in words out ancestors n_unique n_positive w_out stream
+    L.nddm_train_resample.argtypes = [i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]
+    L.nddm_train_resample.restype = i32
     L.nddm_deepset_supported.argtypes = [i32, i32]
     L.nddm_deepset_supported.restype = i32
     common = [fp, i32, i32, i32, i32, i32, fp, i32, fp, f32, fp, i32, fp, i32, fp, fp, fp, fp, fp, i32, fp, i32]   # x .. S_x (csrc/train_deepset.hip)

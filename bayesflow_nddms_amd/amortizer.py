@@ -1099,6 +1099,122 @@ def pareto_smooth(log_w, want_log_w=True, out=None):
     return res
 
 
+RESAMPLE_MAX_OUT = 2 ** 20     # the largest M resample_draws' kernel takes: the comb's 64-bit terms stay below 2^63 up to here
+
+
+def resample_words(B, seed=0):
+    """One 64-bit word per data set for resample_draws: uint64 [B] (numpy) from np.random.Generator(np.random.Philox(seed)), so torch's
+    generator is never touched.  Set b's word is words[b] whatever the launch split; the first B' words of a longer call are the same."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("resample_words needs B >= 1")
+    return np.random.Generator(np.random.Philox(int(seed))).integers(0, 2 ** 64, size=B, dtype=np.uint64)
+
+
+def _resample_lib(theta, M, w):
+    """libnddm_train.so if its resampling kernel (csrc/train_resample.hip) covers theta [B, S, D], M outputs and w [B, S] (float64 log
+    weights or int64 weights), else None (resample_draws' PyTorch evaluation of the same definition)."""
+    if not (theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous() and 1 <= theta.shape[2] <= 8 and 1 <= M <= RESAMPLE_MAX_OUT
+            and w.device == theta.device and w.is_contiguous() and w.dtype in (torch.float64, torch.int64)):
+        return None
+    from . import _train_lib
+    L = _train_lib.lib()
+    return L if L is not None and theta.shape[1] <= L.nddm_train_resample_max_draws() and M <= L.nddm_train_resample_max_out() else None
+
+
+@torch.no_grad()
+def resample_draws(theta, M, log_w=None, weights=None, words=None, seed=0, want_weights=False):
+    """Sampling-importance-resampling: S weighted draws per data set -> M EQUALLY weighted draws of the weighted sample (of the exact
+    posterior, when the weights are importance_weights').  theta [B, S, D] (or [S, D]: one set), EXACTLY ONE of log_w [B, S] (log
+    weights) and weights [B, S] int64 in [0, 2^36] (quantize_weights' output; the range is the caller's to keep), words: one 64-bit
+    word per set (a uint64 array [B], an int64 tensor of the same bits, or None: resample_words(B, seed)) -> {"draws" [B, M, D]
+    float32, "ancestors" [B, M] int32, "n_unique", "n_positive" [B] int64; "weights" [B, S] int64 with want_weights}, tensors on
+    theta's device.
+
+    The definition is on the integer weights W = quantize_weights(log_w), so that every sum is exact and every route agrees on every
+    ancestor.  V_i = W_i if all D components of row i are finite, else 0 (weighted_draw_quantiles' inside rule; n_positive counts the
+    rows with V_i >= 1).  Running sums IN ROW ORDER, no sort: C_k = V_0 + ... + V_k, T = C_(S-1).  The offset U = (r T) >> 64, the high
+    half of the 128-bit product of the set's word r (unsigned) and T: 0 <= U < T, uniform when r is.  The systematic comb t_j =
+    floor((j T + U) / M), j = 0 .. M - 1; the ancestor a_j is the smallest k with C_k > t_j, and draws[j] = theta[a_j], the float32
+    bits copied.  n_unique is the number of distinct ancestors.  So a_j does not decrease in j, a row of weight 0 is never chosen, row
+    k appears floor or ceil of M V_k / T times (|n_k T - M V_k| < T), equal weights with M = S give a_j = j, and summed over all T
+    offsets row k is chosen exactly M V_k times: exactly unbiased given a uniform U.  A set with T = 0: NaN draws, ancestors -1,
+    n_unique 0.
+
+    On the device (float32 contiguous theta, D <= 8, S <= the kernel's cap, 16 384, M <= 2^20) one kernel, a workgroup per set, scans
+    the integer weights in LDS and searches them per output (csrc/train_resample.hip); everywhere else -- a CPU, more draws, no
+    library, a larger M -- an int64 cumsum and searchsorted evaluate the same definition, U in Python integers on the host.  Given
+    `weights` the two agree bit for bit; given log_w they can differ only through exp, by at most 1 in a W."""
+    M = int(M)
+    if M < 1:
+        raise ValueError("M must be at least 1")
+    if (log_w is None) == (weights is None):
+        raise ValueError("give exactly one of log_w and weights")
+    if theta.dim() == 2:
+        theta = theta[None]
+        log_w, weights = (None if v is None else v.reshape(1, -1) for v in (log_w, weights))
+    if theta.dim() != 3 or theta.numel() == 0:
+        raise ValueError(f"theta must be [B, S, D] (or [S, D]) and not empty; got {tuple(theta.shape)}")
+    (B, S, D), dev = theta.shape, theta.device
+    w = log_w if weights is None else weights
+    if tuple(w.shape) != (B, S) or w.device != dev:
+        raise ValueError(f"log_w / weights must be [{B}, {S}] on theta's device; got {tuple(w.shape)} on {w.device}")
+    if weights is not None and weights.dtype != torch.int64:
+        raise ValueError(f"weights must be int64 (quantize_weights' output); got {weights.dtype}")
+    w = w.contiguous() if weights is not None else w.to(torch.float64).contiguous()
+    if words is None:
+        words = resample_words(B, seed)
+    if torch.is_tensor(words):
+        if words.dtype not in (torch.int64, torch.uint64) or tuple(words.shape) != (B,):
+            raise ValueError(f"words must be {B} 64-bit words; got {words.dtype} {tuple(words.shape)}")
+        words_t = words.view(torch.int64).to(dev).contiguous()
+    else:
+        words = np.asarray(words)
+        if words.dtype != np.uint64 or words.shape != (B,):
+            raise ValueError(f"words must be a uint64 array [{B}] (resample_words); got {words.dtype} {words.shape}")
+        words_t = None
+    L = _resample_lib(theta, M, w)
+    if L is not None:
+        if words_t is None:
+            words_t = torch.from_numpy(np.ascontiguousarray(words).view(np.int64)).to(dev)
+        out = torch.empty(B, M, D, dtype=torch.float32, device=dev)
+        anc = torch.empty(B, M, dtype=torch.int32, device=dev)
+        n_uni, n_pos = torch.empty(B, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
+        w_out = torch.empty(B, S, dtype=torch.int64, device=dev) if want_weights and weights is None else None
+        rc = L.nddm_train_resample(B, S, D, M, theta.data_ptr(), w.data_ptr() if weights is None else None,
+                                   None if weights is None else w.data_ptr(), words_t.data_ptr(), out.data_ptr(), anc.data_ptr(),
+                                   n_uni.data_ptr(), n_pos.data_ptr(), None if w_out is None else w_out.data_ptr(),
+                                   torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"nddm_train_resample failed ({rc})")
+        res = {"draws": out, "ancestors": anc, "n_unique": n_uni, "n_positive": n_pos}
+        if want_weights:
+            res["weights"] = w if w_out is None else w_out
+        return res
+    W = w if weights is not None else quantize_weights(w)
+    th = theta.to(torch.float32)
+    V = torch.where(torch.isfinite(th).all(dim=-1), W, torch.zeros((), dtype=torch.int64, device=dev))
+    C = torch.cumsum(V, dim=1)                                                            # [B, S] int64: exact
+    T = C[:, -1]
+    r = [int(v) & (2 ** 64 - 1) for v in (words_t.tolist() if words_t is not None else words.tolist())]
+    U = torch.tensor([(rb * Tb) >> 64 for rb, Tb in zip(r, T.tolist())], dtype=torch.int64, device=dev)      # Python integers: exact
+    fl = lambda a, d: torch.div(a, d, rounding_mode="floor")                              # noqa: E731  (non-negative int64)
+    q, qU = fl(T, M), fl(U, M)
+    rho, rhoU = T - q * M, U - qU * M
+    j = torch.arange(M, dtype=torch.int64, device=dev)[None, :]
+    tj = j * q[:, None] + qU[:, None] + fl(j * rho[:, None] + rhoU[:, None], M)           # [B, M]
+    empty = (T == 0)[:, None]
+    a = torch.searchsorted(C, tj, right=True).clamp(max=S - 1)                            # the smallest k with C_k > t_j (T = 0: masked below)
+    out = torch.gather(th, 1, a[..., None].expand(B, M, D))
+    out = torch.where(empty[..., None], torch.full((), float("nan"), device=dev), out)
+    n_uni = torch.where(empty[:, 0], torch.zeros((), dtype=torch.int64, device=dev), 1 + (a[:, 1:] != a[:, :-1]).sum(dim=1))
+    a = torch.where(empty, torch.full((), -1, dtype=torch.int64, device=dev), a)
+    res = {"draws": out, "ancestors": a.to(torch.int32), "n_unique": n_uni, "n_positive": (V >= 1).sum(dim=1)}
+    if want_weights:
+        res["weights"] = W
+    return res
+
+
 def observed_batch(datasets, device=None):
     """Observed data sets of DIFFERENT trial counts -- a sequence of arrays [n_b, d], a participant each -- as ONE amortizer input:
     {"summary_conditions": float32 [B, max n_b, d], set b's trials first and ZEROS after them; "summary_counts": int32 [B], the n_b;
@@ -1326,7 +1442,7 @@ class AmortizedPosterior(nn.Module):
 
     @torch.no_grad()
     def posterior_importance(self, input_dict, n_samples, model="basic", z_bytes=64 << 20, keep_draws=False, keep_weights=False, probs=None,
-                             smooth=False):
+                             smooth=False, resample=None, resample_seed=0, _resampled_on_device=False):
         """The amortizer's draws importance-weighted against the EXACT posterior of every data set (importance_weights: log w =
         log p(data | theta) + log p(theta) - log q(theta | data)), without the draws leaving the device:
         {"mean", "std" [B, P]: the weighted posterior moments -- a consistent estimate of the exact posterior's, whatever the
@@ -1362,7 +1478,16 @@ class AmortizedPosterior(nn.Module):
         quantiles are then those of the SMOOTHED weights, and the result gains "pareto_k" [B] float64 -- the diagnostic: at or above
         "k_threshold" (pareto_k_threshold(n_samples), a float) a set's numbers are not to be trusted at this sample size, whatever
         its ess says -- "n_tail" [B] int64, and "raw": a dict of the unsmoothed "mean", "std", "ess", "max_share" and "log_evidence", the
-        smooth=False call's bits under the same seed.  keep_weights=True also returns "log_w_smoothed" [B, n_samples] float64."""
+        smooth=False call's bits under the same seed.  keep_weights=True also returns "log_w_smoothed" [B, n_samples] float64.
+
+        resample: None (the default: the call above, its keys, bits, launches and allocations) or M >= 1 -- sampling-importance-
+        resampling: the result gains "resampled" [B, M, P] float32, M EQUALLY weighted draws of the exact posterior per data set
+        (resample_draws' definition on the call's own log weights -- the smoothed ones with smooth=True -- and the words
+        resample_words(B, resample_seed): set b's word is words[b] whatever the launch split), "n_unique" [B] int64, how many different
+        draws they are, and "resample_seed".  Each launch's draws and log weights go through one more kernel (csrc/train_resample.hip, up
+        to 16 384 draws and M <= 2^20; the torch evaluation beyond) on the same stream before the next launch overwrites them.  Every
+        other number keeps its bits, and torch's random stream is consumed exactly as without the option.  (_resampled_on_device:
+        sample_exact's -- "resampled" stays a device tensor instead of making the way to the host.)"""
         if model != "basic":
             raise NotImplementedError(f"posterior_importance scores model='basic' only; for {model!r} the next step is the marginal "
                                       "likelihood, likelihood.single_trial_logpdf, as the target")
@@ -1371,6 +1496,8 @@ class AmortizedPosterior(nn.Module):
             probs = np.asarray(probs, dtype=np.float64).reshape(-1)
             if probs.size == 0 or not np.all((probs >= 0.0) & (probs <= 1.0)):
                 raise ValueError("probs must be probabilities in [0, 1]")
+        if resample is not None and int(resample) < 1:
+            raise ValueError("resample must be None or a number of draws M >= 1")
         table = priors.prior_table(model)
         cond = self._conditions(input_dict)
         data = self._t(input_dict["summary_conditions"])
@@ -1384,12 +1511,14 @@ class AmortizedPosterior(nn.Module):
         per = max(1, int(z_bytes) // max(1, 4 * S * P))
         scratch = torch.empty(min(per, B), S, P, dtype=torch.float32, device=dev)
         scratch_q = torch.empty(min(per, B), S, dtype=torch.float32, device=dev)
-        scratch_w = None if probs is None and not smooth else torch.empty(min(per, B), S, dtype=torch.float64, device=dev)
+        scratch_w = None if probs is None and not smooth and resample is None else torch.empty(min(per, B), S, dtype=torch.float64, device=dev)
         kept, kept_q, kept_w, quants = [], [], [], []
         if smooth:
             scratch_s, kept_s = torch.empty(min(per, B), S, dtype=torch.float64, device=dev), []
             res_s = {k: torch.empty_like(v) for k, v in res.items()}
             res_k = {"pareto_k": torch.empty(B, dtype=torch.float64, device=dev), "n_tail": torch.empty(B, dtype=torch.int64, device=dev)}
+        if resample is not None:
+            words, resampled, n_unique = resample_words(B, resample_seed), [], []
         for b0 in range(0, B, per):
             c = cond[b0:b0 + per]
             nb = c.shape[0]
@@ -1418,6 +1547,10 @@ class AmortizedPosterior(nn.Module):
                     kept_s.append(log_w.clone())
             if probs is not None:
                 quants.append(weighted_draw_quantiles(th, probs, log_w=log_w)["quantiles"])
+            if resample is not None:
+                rs = resample_draws(th, int(resample), log_w=log_w, words=words[b0:b0 + nb])
+                resampled.append(rs["draws"])
+                n_unique.append(rs["n_unique"])
             if keep_draws:
                 kept.append(th.clone())
                 kept_q.append(lq.clone())
@@ -1438,10 +1571,33 @@ class AmortizedPosterior(nn.Module):
                 if name is not None:
                     out[name] = q[:, k, :]
             out.update(quantiles=q, probs=probs)
+        if resample is not None:
+            rs = resampled[0] if len(resampled) == 1 else torch.cat(resampled, dim=0)
+            out.update(resampled=rs if _resampled_on_device else rs.cpu().numpy(), n_unique=torch.cat(n_unique, dim=0).cpu().numpy(),
+                       resample_seed=int(resample_seed))
         if keep_draws:
             out["draws"], out["log_q"] = torch.cat(kept, dim=0).cpu().numpy(), torch.cat(kept_q, dim=0).cpu().numpy()
         if keep_weights:
             out["log_w"] = torch.cat(kept_w, dim=0).cpu().numpy()
+        return out
+
+    @torch.no_grad()
+    def sample_exact(self, input_dict, n_samples, n_proposals=None, smooth=True, seed=0, to_numpy=True):
+        """Draws of the EXACT posterior of every data set: [n_samples, P] for a single data set, [B, n_samples, P] for a batch, as
+        `sample` -- n_proposals (default: n_samples) draws of the flow, importance-weighted against the exact Wiener likelihood and
+        resampled into n_samples equally weighted ones (posterior_importance(..., resample=n_samples, resample_seed=seed); smooth:
+        on the Pareto-smoothed weights).  For joint plots, correlations, posterior-predictive simulation, starting points of fit_hmc.
+        Whether to believe them is in `self.last_exact`: "ess" and "n_unique" [B] (how many of the proposals carry the weight, and how
+        many different rows came back), and with smooth "pareto_k" [B] against "k_threshold" (else None).  model="basic" only, as
+        posterior_importance; a ragged batch (`observed_batch`) needs nothing more."""
+        S = int(n_samples if n_proposals is None else n_proposals)
+        r = self.posterior_importance(input_dict, S, smooth=smooth, resample=int(n_samples), resample_seed=seed,
+                                      _resampled_on_device=not to_numpy)
+        self.last_exact = {"ess": r["ess"], "n_unique": r["n_unique"], "pareto_k": r.get("pareto_k"), "k_threshold": r.get("k_threshold"),
+                           "n_proposals": S}
+        out = r["resampled"]
+        if out.shape[0] == 1:
+            out = out[0]
         return out
 
     @torch.no_grad()

@@ -100,15 +100,17 @@ def build_hip(force=False, verbose=False):
     return SO_PATH
 
 
-# ---- the amortizer's kernels (csrc/train_kernels.hip: the flow; csrc/train_sample.hip: its inverse, the posterior sampler; csrc/train_quantile.hip: the draws' order statistics; csrc/train_importance.hip: their importance weights; csrc/train_wquantile.hip: their weighted quantiles; csrc/train_psis.hip: the weights' Pareto smoothing and k-hat; csrc/train_deepset.hip: the summary network's per-trial MLPs; csrc/train_update.hip: Adam
+# ---- the amortizer's kernels (csrc/train_kernels.hip: the flow; csrc/train_sample.hip: its inverse, the posterior sampler; csrc/train_quantile.hip: the draws' order statistics; csrc/train_importance.hip: their importance weights; csrc/train_wquantile.hip: their weighted quantiles; csrc/train_psis.hip: the weights' Pareto smoothing and k-hat; csrc/train_resample.hip: the weighted draws resampled into equally weighted ones; csrc/train_deepset.hip: the summary network's per-trial MLPs; csrc/train_update.hip: Adam
 # -> libnddm_train.so): not part of the simulator's C ABI; the PyTorch path is the fallback wherever this library is absent or the
 # shape is not covered
 TRAIN_SO_PATH = os.path.join(_HERE, "libnddm_train.so")
 TRAIN_SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("train_kernels.hip", "train_sample.hip", "train_quantile.hip", "train_deepset.hip",
-                                                          "train_update.hip", "train_importance.hip", "train_wquantile.hip", "train_psis.hip")]
+                                                          "train_update.hip", "train_importance.hip", "train_wquantile.hip", "train_psis.hip",
+                                                          "train_resample.hip")]
 # train_flow.h: what train_kernels.hip and train_sample.hip (the flow's inverse) share; train_quantile.h: what the two quantile kernels and
-# train_psis.hip share; train_psis.h: the Pareto fit's arithmetic, which also compiles for the host
-TRAIN_HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("train_flow.h", "train_quantile.h", "train_psis.h")]
+# train_psis.hip share; train_psis.h: the Pareto fit's arithmetic, which also compiles for the host; train_weight.h: the quantisation of a log
+# weight, which train_wquantile.hip and train_resample.hip share
+TRAIN_HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("train_flow.h", "train_quantile.h", "train_psis.h", "train_weight.h")]
 TRAIN_SOURCE = TRAIN_SOURCES[0]
 
 

@@ -18,6 +18,7 @@
 // and answers.  Integer adds only: any scan order gives the same bits.  No floating-point atomics, nothing grid-wide; a set's
 // numbers depend on neither B nor its neighbours.  theta, log_w and the weights passed in are only read.
 #include "train_quantile.h"
+#include "train_weight.h"
 
 namespace nddm_train {
 
@@ -34,11 +35,7 @@ struct WQuantArgs {
     double p[WQ_MAX_PROBS];
 };
 
-// the quantisation: one function, inlined wherever a weight is needed
-__device__ __forceinline__ long long wq_weight(double lw, double m)
-{
-    return isfinite(lw) ? (long long)rint(exp(lw - m) * 68719476736.0) : 0LL;
-}
+// (the quantisation, wq_weight: csrc/train_weight.h -- one function, inlined wherever a weight is needed)
 
 template <int LOGN, int T> __global__ __launch_bounds__(T) void weighted_quantiles_kernel(WQuantArgs A)
 {
