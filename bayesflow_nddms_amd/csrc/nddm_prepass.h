@@ -171,7 +171,20 @@ __global__ void debug_raw_kernel(const uint32_t *ctr, long long n, uint32_t k0, 
 
 // ------------------------------------------------------------------------------------------------
 // on-device draw_prior(): basic_ddm_dc.py:62-80 / single_trial_alpha_not_scaled.py:78-102 (+ _alt :889-913,
-// _scale :1205-1232 share the marginals).  Stream 2 of the row; one thread per row.
+// _scale :1205-1232 share the marginals).  Stream 2 of the row; one thread per row.  The definition, which the tests restate on the
+// CPU and hold this kernel to bit for bit (tests/test_gpu_prior_parity.py):
+//   Row g = set_offset + *set_offset_dev + i, taken mod 2^64.  Rows 2^60 apart share a stream.
+//   Keys: k0 = low32(seed), k1 = high32(seed).
+//   Counter of the row's n-th block, n = 0, 1, ... in order of first use.  Normals and uniforms share the count n.
+//     Normals block: (n, 0, low32(g), (high32(g) & 0x0fffffff) | 0x20000000), giving 4 normals used in order.
+//     Uniforms block: (n, 1, same, same), giving 4 words used in order.
+//     Uniform: u = fmaf((float)word, 2^-32, 2^-33).
+//   TN(mean, sd; lo, hi): take v = fmaf(sd, z, mean) for successive normals until lo <= v <= hi.  There are at most 256 tries,
+//     then a clamp.
+//   Beta(2,2): the median of three uniforms, as fmax(fmin(a,b), fmin(fmax(a,b), c)).
+//   Basic columns: 2z, TN(1,.5;0,10), Beta(2,2), TN(.5,.25;0,1.5), TN(1,.5;0,10).
+//   Single and alt columns: 2z, TN(1,.5;0,10), Beta(2,2), TN(.5,.25;0,1.5), TN(1,.5;0,3), TN(1,.5;0,10), 5u, then gamma if
+//     gamma >= 0, else 2u.
 struct PriorStream {
     uint32_t k0, k1, row_lo, c3, draw;
     float z[4];
@@ -192,7 +205,9 @@ struct PriorStream {
         const int j = 4 - nu; nu--;
         return uniform01(j == 0 ? u[0] : (j == 1 ? u[1] : (j == 2 ? u[2] : u[3])));
     }
-    // N(mean, sd) truncated to [low, upp] by rejection (truncnorm_better, basic_ddm_dc.py:55-57)
+    // N(mean, sd) truncated to [low, upp] by rejection (truncnorm_better, basic_ddm_dc.py:55-57).  The cap of 256 tries only
+    // makes the loop finite: the priors' try fails with probability below 0.023, 256 in a row below 0.023^256, so the clamp
+    // after it cannot be reached through the API (and has no test).
     __device__ float truncnorm(float mean, float sd, float low, float upp)
     {
         float v = mean;

@@ -372,7 +372,7 @@ __device__ __forceinline__ void normals4(uint32_t c0, uint32_t c1, uint32_t c2, 
     z[2] = r * cs; z[3] = r * sn;
 }
 
-// uniform in (0,1) from one u32 (prior sampler)
+// uniform in (0, 1] from one u32 (prior sampler): (float)x rounds the top 128 words to 2^32, which give exactly 1.0f
 __device__ __forceinline__ float uniform01(uint32_t x)
 {
     return __builtin_fmaf((float)x, 2.3283064365386963e-10f, 1.1641532182693481e-10f);

@@ -88,6 +88,10 @@ def lib():
         L.oracle_philox_raw.restype = None
         L.oracle_philox_normals4.argtypes = [ctypes.c_uint32] * 6 + [fp]
         L.oracle_philox_block.argtypes = [ctypes.c_uint32] * 6 + [ctypes.POINTER(ctypes.c_uint32)]
+        L.oracle_prior_rows.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_float, fp, ip, ip]
+        L.oracle_prior_rows.restype = ctypes.c_int
+        L.oracle_prior_rows_first_reject.argtypes = L.oracle_prior_rows.argtypes + [ip]
+        L.oracle_prior_rows_first_reject.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -303,3 +307,26 @@ def philox_block(c0, c1, c2, c3, k0, k1):
     x = np.empty(4, np.uint32)
     lib().oracle_philox_block(c0, c1, c2, c3, k0, k1, x.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
     return x
+
+
+# ----------------------------------------------------------------------------- the prior sampler
+def prior_rows(model, B, seed=0, set_offset=0, gamma=1.0, want_counts=False, want_first_reject=False):
+    """Section E: the on-device prior sampler (csrc/nddm_prepass.h: prior_kernel) on the CPU -- the element-wise checker of
+    engine.draw_prior_device.  f32 [B, P], P = 5 for M_BASIC and 8 for M_SINGLE / M_ALT (gamma < 0: the eighth column is drawn).
+    seed and set_offset wrap to 64 bits as in the ABI; set_offset is the whole row index of row 0 (the device word included).
+    want_counts=True: (rows, n_normals i32[B], n_uniforms i32[B]), the draws each row consumed.
+    want_first_reject=True: one more, i32[B]: the first column whose truncated normal rejected a try, -1 where none did."""
+    B = int(B)
+    P = lib().oracle_model_nparams(int(model))
+    if model not in (M_BASIC, M_SINGLE, M_ALT) or B < 0:
+        raise ValueError(f"prior_rows: model {model} has no prior here, or B = {B} < 0")
+    out = np.empty((B, P), np.float32)
+    nn, nu, fr = (np.empty(B, np.int32) for _ in range(3))
+    ip = ctypes.POINTER(ctypes.c_int32)
+    u64 = 0xFFFFFFFFFFFFFFFF
+    args = (int(model), B, int(seed) & u64, int(set_offset) & u64, np.float32(gamma), _fptr(out), nn.ctypes.data_as(ip), nu.ctypes.data_as(ip))
+    rc = lib().oracle_prior_rows_first_reject(*args, fr.ctypes.data_as(ip)) if want_first_reject else lib().oracle_prior_rows(*args)
+    if rc != 0:
+        raise ValueError(f"oracle_prior_rows rc={rc}")
+    res = (out,) + ((nn, nu) if want_counts or want_first_reject else ()) + ((fr,) if want_first_reject else ())
+    return res[0] if len(res) == 1 else res
