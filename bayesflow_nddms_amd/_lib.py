@@ -46,6 +46,8 @@ def _declare(L):
     L.nddm_wiener_log_likelihood_grad.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_uint32, fp, fp, vp]
     L.nddm_wiener_marginal_log_likelihood.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_float, c.c_uint32, fp, fp, vp]
     L.nddm_wiener_marginal_log_likelihood_grad.argtypes = [c.c_int32, fp, c.c_int64, c.c_int64, fp, c.c_int32, c.c_float, c.c_uint32, fp, fp, vp]
+    L.nddm_wiener_marginal_log_likelihood_ragged.argtypes = [c.c_int32, fp, c.c_int32, c.c_int64, c.c_int64, fp, c.c_int32, fp, c.c_float, c.c_uint32,
+                                                             fp, fp, vp]
     L.nddm_wiener_hmc.argtypes = [c.c_int32, fp, c.c_int64, c.c_int32, c.c_int64, c.c_int64, fp, fp, c.c_int32, c.c_int32, c.c_int32, c.c_int32,
                                   c.c_uint32, c.c_uint64, c.c_uint64, c.c_uint64, c.c_uint32, fp, fp, fp, fp, fp, vp]
     L.nddm_wiener_hmc_joint.argtypes = [c.c_int32, fp, c.c_int64, c.c_int32, c.c_int64, c.c_int64, fp, fp, fp, fp, fp, c.c_int32, c.c_int32, c.c_int32,
@@ -80,7 +82,7 @@ EXPORTS = [
     "nddm_graph_arena_create", "nddm_graph_arena_bind", "nddm_graph_arena_info", "nddm_graph_arena_release", "nddm_build_info",
     "nddm_simulratcliff", "nddm_wiener_log_likelihood", "nddm_wiener_cdf", "nddm_wiener_quantile",
     "nddm_wiener_log_likelihood_grad", "nddm_wiener_marginal_log_likelihood", "nddm_wiener_marginal_log_likelihood_grad",
-    "nddm_wiener_hmc", "nddm_wiener_hmc_joint", "nddm_set_queue_split",
+    "nddm_wiener_hmc", "nddm_wiener_hmc_joint", "nddm_set_queue_split", "nddm_wiener_marginal_log_likelihood_ragged",
 ]
 
 

@@ -1215,6 +1215,40 @@ def resample_draws(theta, M, log_w=None, weights=None, words=None, seed=0, want_
     return res
 
 
+class SingleTrialTarget:
+    """What posterior_importance(..., target=...) weighs the draws against: the single-trial model's MARGINAL likelihood (the latent
+    per-trial boundary integrated out, engine.wiener_marginal_log_likelihood) under its prior RESTRICTED to the rows that likelihood's
+    accuracy is stated on (priors.restricted_density, priors.MARGINAL_DOMAIN).  Made by single_trial_target."""
+
+    def __init__(self, t_censor, gamma, domain):
+        from . import priors
+        self.t_censor, self.gamma = t_censor, gamma
+        self.model, self.num_params = ("scale", 8) if gamma is None else ("single", 7)
+        self.domain = dict(domain)
+        self.density = priors.restricted_density(self.model, self.domain)
+
+    def __repr__(self):
+        return f"SingleTrialTarget(t_censor={self.t_censor!r}, gamma={self.gamma!r}, domain={self.domain!r})"
+
+
+def single_trial_target(t_censor, gamma=1.0, domain=None):
+    """The target of posterior_importance / sample_exact for the single-trial model (single_trial_alpha_not_scaled): its marginal
+    likelihood and its restricted prior.
+
+    t_censor: the decision time a timeout (choicert == 0) is censored at, the simulator's max_steps * dt, >= 0; None or 0: a timeout
+    has no likelihood, its draws' weights are NaN and counted in "n_nan".  gamma: 1.0 -- the reference's main model, a 7-column flow
+    (drift, mu_alpha, beta, ter, std_alpha, dc, sigma1), gamma fixed at 1 -- or None: the flow's 8th column is gamma ("scale", gamma ~
+    U(0, 2)).  Another fixed gamma is not covered: the kernel's 7-column row is gamma = 1.  domain: None (priors.MARGINAL_DOMAIN) or
+    lower bounds of std_alpha, dc, sigma1 by name, as priors.restricted_density takes them."""
+    from . import priors
+    tc = 0.0 if t_censor is None else float(t_censor)
+    if math.isnan(tc) or tc < 0:
+        raise ValueError("t_censor must be >= 0 (or None: timeouts then have no likelihood)")
+    if gamma is not None and float(gamma) != 1.0:
+        raise ValueError("gamma must be 1.0 (a 7-column flow, gamma fixed at 1) or None (the flow's 8th column is gamma)")
+    return SingleTrialTarget(tc, None if gamma is None else 1.0, priors.MARGINAL_DOMAIN if domain is None else domain)
+
+
 def observed_batch(datasets, device=None):
     """Observed data sets of DIFFERENT trial counts -- a sequence of arrays [n_b, d], a participant each -- as ONE amortizer input:
     {"summary_conditions": float32 [B, max n_b, d], set b's trials first and ZEROS after them; "summary_counts": int32 [B], the n_b;
@@ -1442,7 +1476,7 @@ class AmortizedPosterior(nn.Module):
 
     @torch.no_grad()
     def posterior_importance(self, input_dict, n_samples, model="basic", z_bytes=64 << 20, keep_draws=False, keep_weights=False, probs=None,
-                             smooth=False, resample=None, resample_seed=0, _resampled_on_device=False):
+                             smooth=False, resample=None, resample_seed=0, _resampled_on_device=False, target=None):
         """The amortizer's draws importance-weighted against the EXACT posterior of every data set (importance_weights: log w =
         log p(data | theta) + log p(theta) - log q(theta | data)), without the draws leaving the device:
         {"mean", "std" [B, P]: the weighted posterior moments -- a consistent estimate of the exact posterior's, whatever the
@@ -1487,21 +1521,52 @@ class AmortizedPosterior(nn.Module):
         draws they are, and "resample_seed".  Each launch's draws and log weights go through one more kernel (csrc/train_resample.hip, up
         to 16 384 draws and M <= 2^20; the torch evaluation beyond) on the same stream before the next launch overwrites them.  Every
         other number keeps its bits, and torch's random stream is consumed exactly as without the option.  (_resampled_on_device:
-        sample_exact's -- "resampled" stays a device tensor instead of making the way to the host.)"""
-        if model != "basic":
-            raise NotImplementedError(f"posterior_importance scores model='basic' only; for {model!r} the next step is the marginal "
-                                      "likelihood, likelihood.single_trial_logpdf, as the target")
+        sample_exact's -- "resampled" stays a device tensor instead of making the way to the host.)
+
+        target: None (the default: the call above, its keys, bits, launches, allocations and use of torch's random stream) or a
+        single_trial_target(t_censor, gamma) -- the single-trial model (`model` is then the target's).  summary_conditions are its
+        (choicert, z1) [B, N, 2]; the flow has 7 columns (gamma = 1) or 8 (gamma=None), ValueError otherwise.  The likelihood launch is
+        the marginal one, one quadrature per (draw, trial), on the draws as the sampler leaves them -- the kernel reads 7-column rows --
+        and "summary_counts", if present, goes to it as a trial count per set: the padding is never read, whatever it holds.  THE
+        PRIOR IS THE RESTRICTED ONE, priors.restricted_density(target.model): std_alpha >= 0.02, dc >= 0.05, sigma1 >= 0.02, the rows
+        the marginal kernel's accuracy is stated on; a draw outside has weight 0 and is counted in "n_zero".  The result gains
+        "domain", those lower bounds, and every number -- "log_evidence" too -- is that of the RESTRICTED model: the posterior given
+        that the parameters lie in the domain, not the reference prior's.  A timeout in the data with t_censor 0 gives NaN
+        likelihoods, counted in "n_nan".  Everything after the weights (probs, smooth, resample, keep_*) is the path above."""
+        if target is None:
+            if model != "basic":
+                raise NotImplementedError(f"posterior_importance scores model='basic' only; for {model!r} the next step is the marginal "
+                                          "likelihood, likelihood.single_trial_logpdf, as the target")
+        else:
+            if not isinstance(target, SingleTrialTarget):
+                raise TypeError("target must be None or a single_trial_target(...)")
+            if model not in ("basic", target.model):
+                raise ValueError(f"model {model!r} contradicts the target's {target.model!r}")
+            if self.inference_net.num_params != target.num_params:
+                raise ValueError(f"the target (gamma={target.gamma!r}) takes a flow of {target.num_params} parameters; this one has "
+                                 f"{self.inference_net.num_params}")
+            shape = tuple(getattr(input_dict["summary_conditions"], "shape", ()))
+            if len(shape) != 3 or shape[2] != 2:
+                raise ValueError(f"the single-trial model's summary_conditions are (choicert, z1) trials [B, N, 2], got {shape}")
         from . import engine, priors
+        if target is not None:
+            try:
+                engine.require_device()
+            except ImportError as e:                                    # (no library: the same refusal as no device)
+                raise RuntimeError(f"posterior_importance with a target needs the HIP library and a ROCm GPU: {e}") from e
         if probs is not None:
             probs = np.asarray(probs, dtype=np.float64).reshape(-1)
             if probs.size == 0 or not np.all((probs >= 0.0) & (probs <= 1.0)):
                 raise ValueError("probs must be probabilities in [0, 1]")
         if resample is not None and int(resample) < 1:
             raise ValueError("resample must be None or a number of draws M >= 1")
-        table = priors.prior_table(model)
+        table = priors.prior_table(model if target is None else target.density)
         cond = self._conditions(input_dict)
         data = self._t(input_dict["summary_conditions"])
         B, P, dev, net, S = cond.shape[0], self.inference_net.num_params, cond.device, self.inference_net, int(n_samples)
+        counts = None
+        if target is not None and input_dict.get("summary_counts", None) is not None:
+            counts = InvariantNetwork._set_counts(input_dict["summary_counts"], B, data.shape[1], dev)
         if table.shape[0] != P or data.dim() != 3 or data.shape[0] != B or data.shape[2] != 2:
             raise ValueError(f"model {model!r} has {table.shape[0]} parameters and (rt, choice) trials [B, N, 2]; the network has {P} and "
                              f"summary_conditions are {tuple(data.shape)}")
@@ -1530,8 +1595,13 @@ class AmortizedPosterior(nn.Module):
             else:
                 th, lq = net.inverse_with_log_density(z, c.repeat_interleave(S, dim=0))
                 th, lq = th.reshape(nb, S, P).contiguous(), lq.reshape(nb, S).contiguous()
-            ll = engine.wiener_log_likelihood(engine.BASIC_DDM_DC, th.view(nb * S, P), data[b0:b0 + nb], draws_per_dataset=S,
-                                              device=dev)["loglik"].view(nb, S)
+            if target is None:
+                ll = engine.wiener_log_likelihood(engine.BASIC_DDM_DC, th.view(nb * S, P), data[b0:b0 + nb], draws_per_dataset=S,
+                                                  device=dev)["loglik"].view(nb, S)
+            else:
+                ll = engine.wiener_marginal_log_likelihood(engine.SINGLE_TRIAL, th.view(nb * S, P), data[b0:b0 + nb], draws_per_dataset=S,
+                                                           t_censor=target.t_censor, device=dev,
+                                                           counts=None if counts is None else counts[b0:b0 + nb])["loglik"].view(nb, S)
             out_w = {k: v[b0:b0 + nb] for k, v in res.items()}
             if scratch_w is not None:
                 out_w["log_w"] = scratch_w[:nb]
@@ -1558,6 +1628,8 @@ class AmortizedPosterior(nn.Module):
                 kept_w.append(w["log_w"] if scratch_w is None else w["log_w"].clone())
         out = {("std" if k == "sd" else k): v.cpu().numpy() for k, v in res.items()}
         out["n_samples"] = S
+        if target is not None:
+            out["domain"] = dict(target.domain)
         if smooth:
             out["raw"] = {k: out[k] for k in ("mean", "std", "ess", "max_share", "log_evidence")}
             out.update({("std" if k == "sd" else k): res_s[k].cpu().numpy() for k in ("mean", "sd", "ess", "max_share", "log_evidence")})
@@ -1582,17 +1654,18 @@ class AmortizedPosterior(nn.Module):
         return out
 
     @torch.no_grad()
-    def sample_exact(self, input_dict, n_samples, n_proposals=None, smooth=True, seed=0, to_numpy=True):
+    def sample_exact(self, input_dict, n_samples, n_proposals=None, smooth=True, seed=0, to_numpy=True, target=None):
         """Draws of the EXACT posterior of every data set: [n_samples, P] for a single data set, [B, n_samples, P] for a batch, as
         `sample` -- n_proposals (default: n_samples) draws of the flow, importance-weighted against the exact Wiener likelihood and
         resampled into n_samples equally weighted ones (posterior_importance(..., resample=n_samples, resample_seed=seed); smooth:
         on the Pareto-smoothed weights).  For joint plots, correlations, posterior-predictive simulation, starting points of fit_hmc.
         Whether to believe them is in `self.last_exact`: "ess" and "n_unique" [B] (how many of the proposals carry the weight, and how
-        many different rows came back), and with smooth "pareto_k" [B] against "k_threshold" (else None).  model="basic" only, as
-        posterior_importance; a ragged batch (`observed_batch`) needs nothing more."""
+        many different rows came back), and with smooth "pareto_k" [B] against "k_threshold" (else None).  model="basic", as
+        posterior_importance; a ragged batch (`observed_batch`) needs nothing more.  target: None, or a single_trial_target(...) --
+        the single-trial model's posterior under its restricted prior (posterior_importance's `target`)."""
         S = int(n_samples if n_proposals is None else n_proposals)
         r = self.posterior_importance(input_dict, S, smooth=smooth, resample=int(n_samples), resample_seed=seed,
-                                      _resampled_on_device=not to_numpy)
+                                      _resampled_on_device=not to_numpy, target=target)
         self.last_exact = {"ess": r["ess"], "n_unique": r["n_unique"], "pareto_k": r.get("pareto_k"), "k_threshold": r.get("k_threshold"),
                            "n_proposals": S}
         out = r["resampled"]

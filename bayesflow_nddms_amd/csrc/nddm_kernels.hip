@@ -1331,6 +1331,23 @@ int nddm_wiener_marginal_log_likelihood(int32_t model, const float *params, int6
                          out_trial || out_sum, stream, A, K);
 }
 
+/* the same marginal log-likelihood with a trial count per data set and rows of 7 (gamma = 1) or 8 columns: the ragged instantiations of
+ * csrc/nddm_wiener_marginal.h's kernel.  param_cols is checked where the flags are (NDDM_ERR_PARAM). */
+int nddm_wiener_marginal_log_likelihood_ragged(int32_t model, const float *params, int32_t param_cols, int64_t R, int64_t draws_per_dataset,
+                                               const float *data, int32_t n_trials, const int32_t *set_counts, float t_censor, uint32_t flags,
+                                               float *out_trial, double *out_sum, void *stream)
+{
+    using namespace nddm;
+    static const WienerEntry E = {"nddm_wiener_marginal_log_likelihood_ragged: model %s has no marginal likelihood here (NDDM_SINGLE_TRIAL only)",
+                                  "nddm_wiener_marginal_log_likelihood_ragged: flags must be 0 (reserved) and param_cols 7 or 8%s", WIENER_SHAPE_MSG,
+                                  WIENER_NULL_IN_MSG, WIENER_NULL_OUT_MSG, "wiener ragged marginal kernel launch failed: %s", WMARG_ROWS};
+    static void (*const K[2])(WienerMarginalRaggedArgs) = {wiener_marginal_kernel<false, true>, wiener_marginal_kernel<true, true>};
+    WienerMarginalRaggedArgs A;
+    A.out_trial = out_trial; A.out_sum = out_sum; A.t_censor = t_censor; A.cols = param_cols; A.counts = set_counts;
+    return wiener_launch(E, model, model == NDDM_SINGLE_TRIAL, flags == 0u && (param_cols == 7 || param_cols == 8), params, data, R,
+                         draws_per_dataset, n_trials, params && data, out_trial || out_sum, stream, A, K);
+}
+
 /* the value and the gradient of the single-trial model's marginal log-likelihood in one launch: csrc/nddm_wiener_marginal_grad.h.
  * out_loglik may be NULL. */
 int nddm_wiener_marginal_log_likelihood_grad(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,

@@ -331,12 +331,19 @@ __device__ __forceinline__ WienerWaveRow wiener_wave_row(long long R, long long 
 
 // The head of a kernel's tile loop, `for (int t0 = 0; t0 < N; t0 += WIENER_TILE)`: the number of trials nt <= WIENER_TILE of the tile
 // that begins at t0, after the workgroup has staged them (STAGED: every thread of the workgroup gets here; rbase tells the data set)
+// A data set may hold fewer trials than its stride: the sweep is over `n` <= N trials of a set whose rows lie N pairs apart (the ragged
+// marginal kernel; n must be workgroup-uniform when STAGED, the staging barrier is every thread's).  The others sweep all N.
+template <bool STAGED>
+__device__ __forceinline__ int wiener_enter_tile(float2 *tile, const float *data, long long S, int N, int n, long long rbase, int t0)
+{
+    const int nt = n - t0 < WIENER_TILE ? n - t0 : WIENER_TILE;
+    if (STAGED) wiener_stage_tile(tile, wiener_pairs(data, S, N, rbase, t0), nt);
+    return nt;
+}
 template <bool STAGED>
 __device__ __forceinline__ int wiener_enter_tile(float2 *tile, const float *data, long long S, int N, long long rbase, int t0)
 {
-    const int nt = N - t0 < WIENER_TILE ? N - t0 : WIENER_TILE;
-    if (STAGED) wiener_stage_tile(tile, wiener_pairs(data, S, N, rbase, t0), nt);
-    return nt;
+    return wiener_enter_tile<STAGED>(tile, data, S, N, N, rbase, t0);
 }
 
 // A lane's pairs of one row in one tile: f(i, x0, x1) for the trials t0 + i, i = lane, lane + 64, ... below nt, in that order.
@@ -361,14 +368,20 @@ __device__ __forceinline__ void wiener_tile_trials(const float2 *tile, const flo
 }
 
 // The whole sweep of a wave's one row: every tile staged by all, and f(t, x0, x1) for the lane's trials t = lane, lane + 64, ... below N
-// in the waves that have a row
+// in the waves that have a row.  With a sweep length `n` of its own: the trials below n <= N of a set N pairs long (wiener_enter_tile).
+template <bool STAGED, bool PREFETCH, class F>
+__device__ __forceinline__ void wiener_row_trials(float2 *tile, const float *data, long long S, int N, int n, const WienerWaveRow &w, int lane,
+                                                  const F &f)
+{
+    for (int t0 = 0; t0 < n; t0 += WIENER_TILE) {
+        const int nt = wiener_enter_tile<STAGED>(tile, data, S, N, n, w.rbase, t0);
+        if (w.has_row) wiener_tile_trials<STAGED, PREFETCH>(tile, data, S, N, w.row, t0, nt, lane, [&](int i, float x0, float x1) { f(t0 + i, x0, x1); });
+    }
+}
 template <bool STAGED, bool PREFETCH, class F>
 __device__ __forceinline__ void wiener_row_trials(float2 *tile, const float *data, long long S, int N, const WienerWaveRow &w, int lane, const F &f)
 {
-    for (int t0 = 0; t0 < N; t0 += WIENER_TILE) {
-        const int nt = wiener_enter_tile<STAGED>(tile, data, S, N, w.rbase, t0);
-        if (w.has_row) wiener_tile_trials<STAGED, PREFETCH>(tile, data, S, N, w.row, t0, nt, lane, [&](int i, float x0, float x1) { f(t0 + i, x0, x1); });
-    }
+    wiener_row_trials<STAGED, PREFETCH>(tile, data, S, N, N, w, lane, f);
 }
 
 // The sum of the 64 lanes' values in the butterfly's order (a + b == b + a: every lane ends with the same bits)

@@ -45,6 +45,8 @@
 // parameters, its data set, n_trials, t_censor) alone.  The 32 node values of a pass live in LDS (32 KB per workgroup, lane-interleaved: no
 // bank conflict), not in 32 registers of an unrolled loop.  No scratch memory, no atomics; stores are plain vector stores.
 #pragma once
+#include <type_traits>
+
 #include "nddm_wiener.h"
 
 namespace nddm {
@@ -223,9 +225,28 @@ __device__ __forceinline__ float wiener_marginal_trial(const WienerRow &b, const
     return out * r.valid * b.valid;
 }
 
-// STAGED: the workgroup's rows all score one data set, read from LDS (broadcast layout); else every row reads its own (paired layout)
-template <bool STAGED>
-__global__ __launch_bounds__(256) void wiener_marginal_kernel(WienerMarginalArgs G)
+// The ragged entry point's arguments (nddm_wiener_marginal_log_likelihood_ragged): WienerMarginalArgs' fields in their places, then its own.
+// A struct of its own, so that the two kernels of the plain entry point keep their kernel-argument segment and their code.
+struct WienerMarginalRaggedArgs {
+    const float *params;        // [R, cols]
+    const float *data;          // [D, N, 2] = (choicert, z1); set d's pairs at and beyond counts[d] are never read
+    float *out_trial;           // [R, N] or NULL
+    double *out_sum;            // [R] or NULL
+    long long R, S;
+    long long chunks;
+    int N, P;                   // N: the padded length, the stride of data and out_trial; P: the model's 8 (wiener_launch's; unused)
+    float t_censor;
+    int cols;                   // 7 (gamma = 1) or 8
+    const int *counts;          // [D] trials per set or NULL (every set has N)
+};
+
+// STAGED: the workgroup's rows all score one data set, read from LDS (broadcast layout); else every row reads its own (paired layout).
+// RAGGED: a trial count per data set and rows of 7 or 8 columns (WienerMarginalRaggedArgs): instantiations of their own.  A row sweeps the
+// trials below its set's count n in the order a call at n_trials = n would, so its sum has that call's bits; out_trial beyond n is 0.  A
+// count outside [1, N] reads no data and gives NaN in the row's sum and its N per-trial values.  Broadcast layout: the workgroup's rows
+// share one set, so n is a function of blockIdx alone and the staging barriers stay uniform; paired: no barrier, a count per wave.
+template <bool STAGED, bool RAGGED = false>
+__global__ __launch_bounds__(256) void wiener_marginal_kernel(typename std::conditional<RAGGED, WienerMarginalRaggedArgs, WienerMarginalArgs>::type G)
 {
     __shared__ float2 tile[STAGED ? WIENER_TILE : 1];
     __shared__ float nodes[WMARG_K * 256];                              // a pass's node values, [k][thread]
@@ -233,7 +254,24 @@ __global__ __launch_bounds__(256) void wiener_marginal_kernel(WienerMarginalArgs
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const WienerWaveRow w = wiener_wave_row<STAGED, WMARG_ROWS>(G.R, G.S, G.chunks, wave);
     if (!STAGED && !w.has_row) return;
-    const float *p = G.params + w.row * G.P;
+    float q[8];                                                         // (RAGGED: the row as 8 columns, registers)
+    const float *p;
+    int n = G.N;                                                        // the trials the row sweeps
+    bool count_ok = true;
+    if constexpr (RAGGED) {
+        const float *src = G.params + w.row * G.cols;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) q[j] = src[j];
+        q[7] = G.cols == 8 ? src[7] : 1.0f;
+        p = q;
+        if (G.counts) {
+            const int c = G.counts[(STAGED ? w.rbase : w.row) / G.S];   // (STAGED: one scalar load per workgroup, rbase is blockIdx's)
+            count_ok = c >= 1 && c <= G.N;
+            n = count_ok ? c : 0;
+        }
+    } else {
+        p = G.params + w.row * G.P;
+    }
     // every lane works out the row's constants; the wave keeps lane 0's copy as uniform values
     WienerRow b;
     WienerMarginalRow r;
@@ -250,13 +288,23 @@ __global__ __launch_bounds__(256) void wiener_marginal_kernel(WienerMarginalArgs
     float *buf = nodes + threadIdx.x;
     double s = 0.0;
     float *dst = G.out_trial ? G.out_trial + w.row * (long long)G.N : nullptr;
-    wiener_row_trials<STAGED, false>(tile, G.data, G.S, G.N, w, lane, [&](int t, float x0, float x1) {
+    const auto trial = [&](int t, float x0, float x1) {
         const float lf = wiener_marginal_trial(b, r, x0, x1, G.t_censor, buf, 256);
         if (dst) dst[t] = lf;
         s += (double)lf;
-    });
+    };
+    if constexpr (RAGGED) {
+        wiener_row_trials<STAGED, false>(tile, G.data, G.S, G.N, n, w, lane, trial);
+        if (dst && w.has_row) {                                         // the padding's values: 0, or NaN under an invalid count
+            const float fill = count_ok ? 0.0f : __builtin_nanf("");
+            for (int t = n + lane; t < G.N; t += 64) dst[t] = fill;
+        }
+    } else {
+        wiener_row_trials<STAGED, false>(tile, G.data, G.S, G.N, w, lane, trial);
+    }
     if (!G.out_sum || !w.has_row) return;
     s = wiener_wave_sum(s);
+    if (RAGGED && !count_ok) s = __builtin_nan("");
     if (lane == 0) G.out_sum[w.row] = s;
 }
 

@@ -360,12 +360,13 @@ def _marginal_check_params(p_np):
         raise ValueError("ter must be >= 0")
 
 
-def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs, requests=False, marginal=False):
+def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs, requests=False, marginal=False, cols=None):
     """The front end wiener_log_likelihood, wiener_cdf, wiener_quantile and wiener_marginal_log_likelihood share: host inputs are refused
     here (ValueError), before any device work; a device tensor's shape is checked where it is cast, after the split.  -> (S, params' and
     data's row descriptions, the host arrays or None, R).  `what`: the quantity the model would have to have a closed form of; `outputs`:
     the caller's output switches by name; `requests`: `data` holds wiener_quantile's (p, boundary code) pairs instead of trials;
-    `marginal`: the caller integrates SINGLE_TRIAL's latent boundary out -- that model and no other, its columns and (choicert, z1) data."""
+    `marginal`: the caller integrates SINGLE_TRIAL's latent boundary out -- that model and no other, its columns and (choicert, z1) data;
+    `cols`: the columns params has instead of the model's own (the marginal's 7-column rows, gamma = 1)."""
     if marginal:
         if model != SINGLE_TRIAL:
             raise ValueError(f"model {model} has no {what} here (SINGLE_TRIAL only)")
@@ -376,7 +377,8 @@ def _wiener_host_checks(model, params, data, draws_per_dataset, what, outputs, r
     S = int(draws_per_dataset)
     if S <= 0:
         raise ValueError("draws_per_dataset must be > 0")
-    p_rows = (2, NPARAMS[model], f"params must have shape [R, {NPARAMS[model]}]")
+    P = NPARAMS[model] if cols is None else cols
+    p_rows = (2, P, f"params must have shape [R, {P}]")
     d_rows = (3, 2, "probs must have shape [D, n, 2]" if requests else "data must have shape [D, n_trials, 2]")
     p_np = _host_rows(params, *p_rows)
     if p_np is not None:
@@ -436,7 +438,25 @@ def wiener_log_likelihood(model, params, data, draws_per_dataset=1, per_trial=Fa
         lambda L, p, d, N, o, st: _lib.check(L.nddm_wiener_log_likelihood(int(model), p, R, S, d, N, 0, o["trial_logp"], o["loglik"], st)))
 
 
-def wiener_marginal_log_likelihood(model, params, data, draws_per_dataset=1, t_censor=None, per_trial=False, want_sum=True, device=None):
+def _marginal_cols(params):
+    """7 for a DEVICE tensor whose last dimension is 7 (rows without gamma, gamma = 1: the flow's draws, which the kernel reads as they
+    are instead of an [R, 8] copy); else None, the model's own 8 -- a host array has its gamma column appended on the host for free
+    (single_trial_alpha_not_scaled._with_gamma) and keeps the one documented shape, whose check names a wrong one."""
+    return 7 if getattr(params, "is_cuda", False) and params.dim() >= 1 and int(params.shape[-1]) == 7 else None
+
+
+def _host_counts(counts, D, N):
+    """Host-side trial counts per data set -> int32 [D], each in [1, N] (ValueError otherwise, as InvariantNetwork._set_counts refuses
+    them): no device work."""
+    c = np.asarray(counts.cpu() if hasattr(counts, "cpu") else counts)
+    if c.ndim != 1 or c.shape[0] != D or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"counts must be integers [D = {D}], got {c.dtype} {c.shape}")
+    if np.any(c < 1) or np.any(c > N):
+        raise ValueError(f"counts must lie in [1, n_trials = {N}]")
+    return c.astype(np.int32)
+
+
+def wiener_marginal_log_likelihood(model, params, data, draws_per_dataset=1, t_censor=None, per_trial=False, want_sum=True, device=None, counts=None):
     """Marginal log-likelihood of observed trials under the single-trial model, the latent per-trial boundary integrated out (include/nddm.h:
     nddm_wiener_marginal_log_likelihood), one kernel launch.
 
@@ -444,17 +464,43 @@ def wiener_marginal_log_likelihood(model, params, data, draws_per_dataset=1, t_c
     2] in the simulator's output format, R = D * draws_per_dataset, row r scored against data set r // draws_per_dataset.  t_censor: the
     decision time a timeout (choicert == 0) is censored at, the simulator's max_steps * dt; None: timeouts give NaN.
     Returns a dict of device tensors: 'loglik' float64 [R] (want_sum) and 'trial_logp' float32 [R, n_trials] (per_trial).
-    Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN."""
+    Host arrays are shape- and range-checked (ValueError); device tensors go to the kernel as they are, where an invalid row gives NaN.
+
+    A device tensor params [R, 7] (no gamma column: gamma = 1, the bits of the 8-column row with 1.0f; host arrays are [R, 8]) and counts (None, or a trial count per data set,
+    integers [D]: set d's rows score its first counts[d] trials only, the data beyond are never read, 'trial_logp' is 0 there, and
+    'loglik' has the bits of a call on that set alone at n_trials = counts[d]) go through nddm_wiener_marginal_log_likelihood_ragged, the
+    same kernel instantiated for them; without either the call is the one above.  Host-side counts outside [1, n_trials] are refused
+    (ValueError); a device tensor passes through, and a count outside gives NaN in that set's rows."""
+    cols = _marginal_cols(params)
     checked = _wiener_host_checks(model, params, data, draws_per_dataset, "marginal likelihood", {"per_trial": per_trial, "want_sum": want_sum},
-                                  marginal=True)
+                                  marginal=True, cols=cols)
     S, R = checked[0], checked[-1]
     tc = 0.0 if t_censor is None else float(t_censor)
     if math.isnan(tc) or tc < 0:
         raise ValueError("t_censor must be >= 0 (or None: timeouts then give NaN)")
-    return _wiener_device_call(
-        checked, params, data, device, [("loglik", want_sum, (R,), "float64"), ("trial_logp", per_trial, (R, None), "float32")],
-        lambda L, p, d, N, o, st: _lib.check(L.nddm_wiener_marginal_log_likelihood(int(model), p, R, S, d, N, tc, 0, o["trial_logp"], o["loglik"],
-                                                                                   st)))
+    outputs = [("loglik", want_sum, (R,), "float64"), ("trial_logp", per_trial, (R, None), "float32")]
+    if cols is None and counts is None:
+        return _wiener_device_call(
+            checked, params, data, device, outputs,
+            lambda L, p, d, N, o, st: _lib.check(L.nddm_wiener_marginal_log_likelihood(int(model), p, R, S, d, N, tc, 0, o["trial_logp"], o["loglik"],
+                                                                                       st)))
+    c_dev = None
+    if counts is not None:
+        D, N = R // S, int((checked[4] if checked[4] is not None else data).shape[-2])
+        on_device = bool(getattr(counts, "is_cuda", False))
+        if on_device and (counts.dim() != 1 or counts.shape[0] != D or counts.is_floating_point()):
+            raise ValueError(f"counts must be an integer tensor [D = {D}], got {counts.dtype} {tuple(counts.shape)}")
+        c_host = None if on_device else _host_counts(counts, D, N)      # refused here, before any device work
+        torch = require_device()
+        dev = _device(device)
+        c_dev = counts.to(dev, torch.int32).contiguous() if on_device else torch.as_tensor(c_host, device=dev)
+
+    def call(L, p, d, N, o, st):
+        _lib.check(L.nddm_wiener_marginal_log_likelihood_ragged(int(model), p, 8 if cols is None else cols, R, S, d, N, _ptr(c_dev), tc, 0,
+                                                                o["trial_logp"], o["loglik"], st))
+        if c_dev is not None:
+            c_dev.record_stream(require_device().cuda.current_stream(c_dev.device))
+    return _wiener_device_call(checked, params, data, device, outputs, call)
 
 
 WHMC_STATE, WHMC_MAX_TRIALS, WHMC_MAX_ROUNDS = 12, 2048, 1 << 19

@@ -119,6 +119,33 @@ def prior_table(model="basic"):
     return np.asarray(rows, dtype=np.float64)
 
 
+# The rows the marginal likelihood's accuracy is stated on (tests/wiener_marginal_ref.py: _prior_pool, DEVICE_BAR): lower bounds by column
+# name.  An importance sampler sends the likelihood its proposal's tail draws, so its target is the posterior under the prior restricted
+# to these rows (restricted_density), and says so.
+MARGINAL_DOMAIN = {"std_alpha": 0.02, "dc": 0.05, "sigma1": 0.02}
+_SINGLE_COLUMNS = ("drift", "mu_alpha", "beta", "ter", "std_alpha", "dc", "sigma1", "gamma")
+
+
+def restricted_density(model, lows=MARGINAL_DOMAIN):
+    """PRIOR_DENSITY[model] ("single": 7 columns; "scale": 8, gamma ~ U(0, 2)) with the lower end of the named columns RAISED to lows[name]
+    (never lowered): a description prior_table and log_prior_density accept, which renormalise the truncated normals and the uniform
+    themselves -- the prior conditioned on the rows inside, a proper density.  lows: {column name: lower bound} over std_alpha, dc, sigma1."""
+    if model not in ("single", "scale"):
+        raise ValueError(f"restricted_density covers the single-trial models 'single' and 'scale', not {model!r}")
+    unknown = set(lows) - set(_SINGLE_COLUMNS[4:7])
+    if unknown:
+        raise ValueError(f"lower bounds may be given for std_alpha, dc and sigma1, not {sorted(unknown)}")
+    out = []
+    for name, col in zip(_SINGLE_COLUMNS, PRIOR_DENSITY[model]):
+        if name in lows:
+            low = max(float(lows[name]), float(col[-2]))
+            if not low < float(col[-1]):
+                raise ValueError(f"the lower bound of {name} must lie below its upper end {col[-1]}")
+            col = col[:-2] + (low, col[-1])
+        out.append(col)
+    return tuple(out)
+
+
 def log_prior_density(model, theta):
     """log p(theta) under the model's prior, float64: theta [..., P] -> [...], the sum over the columns of prior_table(model)'s
     densities; -inf where a component is outside its support or not finite.  The host definition of what the importance kernel

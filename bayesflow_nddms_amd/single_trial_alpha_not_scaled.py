@@ -54,13 +54,16 @@ def simulate_trials(params, n_trials, dt=.01, max_steps=400., seed=None, set_off
     return r["trials"][0].cpu().numpy().astype(np.float64)
 
 
-def log_likelihood(params, sim_data, dt=.01, max_steps=400., gamma=1.0, device=None):
+def log_likelihood(params, sim_data, dt=.01, max_steps=400., gamma=1.0, device=None, counts=None):
     """Marginal log-likelihood of simulated (or observed) trials, the per-trial boundary integrated out: params [7] or [B, 7] (gamma
     appended, as the simulators here do) or [B, 8] (the _scale layout, gamma last); sim_data [n_trials, 2] or [B, n_trials, 2] = (choicert,
     z1) as simulate_trials / batch_simulate_trials return them.  A missing response (choicert 0) is censored at the simulator's decision-time
-    cap max_steps * dt: pass the dt and max_steps the data were simulated with.  -> float64 device tensor [B] (engine.wiener_marginal_log_likelihood)."""
+    cap max_steps * dt: pass the dt and max_steps the data were simulated with.  counts: None, or a trial count per data set (integers [B]:
+    sets of different lengths padded to one, `amortizer.observed_batch`'s "summary_counts"; the padding is never read).
+    -> float64 device tensor [B] (engine.wiener_marginal_log_likelihood)."""
     tc = float(engine.max_k_of(max_steps)) * float(dt)
-    return engine.wiener_marginal_log_likelihood(engine.SINGLE_TRIAL, _with_gamma(params, gamma), sim_data, t_censor=tc, device=device)["loglik"]
+    return engine.wiener_marginal_log_likelihood(engine.SINGLE_TRIAL, _with_gamma(params, gamma), sim_data, t_censor=tc, device=device,
+                                                 counts=counts)["loglik"]
 
 
 def log_likelihood_and_grad(params, sim_data, dt=.01, max_steps=400., gamma=1.0, device=None):

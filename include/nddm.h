@@ -77,6 +77,7 @@ extern "C" {
 /* 4 (additive): nddm_wiener_hmc_joint.  No existing entry point changes. */
 /* 4 (additive): NDDM_WIENER_CENSORED (flag 4 of nddm_wiener_log_likelihood_grad, nddm_wiener_hmc and nddm_wiener_hmc_joint).  With the
  *    flag clear no output changes. */
+/* 4 (additive): nddm_wiener_marginal_log_likelihood_ragged.  No existing entry point changes. */
 #define NDDM_ABI_VERSION 4
 #define NDDM_SUMMARY_K 10
 
@@ -413,6 +414,26 @@ int nddm_wiener_hmc_joint(int32_t model, const float *data /* [P, n_trials, 2] *
 int nddm_wiener_marginal_log_likelihood(int32_t model, const float *params, int64_t R, int64_t draws_per_dataset, const float *data,
                                         int32_t n_trials, float t_censor, uint32_t flags /* 0, reserved */,
                                         float *out_trial /* [R, n_trials] or NULL */, double *out_sum /* [R] or NULL */, void *stream);
+
+/* The same marginal log-likelihood for data sets of DIFFERENT trial counts and for rows without the gamma column: what importance weights
+ * of the amortizer's draws need (a 7-column flow, a ragged batch of participants).  (ABI 4, additive)
+ *   model, draws_per_dataset, t_censor, flags, out_trial, out_sum, stream: as nddm_wiener_marginal_log_likelihood takes them
+ *   params, param_cols device f32 [R, param_cols], param_cols 7 or 8 (NDDM_ERR_PARAM otherwise, checked where the flags are).  7: the
+ *                      columns drift .. sigma1 and gamma = 1; the bits are those of the 8-column row with gamma = 1.0f
+ *   data, n_trials     device f32 [D, n_trials, 2]: n_trials is the PADDED length, the stride of data and of out_trial
+ *   set_counts         device i32 [D] or NULL (every set has n_trials trials).  set_counts[d] = n_d: the rows of set d score its trials
+ *                      0 .. n_d - 1 only; data at or beyond n_d are never read (NaN there changes nothing); out_trial[r, t >= n_d] is
+ *                      written as 0; the row's out_sum is BIT FOR BIT nddm_wiener_marginal_log_likelihood's for that set alone at
+ *                      n_trials = n_d.  A count outside [1, n_trials] gives NaN in out_sum and in all n_trials values of out_trial of that
+ *                      set's rows, reads none of its data and leaves the other rows unaffected
+ * With param_cols 8 and set_counts NULL both outputs have nddm_wiener_marginal_log_likelihood's bits.  Special values, the bit property of
+ * out_sum, no scratch memory, no atomics, one capturable kernel node, the error checks, their order and their status codes: that entry
+ * point's; R = 0 is NDDM_OK.  The kernels are instantiations of their own: the plain entry point's are unchanged.  DESIGN.md section 26. */
+int nddm_wiener_marginal_log_likelihood_ragged(int32_t model, const float *params, int32_t param_cols /* 7 or 8 */, int64_t R,
+                                               int64_t draws_per_dataset, const float *data /* [D, n_trials, 2] */,
+                                               int32_t n_trials /* the padded length */, const int32_t *set_counts /* device [D] or NULL */,
+                                               float t_censor, uint32_t flags /* 0, reserved */, float *out_trial /* [R, n_trials] or NULL */,
+                                               double *out_sum /* [R] or NULL */, void *stream);
 
 /* The same marginal log-likelihood AND its gradient in the model's eight parameter columns, one fused launch: what a gradient-based fit of
  * the single-trial model consumes per step (MAP refinement of amortized draws, Laplace / variational fits, HMC / NUTS).  (ABI 4, additive)

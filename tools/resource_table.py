@@ -38,9 +38,9 @@ def pretty(name):
     if m:                                                     # the value-and-gradient kernel, the same two layouts; censored: NDDM_WIENER_CENSORED's
         return (f"wiener_grad_kernel<{MODELS[int(m.group(1))]}, {'broadcast' if m.group(2) == '1' else 'paired'}"
                 f"{', censored' if m.group(3) == '1' else ''}>")
-    m = re.match(r"_ZN4nddm22wiener_marginal_kernelILb(\d)E", name)
-    if m:                                                     # the single-trial model's marginal likelihood, the same two layouts
-        return f"wiener_marginal_kernel<{'broadcast' if m.group(1) == '1' else 'paired'}>"
+    m = re.match(r"_ZN4nddm22wiener_marginal_kernelILb(\d)ELb(\d)E", name)
+    if m:                                                     # the single-trial model's marginal likelihood, the same two layouts; ragged: a count per set
+        return f"wiener_marginal_kernel<{'broadcast' if m.group(1) == '1' else 'paired'}{', ragged' if m.group(2) == '1' else ''}>"
     m = re.match(r"_ZN4nddm27wiener_marginal_grad_kernelILb(\d)E", name)
     if m:                                                     # its value-and-gradient kernel, the same two layouts
         return f"wiener_marginal_grad_kernel<{'broadcast' if m.group(1) == '1' else 'paired'}>"
